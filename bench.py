@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- HE-AAC decode DSP throughput on MI355X (driver contract).
 
-  python bench.py --gpus N --steps K --warmup W [--workload hev2|hev1|lc_stereo]
+  python bench.py --gpus N --steps K --warmup W [--workload hev2|hev1|lc_stereo] [--dump-outputs DIR] [--full]
 
 A "step" is one pass of the hot path over one batch of synthetic frames, inputs
 resident in HBM, state chained from step to step.  N > 1 is launched by
@@ -9,8 +9,15 @@ torch.distributed.run, one rank per GPU; the batch is per-GPU (weak scaling), no
 data-path collective (frames are independent).
 
 Prints ONE JSON line on rank 0 with `roofline` (algorithmic bytes / kernel time,
-HIP-event timed on the launch stream) and `cpu_baseline` (the oracle, timed on the
-host on a bounded sample of the same workload; rank 0, N = 1 only).
+HIP-event timed on the launch stream).  A plain run does only what that line needs:
+set up, warm up, time the steps, write the outputs (--dump-outputs), print.  --full
+adds `cpu_baseline` (the oracle, timed on the host on a bounded sample of the same
+workload; rank 0, N = 1 only).
+
+--dump-outputs DIR writes what the last timed step returned to its caller, on rank 0:
+DIR/pcm.npy and DIR/state.npy (float32) for a fixed, seeded sample of at most
+DUMP_FRAMES frames, whose indices are DIR/frame_index.npy (float64).  Inputs depend
+only on the arguments, so two builds can be compared output for output.
 """
 import argparse
 import importlib
@@ -39,6 +46,9 @@ ALGO_BYTES_OVERRIDE = {"hev2_34": 95788}       # PS state 17 996 B i
 ALGO_FLOPS = {"lc_stereo": 57e3, "hev1": 0.50e6, "hev2": 0.60e6, "hev2_34": 0.68e6}
 # 256 CUs x 4 SIMD-32 x 2.4 GHz, one add or multiply per lane and cycle (no FMA: -ffp-contract=off)
 VALU_NOFMA_PEAK_GFLOPS = 256 * 4 * 32 * 2.4
+# --dump-outputs: frames in the sample (HE-AACv2: 512 x 53.5 KB of PCM + state, 27 MB in all)
+DUMP_FRAMES = 512
+DUMP_SEED = 2024
 
 
 def make_inputs(pkg, synth, torch, cfg, n, seed, pool=4096, ps_mode="20"):
@@ -150,6 +160,22 @@ def cpu_baseline(pkg, synth, cfg, seconds=10.0):
                        "in %.1f s on %d threads (disjoint frame ranges)" % (n, c1, d1, cn, dn, ncores))
 
 
+def dump_outputs(path, n, pcm, state):
+    """The last step's outputs as float32 .npy files under `path`: PCM (int16 PCM converted exactly) and, when there
+    is one, the state the step left, both for the same fixed, seeded sample of frame indices."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    idx = np.arange(n) if n <= DUMP_FRAMES else np.sort(
+        np.random.default_rng(DUMP_SEED).choice(n, DUMP_FRAMES, replace=False))
+    sel = torch.from_numpy(idx).to(pcm.device)
+    np.save(os.path.join(path, "frame_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(path, "pcm.npy"), pcm.index_select(0, sel).cpu().numpy().astype(np.float32))
+    if state is not None:
+        st = state.reshape(n, -1).index_select(0, sel.to(state.device))
+        np.save(os.path.join(path, "state.npy"), st.cpu().numpy().astype(np.float32))
+
+
 def self_launch(n):
     """Start `n` ranks of this script under torch.distributed.run (one per GPU, rendezvous on
     127.0.0.1), relay rank 0's JSON line, return non-zero if any rank failed."""
@@ -184,7 +210,11 @@ def main():
     ap.add_argument("--workload", default=None, choices=sorted(WORKLOADS))
     ap.add_argument("--frames", type=int, default=None, help="frames per GPU (default: BASELINE config)")
     ap.add_argument("--pcm", default="f32", choices=["f32", "s16"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the CPU baseline (oracle on the host)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's PCM and state (a seeded sample of frames) as DIR/*.npy")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo to rehearse)")
     ap.add_argument("--gather", action="store_true",
                     help="also time the PCM gather onto rank 0 (BASELINE config 5), reported separately")
@@ -241,6 +271,7 @@ def main():
             time.sleep(0.002)
         fmt = pkg.PCM_F32 if args.pcm == "f32" else pkg.PCM_S16
         pcm = torch.zeros((min(n, 64), pkg.OUT_CH[cfg], pkg.OUT_LEN[cfg]))
+        st = [None] * 2
     else:
         torch.cuda.set_device(local)
         dev = pkg.Device(n)
@@ -287,6 +318,9 @@ def main():
         dist.barrier()
     sync()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        # state is updated in place: st[0] is st[1], the state the last timed step wrote
+        dump_outputs(args.dump_outputs, pcm.shape[0], pcm, st[0])
 
     # device time of one step's launches: HIP events on the launch stream (the library launches on
     # torch's current stream, the one these events are recorded on)
@@ -362,7 +396,7 @@ def main():
             out["pcm_gather_ms"] = gather_ms
         if gather_check is not None:
             out["pcm_gather_check"] = gather_check
-        if world == 1 and not args.no_cpu_baseline and not dry:
+        if args.full and world == 1 and not args.no_cpu_baseline and not dry:
             out["cpu_baseline"] = cpu_baseline(pkg, synth, cfg)
         print(json.dumps(out))
     if dist is not None:

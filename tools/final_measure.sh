@@ -1,8 +1,8 @@
 #!/bin/bash
 # The round's closing measurement on ONE box: the whole GPU suite, one bench line per workload, per-kernel
 # averages (rocprofv3 --kernel-trace --stats), HBM traffic (FETCH_SIZE / WRITE_SIZE in separate passes) and
-# three PMC passes of the headline workload.  Everything lands in gpurun_out/<tag>.*; copy what is to be
-# judged into profiles/.
+# three PMC passes of the headline workload.  The bench lines go to $BENCH_LINES (default $TMPDIR/<tag>.bench.jsonl),
+# the rest next to the test log; copy what is to be judged into profiles/.
 # usage (via gpurun): tools/final_measure.sh <tag> a|b     (two calls: a box call is limited to 20 minutes)
 #   a: GPU suite, bench lines, per-kernel averages        b: HBM traffic and the PMC passes
 tag=${1:-final}
@@ -12,13 +12,14 @@ cd $root
 if [ $part = a ]; then
 python -m pytest tests -m gpu -x -q > gpurun_out/$tag.tests.log 2>&1 || { tail -30 gpurun_out/$tag.tests.log; exit 1; }
 tail -1 gpurun_out/$tag.tests.log
-: > gpurun_out/$tag.bench.jsonl
-python bench.py --steps 10 --warmup 3 | tail -1 >> gpurun_out/$tag.bench.jsonl || exit 1
+lines=${BENCH_LINES:-${TMPDIR:-/tmp}/$tag.bench.jsonl}
+: > $lines
+python bench.py --full --steps 10 --warmup 3 | tail -1 >> $lines || exit 1
 for wl in hev1 lc_stereo hev2_34; do
-    python bench.py --workload $wl --steps 10 --warmup 3 --no-cpu-baseline | tail -1 >> gpurun_out/$tag.bench.jsonl || exit 1
+    python bench.py --workload $wl --steps 10 --warmup 3 --no-cpu-baseline | tail -1 >> $lines || exit 1
 done
-python bench.py --pcm s16 --steps 10 --warmup 3 --no-cpu-baseline | tail -1 >> gpurun_out/$tag.bench.jsonl || exit 1
-cut -c1-400 gpurun_out/$tag.bench.jsonl
+python bench.py --pcm s16 --steps 10 --warmup 3 --no-cpu-baseline | tail -1 >> $lines || exit 1
+cut -c1-400 $lines
 for wl in hev2 hev1 lc_stereo hev2_34; do
     echo "== $wl"
     tools/kprof.sh ${tag}_k_$wl --workload $wl --steps 8 --warmup 2 || exit 1

@@ -113,7 +113,7 @@ EXPORTED = [
     # heaac_dsp.h
     "heaac_device_create", "heaac_device_destroy", "heaac_device_workspace_bytes",
     "heaac_strerror", "heaac_imdct_half_batch", "heaac_lc_decode_batch",
-    "heaac_he_decode_batch", "heaac_he_decode_batch_ex", "heaac_qmf_analysis_batch", "heaac_qmf_synthesis_batch",
+    "heaac_he_decode_batch", "heaac_he_decode_batch_ex", "heaac_he_decode_streams", "heaac_qmf_analysis_batch", "heaac_qmf_synthesis_batch",
     "heaac_qmf_synthesis_ds_batch",
     "heaac_sbr_make_header", "heaac_build_info", "heaac_spectral_tools_batch",
     "heaac_validate_frame", "heaac_he_check_batch", "heaac_couple_after_imdct_batch",
@@ -463,6 +463,44 @@ class Device:
                                               _ptr(hdr), C.c_size_t(n_hdr), _ptr(ps), _ptr(state_in), _ptr(state_out),
                                               _ptr(pcm), pcm_format, C.c_size_t(n), _stream()),
                "heaac_he_decode_batch")
+        return pcm, state_out
+
+    def he_decode_streams(self, cfg, coeffs, ics, sbr, hdr, ps, state_in, frames_per_stream, state_out=None, pcm=None,
+                          pcm_format=PCM_F32, downsampled=False):
+        """heaac_he_decode_streams: S streams x T = frames_per_stream consecutive frames each.  The per-frame tensors
+        are laid out as for he_decode with n = S * T (frame t of stream s at s * T + t); state_in / state_out hold ONE
+        record per stream (before frame 0 / after frame T - 1).  Returns (pcm, state_out)."""
+        import torch
+        T = int(frames_per_stream)
+        S = state_in.numel() // STATE_WORDS[cfg]
+        n = S * T
+        # a wrong-length tensor would be a silent device out-of-bounds read: check them all here
+        assert state_in.dtype == torch.float32 and state_in.numel() == S * STATE_WORDS[cfg], "state_in"
+        assert coeffs.dtype == torch.float32 and coeffs.numel() == n * CORE_CH[cfg] * 1024, "coeffs"
+        assert ics.numel() * ics.element_size() == n * CORE_CH[cfg] * ICS_DT.itemsize, "ics"
+        assert sbr.numel() * sbr.element_size() == n * SBR_FRAME_DT.itemsize, "sbr"
+        assert hdr.numel() * hdr.element_size() >= SBR_HDR_DT.itemsize and \
+            (hdr.numel() * hdr.element_size()) % SBR_HDR_DT.itemsize == 0, "hdr"
+        if cfg == CFG_HEV2:
+            assert ps is not None and ps.numel() * ps.element_size() == n * PS_FRAME_DT.itemsize, "ps"
+        if state_out is None:
+            state_out = torch.empty_like(state_in)
+        else:
+            assert state_out.dtype == torch.float32 and state_out.numel() == state_in.numel(), "state_out"
+        length = 1024 if downsampled else 2048
+        if pcm is None:
+            if pcm_format == PCM_F32:
+                pcm = torch.empty((n, OUT_CH[cfg], length), dtype=torch.float32, device=coeffs.device)
+            else:
+                pcm = torch.empty((n, length, OUT_CH[cfg]), dtype=torch.int16, device=coeffs.device)
+        else:
+            assert pcm.numel() == n * OUT_CH[cfg] * length and \
+                pcm.dtype == (torch.float32 if pcm_format == PCM_F32 else torch.int16), "pcm"
+        n_hdr = hdr.numel() // SBR_HDR_DT.itemsize
+        _check(lib().heaac_he_decode_streams(self._h, cfg, 1 if downsampled else 0, _ptr(coeffs), _ptr(ics), _ptr(sbr),
+                                             _ptr(hdr), C.c_size_t(n_hdr), _ptr(ps), _ptr(state_in), _ptr(state_out),
+                                             _ptr(pcm), pcm_format, C.c_size_t(S), C.c_size_t(T), _stream()),
+               "heaac_he_decode_streams")
         return pcm, state_out
 
     def qmf_analysis(self, x, xhist, scale=32768.0):

@@ -96,13 +96,21 @@ struct CaWave {
 static_assert(CA_U >= 1312, "x of channel 0 fits under u of channel 1");
 static_assert(CA_U <= 2 * 2 * C2_TSTRIDE, "u rows of channel 0 lie over the core's transpose regions");
 
+// STRIDED (heaac_he_decode_streams): frame f of the launch reads its coefficients and ics at record f * rstride (frame
+// t of stream f, the pointers offset by t), its state at f and its W at unit f * ncore + ch of the launch.
+template <bool STRIDED>
 __global__ __launch_bounds__(CA_WAVES * WAVE)
 void k_core_ana(const float *__restrict__ g_tab, const uint16_t *__restrict__ g_rev,
                 const float *__restrict__ g_coeffs, const HeaacIcs *__restrict__ g_ics,
                 const float *g_state_in, float *g_state_out, int state_words,
                 int ncore, int off_saved0, int off_sbr0,
-                float *__restrict__ g_W, float scale, unsigned long long n_units)
+                float *__restrict__ g_W, float scale, unsigned long long n_units, unsigned long long rstride)
 {
+    // record index of unit u (= frame u / ncore, channel u % ncore)
+    auto rec = [&](unsigned long long u) -> unsigned long long {
+        if constexpr (STRIDED) return (u / ncore) * rstride * ncore + u % ncore;
+        else return u;
+    };
     // Tables: the small ones in LDS; the long windows (8 KB), the N = 2048 post-rotation table (4 KB) and the pre-rotation
     // twiddles (4.5 KB) are read from the table blob in global memory (cache resident, coalesced, loaded well ahead of
     // their use) -- the LDS they would take is what a seventh wave per CU needs.
@@ -144,10 +152,11 @@ void k_core_ana(const float *__restrict__ g_tab, const uint16_t *__restrict__ g_
         const unsigned long long u0 = 2 * pr;
         const bool have1 = u0 + 1 < n_units;                            // uniform
         const unsigned long long u1 = have1 ? u0 + 1 : u0;
-        const HeaacIcs ics0 = g_ics[u0], ics1 = g_ics[u1];
+        const unsigned long long r0 = rec(u0), r1 = rec(u1);
+        const HeaacIcs ics0 = g_ics[r0], ics1 = g_ics[r1];
         int lane = opaque(lane0);      // lane-derived addresses are recomputed per pair, not hoisted and spilled
-        core2_stage_coeffs(reinterpret_cast<float *>(T0), g_coeffs + u0 * 1024, lane);
-        core2_stage_coeffs(reinterpret_cast<float *>(T1), g_coeffs + u1 * 1024, lane);
+        core2_stage_coeffs(reinterpret_cast<float *>(T0), g_coeffs + r0 * 1024, lane);
+        core2_stage_coeffs(reinterpret_cast<float *>(T1), g_coeffs + r1 * 1024, lane);
         wave_sync();
         {
             const int half = lane >> 5, hl = lane & 31;
@@ -258,12 +267,14 @@ void k_core_ana(const float *__restrict__ g_tab, const uint16_t *__restrict__ g_
     }
 }
 
+// STRIDED: frame f's SBR record is g_sbr[f * rstride] (see k_core_ana)
+template <bool STRIDED>
 __global__ __launch_bounds__(HF_WAVES * WAVE)
 void k_hfadj(const float *__restrict__ g_tab,
              const HeaacSbrFrame *__restrict__ g_sbr, const HeaacSbrHeader *__restrict__ g_hdr, unsigned n_hdr,
              const float *g_W, const float *g_state_in, float *g_state_out, int state_words,
              int ncore, int off_sbr0, float *g_X, unsigned long long n_units, unsigned *g_queue,
-             unsigned char *__restrict__ g_xtop)
+             unsigned char *__restrict__ g_xtop, unsigned long long rstride)
 {
     __shared__ float s_xlow[HF_WAVES][HF_XLOW_WORDS], s_aux[HF_WAVES][HF_AUX_WORDS], s_rec[HF_WAVES][HF_REC_WORDS];
     __shared__ float s_noise[1024];              // sbr_noise_table, staged once per workgroup
@@ -283,9 +294,10 @@ void k_hfadj(const float *__restrict__ g_tab,
         const unsigned long long f = u / ncore;
         const int ch = (int)(u - f * ncore);
         const int off = off_sbr0 + ch * HEAAC_ST_SBR;
+        const HeaacSbrFrame *sbr = STRIDED ? &g_sbr[f * rstride] : &g_sbr[f];
         v2f *Xc = reinterpret_cast<v2f *>(g_X + (f * 2 + ch) * HE_X_CHANNEL);
         int xb = 64;
-        hf_channel(S, s_noise, &g_sbr[f], g_hdr, n_hdr, ch, g_W + u * 2048,
+        hf_channel(S, s_noise, sbr, g_hdr, n_hdr, ch, g_W + u * 2048,
                    g_state_in + f * state_words + off, g_state_out + f * state_words + off, lane,
                    [&](int i, float re, float im) {
                        if (i == 0 && g_xtop) {            // (g_xtop == nullptr: a PS stage follows and reads every band)
@@ -296,7 +308,7 @@ void k_hfadj(const float *__restrict__ g_tab,
                            // rest from its page of zeros.
                            const int top16 = (S.h.kx + S.h.m + 15) & ~15;
                            const int t_old = S.c[ch].t_env_num_env_old;
-                           const bool zero = 2 * t_old - 32 <= 0 || (int)g_sbr[f].kx_old + (int)g_sbr[f].m_old <= top16;
+                           const bool zero = 2 * t_old - 32 <= 0 || (int)sbr->kx_old + (int)sbr->m_old <= top16;
                            xb = __builtin_amdgcn_readfirstlane(zero && top16 < 64 ? top16 : 64);
                            if (lane == 0 && xb != 64) g_xtop[f * 2 + ch] = (unsigned char)xb;
                        }
@@ -369,7 +381,13 @@ __device__ __forceinline__ void syn_st(T *p, T v) { __builtin_nontemporal_store(
 // PLANES = true: X0 / X1 are the re / im planes [32][64] of the stage-level entry point (heaac_qmf_synthesis_batch).
 // PLANES = false: X0 is a channel of the decoders' hand-over workspace, [slot][band][re, im] (X1 unused): load q holds
 // the bands 2 (lane & 31), + 1 of slot 2 q + (lane >> 5) as (re, im, re, im).
-template <bool PLANES>
+__device__ __forceinline__ void syn_load_ring(const float *v_in, int lane, SynIn &d)
+{
+#pragma unroll
+    for (int r = 0; r < 18; r++) d.h[r] = syn_ld1(v_in + lane + 64 * r);
+}
+// RING = false: the X rows only (the streams form's ring stays on chip between the frames of a stream)
+template <bool PLANES, bool RING = true>
 __device__ __forceinline__ void syn_load(const float *X0, const float *X1, const float *v_in, int lane, SynIn &d)
 {
     const f32x4 *p0 = reinterpret_cast<const f32x4 *>(X0), *p1 = reinterpret_cast<const f32x4 *>(X1);
@@ -379,8 +397,7 @@ __device__ __forceinline__ void syn_load(const float *X0, const float *X1, const
                                : syn_ld4(p0 + q * 64 + lane);
         d.x[4 * q] = t.x; d.x[4 * q + 1] = t.y; d.x[4 * q + 2] = t.z; d.x[4 * q + 3] = t.w;
     }
-#pragma unroll
-    for (int r = 0; r < 18; r++) d.h[r] = syn_ld1(v_in + lane + 64 * r);
+    if constexpr (RING) syn_load_ring(v_in, lane, d);
 }
 
 template <bool PLANES, class SL>
@@ -573,6 +590,81 @@ void k_synth(const float *__restrict__ g_tab, const float *g_X,
     }
 }
 
+// k_synth in the streams form (heaac_he_decode_streams): a wave works through one output channel of one stream at a
+// time (a "chain"), its T frames in t order, so one ring is resident per wave.  The ring is loaded at t = 0 and stored after t = T - 1; in
+// between, the new ring (v rows 0..8, what syn_hist_out would store) goes from the wave's LDS rows into the registers
+// that syn_rows writes to rows 32..40 for the next frame.  While a frame runs its polyphase sum, the X rows of the
+// next frame -- or, after the last, the X rows and ring of the next ticket -- are on their way into registers.
+// X of frame (s, t) is unit t * n_streams + s of the workspace (the stages before run one launch per t); its PCM is
+// record s * T + t.
+template <int FMT>
+__global__ __launch_bounds__(SYN_WAVES_F32 * WAVE)
+void k_synth_streams(const float *__restrict__ g_tab, const float *g_X,
+                     const float *g_state_in, float *g_state_out, int state_words, int off_syn0,
+                     int nout, void *__restrict__ g_pcm, float scale, float bias,
+                     unsigned long long n_streams, unsigned T, unsigned *g_queue,
+                     const unsigned char *__restrict__ g_xtop, const float *__restrict__ g_zero)
+{
+    constexpr int NW = SYN_WAVES_F32;
+    __shared__ SynLdsT<NW> S;
+    for (int i = threadIdx.x; i < 640; i += blockDim.x) S.win[i] = g_tab[TB_QMF_US + i];
+    if (threadIdx.x < 64) S.rot[threadIdx.x] = g_tab[TB_ROT128S + threadIdx.x];
+    if (threadIdx.x < 5) S.c16[threadIdx.x] = g_tab[TB_COS16 + threadIdx.x];
+    if (threadIdx.x < 9) S.c32[threadIdx.x] = g_tab[TB_COS32 + threadIdx.x];
+    __syncthreads();
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / WAVE), lane = threadIdx.x % WAVE;
+    SynWave &w = S.w[wave];
+    const unsigned long long n_chains = n_streams * nout;
+    auto load_x = [&](unsigned long long st, unsigned t, int ch, SynIn &d) {
+        const unsigned long long u = (unsigned long long)t * n_streams + st;
+        const int xt = __builtin_amdgcn_readfirstlane((int)g_xtop[u * 2 + ch]);
+        const float *X0 = (lane & 31) * 2 < xt ? g_X + (u * 2 + ch) * HE_X_CHANNEL : g_zero;
+        syn_load<false, false>(X0, nullptr, nullptr, lane, d);
+    };
+    auto load_chain = [&](unsigned long long c, SynIn &d) {
+        const unsigned long long st = c / nout;
+        const int ch = (int)(c - st * nout);
+        load_x(st, 0, ch, d);
+        syn_load_ring(g_state_in + st * state_words + off_syn0 + ch * HEAAC_ST_SYNTH, lane, d);
+    };
+    // (two chains per ticket, as k_synth takes two frames: at small T one ticket per chain would run into the
+    // queue word's atomic rate)
+    FrameFeed<2> feed;
+    feed.init((unsigned long long)blockIdx.x * NW + wave, (unsigned long long)gridDim.x * NW, g_queue, lane);
+    SynIn cur;
+    if (feed.cur < n_chains) load_chain(feed.cur, cur);
+    while (feed.cur < n_chains) {
+        const unsigned long long c = feed.cur, c1 = feed.nxt;
+        feed.request(lane);
+        const unsigned long long st = c / nout;
+        const int ch = (int)(c - st * nout);
+        for (unsigned t = 0; t < T; t++) {
+            const bool last = t + 1 == T;
+            syn_rows<false>(S, w, cur, lane);
+            wave_sync();
+            if (!last) load_x(st, t + 1, ch, cur);
+            else if (c1 < n_chains) load_chain(c1, cur);
+            const unsigned long long r = st * T + t;
+            if constexpr (FMT == HEAAC_PCM_F32_PLANAR) {
+                float *o = reinterpret_cast<float *>(g_pcm) + (r * nout + ch) * 2048;
+                syn_poly<1>(S, w, scale, bias, lane, [&](int i, int n, float v) { syn_st(o + 64 * i + n, v); });
+            } else {
+                int16_t *o = reinterpret_cast<int16_t *>(g_pcm) + r * 2048 * nout;
+                syn_poly<1>(S, w, scale, bias, lane,
+                            [&](int i, int n, float v) { o[(64 * i + n) * nout + ch] = (int16_t)pcm_int16<FMT>(v); });
+            }
+            if (!last) {
+#pragma unroll
+                for (int q = 0; q < 18; q++) cur.h[q] = w.vb[(q >> 1) * VB_STRIDE + (q & 1) * 64 + lane];
+            } else {
+                syn_hist_out(w, g_state_out + st * state_words + off_syn0 + ch * HEAAC_ST_SYNTH, lane);
+            }
+            wave_sync();
+        }
+        feed.advance();
+    }
+}
+
 // Stage-level batched filterbanks (heaac_qmf_analysis_batch / _synthesis_batch)
 __global__ __launch_bounds__(ANA_WAVES * WAVE)
 void k_qmf_analysis(const float *__restrict__ g_tab, const float *__restrict__ g_in,
@@ -648,13 +740,16 @@ __device__ __forceinline__ void syn_ds_lds_init(SynDsLds &S, const float *g_tab)
 // One channel of the downsampled bank.  X0 / X1: re / im planes, row stride 64 (bands 0..31 used);
 // v_in / v_out: 576 floats; emit(i, n, value) receives out[32 i + n].
 // PLANES = false: X0 is a channel of the hand-over workspace, [slot][band][re, im] (X1 unused).
-template <bool PLANES, class Emit>
+// RING = false: v_in / v_out are not used; the caller has put the history into rows 32..40 and takes the new ring
+// from rows 0..8.
+template <bool PLANES, bool RING = true, class Emit>
 __device__ __forceinline__ void synth_ds_channel(const SynDsLds &S, float *vb, const float *X0, const float *X1,
                                                  const float *v_in, float *v_out, float scale, float bias,
                                                  int lane, Emit emit)
 {
     // history: 9 slots of 64 behind the 32 new ones
-    for (int t = lane; t < 576; t += WAVE) vb[(32 + (t >> 6)) * DS_STRIDE + (t & 63)] = v_in[t];
+    if constexpr (RING)
+        for (int t = lane; t < 576; t += WAVE) vb[(32 + (t >> 6)) * DS_STRIDE + (t & 63)] = v_in[t];
     if constexpr (PLANES) {
         if (lane < 32) {
             const int i = lane;
@@ -721,7 +816,8 @@ __device__ __forceinline__ void synth_ds_channel(const SynDsLds &S, float *vb, c
             emit(i, nn, acc);
         }
     }
-    for (int t = lane; t < 576; t += WAVE) v_out[t] = vb[(t >> 6) * DS_STRIDE + (t & 63)];
+    if constexpr (RING)
+        for (int t = lane; t < 576; t += WAVE) v_out[t] = vb[(t >> 6) * DS_STRIDE + (t & 63)];
     wave_sync();
 }
 
@@ -771,6 +867,57 @@ void k_synth_ds(const float *__restrict__ g_tab, const float *g_X,
                                  [&](int i, int nn, float v) { o[(32 * i + nn) * nout] = (int16_t)pcm_int16<FMT>(v); });
             }
         }
+    }
+}
+
+// k_synth_ds in the streams form: one wave per (stream, output channel), its T frames in t order.  The ring (the
+// first 576 words of the channel's synthesis state) is loaded once, moves from v rows 0..8 to rows 32..40 between
+// frames, and is stored once; the rest of the record passes through.  X and PCM as k_synth_streams.
+template <int FMT>
+__global__ __launch_bounds__(DS_WAVES * WAVE)
+void k_synth_ds_streams(const float *__restrict__ g_tab, const float *g_X,
+                        const float *g_state_in, float *g_state_out, int state_words, int off_syn0,
+                        int nout, void *__restrict__ g_pcm, float scale, float bias,
+                        unsigned long long n_streams, unsigned T)
+{
+    __shared__ SynDsLds S;
+    syn_ds_lds_init(S, g_tab);
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / WAVE), lane = threadIdx.x % WAVE;
+    float *vb = S.vb[wave];
+    const unsigned long long n_chains = n_streams * nout;
+    for (unsigned long long c = (unsigned long long)blockIdx.x * DS_WAVES + wave; c < n_chains;
+         c += (unsigned long long)gridDim.x * DS_WAVES) {
+        const unsigned long long st = c / nout;
+        const int ch = (int)(c - st * nout);
+        const float *v_in = g_state_in + st * state_words + off_syn0 + ch * HEAAC_ST_SYNTH;
+        float *v_out = g_state_out + st * state_words + off_syn0 + ch * HEAAC_ST_SYNTH;
+        if (v_out != v_in)
+            for (int q = 576 + lane; q < HEAAC_ST_SYNTH; q += WAVE) v_out[q] = v_in[q];
+        for (int q = lane; q < 576; q += WAVE) vb[(32 + (q >> 6)) * DS_STRIDE + (q & 63)] = v_in[q];
+        for (unsigned t = 0; t < T; t++) {
+            if (t) {
+                // the frame before left its new ring in rows 0..8 (its last reads of rows 32..40 are behind the
+                // wave_sync that ends synth_ds_channel); lane = column
+                float h[9];
+#pragma unroll
+                for (int k = 0; k < 9; k++) h[k] = vb[k * DS_STRIDE + lane];
+#pragma unroll
+                for (int k = 0; k < 9; k++) vb[(32 + k) * DS_STRIDE + lane] = h[k];
+            }
+            const unsigned long long u = (unsigned long long)t * n_streams + st, r = st * T + t;
+            const float *X0 = g_X + (u * 2 + ch) * HE_X_CHANNEL;
+            if constexpr (FMT == HEAAC_PCM_F32_PLANAR) {
+                float *o = reinterpret_cast<float *>(g_pcm) + (r * nout + ch) * 1024;
+                synth_ds_channel<false, false>(S, vb, X0, nullptr, nullptr, nullptr, scale, bias, lane,
+                                               [&](int i, int nn, float v) { o[32 * i + nn] = v; });
+            } else {
+                int16_t *o = reinterpret_cast<int16_t *>(g_pcm) + r * 1024 * nout + ch;
+                synth_ds_channel<false, false>(S, vb, X0, nullptr, nullptr, nullptr, scale, bias, lane,
+                                               [&](int i, int nn, float v) { o[(32 * i + nn) * nout] = (int16_t)pcm_int16<FMT>(v); });
+            }
+        }
+        for (int q = lane; q < 576; q += WAVE) v_out[q] = vb[(q >> 6) * DS_STRIDE + (q & 63)];
+        wave_sync();
     }
 }
 
@@ -828,25 +975,25 @@ extern "C" int heaac_launch_he(const float *d_tab, const uint16_t *d_rev, int cf
     if (hipMemsetAsync(d_queue, 0, 64, s) != hipSuccess) return HEAAC_ERR_HIP;
     // every frame's X rows are whole (64 bands) unless the fused HF + PS kernel says otherwise
     if (hipMemsetAsync(d_xtop, 64, 2 * n, s) != hipSuccess) return HEAAC_ERR_HIP;
-    hipLaunchKernelGGL(k_core_ana, dim3(he_grid((units + 1) / 2, CA_WAVES)), dim3(CA_WAVES * WAVE), 0, s,
+    hipLaunchKernelGGL(k_core_ana<false>, dim3(he_grid((units + 1) / 2, CA_WAVES)), dim3(CA_WAVES * WAVE), 0, s,
                        d_tab, d_rev, d_coeffs, d_ics, d_state_in, d_state_out, words, ncore,
-                       off_saved0, off_sbr0, d_ws_W, 1 / (-1024 * sf_scale), units);
+                       off_saved0, off_sbr0, d_ws_W, 1 / (-1024 * sf_scale), units, 1ull);
     if (cfg == HEAAC_CFG_HEV2 && he_fused()) {
         // HF adjustment + baseline PS in one kernel; the general PS kernel finishes the
         // frames with another PS layout (it skips the rest)
         const int off_ps = off_syn0 + 2 * HEAAC_ST_SYNTH;
         int rc = heaac_launch_hfps(d_tab, d_sbr, d_hdr, n_hdr, d_ps, d_ws_W, d_state_in, d_state_out, words,
-                                   off_sbr0, off_ps, d_ws_X, n, d_queue, d_xtop, s);
+                                   off_sbr0, off_ps, d_ws_X, n, d_queue, d_xtop, 1, s);
         if (rc != HEAAC_OK) return rc;
-        rc = heaac_launch_ps(d_tab, d_ps, d_sbr, d_hdr, n_hdr, d_state_in, d_state_out, words, off_ps, d_ws_X, n, 2, s);
+        rc = heaac_launch_ps(d_tab, d_ps, d_sbr, d_hdr, n_hdr, d_state_in, d_state_out, words, off_ps, d_ws_X, n, 2, 1, s);
         if (rc != HEAAC_OK) return rc;
     } else {
-        hipLaunchKernelGGL(k_hfadj, dim3(he_grid((units + 1) / 2, HF_WAVES)), dim3(HF_WAVES * WAVE), 0, s,
+        hipLaunchKernelGGL(k_hfadj<false>, dim3(he_grid((units + 1) / 2, HF_WAVES)), dim3(HF_WAVES * WAVE), 0, s,
                            d_tab, d_sbr, d_hdr, n_hdr, d_ws_W, d_state_in, d_state_out, words, ncore, off_sbr0,
-                           d_ws_X, units, d_queue + 1, cfg == HEAAC_CFG_HEV2 ? nullptr : d_xtop);
+                           d_ws_X, units, d_queue + 1, cfg == HEAAC_CFG_HEV2 ? nullptr : d_xtop, 1ull);
         if (cfg == HEAAC_CFG_HEV2) {
             int rc = heaac_launch_ps(d_tab, d_ps, d_sbr, d_hdr, n_hdr, d_state_in, d_state_out, words,
-                                     off_syn0 + 2 * HEAAC_ST_SYNTH, d_ws_X, n, 3, s);
+                                     off_syn0 + 2 * HEAAC_ST_SYNTH, d_ws_X, n, 3, 1, s);
             if (rc != HEAAC_OK) return rc;
         }
     }
@@ -878,6 +1025,93 @@ extern "C" int heaac_launch_he(const float *d_tab, const uint16_t *d_rev, int cf
         hipLaunchKernelGGL((k_synth<HEAAC_PCM_S16_INTERLEAVED_SSE2>), g, b, 0, s, d_tab, d_ws_X, d_state_in, d_state_out,
                            words, off_syn0, nout, d_pcm, scale, bias,
                            (unsigned long long)n, (unsigned long long)pcm_frame0, d_queue + 2, d_xtop, d_zero);
+    else
+        return HEAAC_ERR_ARG;
+    return hipGetLastError() == hipSuccess ? HEAAC_OK : HEAAC_ERR_HIP;
+}
+
+// The streams form (heaac_he_decode_streams) over one chunk of whole streams: n_streams x T frames, frame (s, t) at
+// record s * T + t of the per-frame arrays, the state one record per stream.  The core + analysis and HF (+ PS) stages
+// run one launch per t, in t order, over the n_streams frames of position t (the record stride is T; frame t reads the
+// state that frame t - 1 left in d_state_out); their W / X hand-over units are t-major (unit t * n_streams + s).  The
+// synthesis stage runs each (stream, channel) chain inside one launch with the ring on chip (k_synth_streams).
+extern "C" int heaac_launch_he_streams(const float *d_tab, const uint16_t *d_rev, int cfg,
+                                       const float *d_coeffs, const HeaacIcs *d_ics,
+                                       const HeaacSbrFrame *d_sbr, const HeaacSbrHeader *d_hdr, unsigned n_hdr,
+                                       const HeaacPsFrame *d_ps,
+                                       const float *d_state_in, float *d_state_out,
+                                       void *d_pcm, int pcm_format,
+                                       float *d_ws_W, float *d_ws_X, unsigned *d_queue,
+                                       unsigned char *d_xtop, const float *d_zero,
+                                       size_t n_streams, size_t T, int flags, hipStream_t s)
+{
+    const int ncore = cfg == HEAAC_CFG_HEV1 ? 2 : 1;
+    const int nout  = cfg == HEAAC_CFG_HEV1_MONO ? 1 : 2;
+    int words, off_saved0 = 0, off_sbr0, off_syn0;
+    if (cfg == HEAAC_CFG_HEV1) {
+        words = HEAAC_STATE_WORDS_HEV1; off_sbr0 = 2 * HEAAC_ST_SAVED; off_syn0 = off_sbr0 + 2 * HEAAC_ST_SBR;
+    } else if (cfg == HEAAC_CFG_HEV1_MONO) {
+        words = HEAAC_STATE_WORDS_HEV1_MONO; off_sbr0 = HEAAC_ST_SAVED; off_syn0 = off_sbr0 + HEAAC_ST_SBR;
+    } else if (cfg == HEAAC_CFG_HEV2) {
+        words = HEAAC_STATE_WORDS_HEV2; off_sbr0 = HEAAC_ST_SAVED; off_syn0 = off_sbr0 + HEAAC_ST_SBR;
+    } else
+        return HEAAC_ERR_ARG;
+    if (!n_streams || !T) return HEAAC_OK;
+    const unsigned long long units = (unsigned long long)n_streams * ncore;
+    const bool simd = pcm_format == HEAAC_PCM_S16_INTERLEAVED_SSE2;
+    const float sf_scale = simd ? -1.0f / 1024.0f : HEAAC_SF_SCALE;
+    if (hipMemsetAsync(d_xtop, 64, 2 * n_streams * T, s) != hipSuccess) return HEAAC_ERR_HIP;
+    for (size_t t = 0; t < T; t++) {
+        const float *st_in = t ? d_state_out : d_state_in;
+        float *W = d_ws_W + t * units * 2048;
+        float *X = d_ws_X + t * n_streams * 2 * HE_X_CHANNEL;
+        unsigned char *xtop = d_xtop + 2 * t * n_streams;
+        hipLaunchKernelGGL(k_core_ana<true>, dim3(he_grid((units + 1) / 2, CA_WAVES)), dim3(CA_WAVES * WAVE), 0, s,
+                           d_tab, d_rev, d_coeffs + t * ncore * 1024, d_ics + t * ncore, st_in, d_state_out, words, ncore,
+                           off_saved0, off_sbr0, W, 1 / (-1024 * sf_scale), units, (unsigned long long)T);
+        // queue heads (k_hfps: [0], k_hfadj: [1]; k_synth_streams: [2], which no launch before it draws from)
+        if (hipMemsetAsync(d_queue, 0, 64, s) != hipSuccess) return HEAAC_ERR_HIP;
+        if (cfg == HEAAC_CFG_HEV2) {
+            const int off_ps = off_syn0 + 2 * HEAAC_ST_SYNTH;
+            int rc = heaac_launch_hfps(d_tab, d_sbr + t, d_hdr, n_hdr, d_ps + t, W, st_in, d_state_out, words,
+                                       off_sbr0, off_ps, X, n_streams, d_queue, xtop, T, s);
+            if (rc != HEAAC_OK) return rc;
+            rc = heaac_launch_ps(d_tab, d_ps + t, d_sbr + t, d_hdr, n_hdr, st_in, d_state_out, words, off_ps, X,
+                                 n_streams, 2, T, s);
+            if (rc != HEAAC_OK) return rc;
+        } else {
+            hipLaunchKernelGGL(k_hfadj<true>, dim3(he_grid((units + 1) / 2, HF_WAVES)), dim3(HF_WAVES * WAVE), 0, s,
+                               d_tab, d_sbr + t, d_hdr, n_hdr, W, st_in, d_state_out, words, ncore, off_sbr0,
+                               X, units, d_queue + 1, xtop, (unsigned long long)T);
+        }
+    }
+    const float scale = -1024 * sf_scale, bias = simd ? 0.0f : HEAAC_ADD_BIAS;
+    const unsigned long long chains = (unsigned long long)n_streams * nout;
+    const unsigned long long ns = n_streams;
+    const unsigned Tu = (unsigned)T;
+    if (flags & HEAAC_HE_DOWNSAMPLED) {
+        const dim3 gd(he_grid(chains, DS_WAVES)), bd(DS_WAVES * WAVE);
+        if (pcm_format == HEAAC_PCM_F32_PLANAR)
+            hipLaunchKernelGGL((k_synth_ds_streams<HEAAC_PCM_F32_PLANAR>), gd, bd, 0, s, d_tab, d_ws_X, d_state_in,
+                               d_state_out, words, off_syn0, nout, d_pcm, scale, bias, ns, Tu);
+        else if (simd)
+            hipLaunchKernelGGL((k_synth_ds_streams<HEAAC_PCM_S16_INTERLEAVED_SSE2>), gd, bd, 0, s, d_tab, d_ws_X, d_state_in,
+                               d_state_out, words, off_syn0, nout, d_pcm, scale, bias, ns, Tu);
+        else
+            hipLaunchKernelGGL((k_synth_ds_streams<HEAAC_PCM_S16_INTERLEAVED>), gd, bd, 0, s, d_tab, d_ws_X, d_state_in,
+                               d_state_out, words, off_syn0, nout, d_pcm, scale, bias, ns, Tu);
+        return hipGetLastError() == hipSuccess ? HEAAC_OK : HEAAC_ERR_HIP;
+    }
+    const dim3 g(he_grid(chains, SYN_WAVES_F32)), b(SYN_WAVES_F32 * WAVE);
+    if (pcm_format == HEAAC_PCM_F32_PLANAR)
+        hipLaunchKernelGGL((k_synth_streams<HEAAC_PCM_F32_PLANAR>), g, b, 0, s, d_tab, d_ws_X, d_state_in, d_state_out,
+                           words, off_syn0, nout, d_pcm, scale, bias, ns, Tu, d_queue + 2, d_xtop, d_zero);
+    else if (pcm_format == HEAAC_PCM_S16_INTERLEAVED)
+        hipLaunchKernelGGL((k_synth_streams<HEAAC_PCM_S16_INTERLEAVED>), g, b, 0, s, d_tab, d_ws_X, d_state_in, d_state_out,
+                           words, off_syn0, nout, d_pcm, scale, bias, ns, Tu, d_queue + 2, d_xtop, d_zero);
+    else if (simd)
+        hipLaunchKernelGGL((k_synth_streams<HEAAC_PCM_S16_INTERLEAVED_SSE2>), g, b, 0, s, d_tab, d_ws_X, d_state_in, d_state_out,
+                           words, off_syn0, nout, d_pcm, scale, bias, ns, Tu, d_queue + 2, d_xtop, d_zero);
     else
         return HEAAC_ERR_ARG;
     return hipGetLastError() == hipSuccess ? HEAAC_OK : HEAAC_ERR_HIP;

@@ -18,12 +18,13 @@
 #include "k_hfr.h"       // (hf_frame_is_fast; the register form of the HF stage is a measurement-build kernel's)
 #include "k_psf.h"
 
-template <bool GENERAL, int WAVES>
+// STRIDED (heaac_he_decode_streams): frame f's SBR and PS records are at f * rstride; X and state at f.
+template <bool GENERAL, int WAVES, bool STRIDED = false>
 __global__ __launch_bounds__(WAVES * WAVE)
 void k_ps(const float *__restrict__ g_tab, const HeaacPsFrame *__restrict__ g_ps,
           const HeaacSbrFrame *__restrict__ g_sbr, const HeaacSbrHeader *__restrict__ g_hdr, unsigned n_hdr,
           const float *g_state_in, float *g_state_out, int state_words, int off_ps,
-          float *g_X, unsigned long long n)
+          float *g_X, unsigned long long n, unsigned long long rstride)
 {
     using WT = PsWaveT<GENERAL>;
     __shared__ HeaacPsFrame s_p[WAVES];
@@ -50,17 +51,17 @@ void k_ps(const float *__restrict__ g_tab, const HeaacPsFrame *__restrict__ g_ps
     const unsigned long long nw = (unsigned long long)gridDim.x * WAVES;
     for (unsigned long long base = wid; base < n; base += nw * WAVE) {
         const unsigned long long fl = base + (unsigned long long)lane * nw;
-        const bool mine = fl < n && ps_frame_is_general(&g_ps[fl]) == GENERAL;
+        const bool mine = fl < n && ps_frame_is_general(&g_ps[STRIDED ? fl * rstride : fl]) == GENERAL;
         unsigned long long todo = __ballot(mine);
         while (todo) {
             const int j = __builtin_amdgcn_readfirstlane(__builtin_ctzll(todo));
             todo &= todo - 1;
-            const unsigned long long f = base + (unsigned long long)j * nw;
-            const unsigned hi = g_sbr[f].hdr;
+            const unsigned long long f = base + (unsigned long long)j * nw, rf = STRIDED ? f * rstride : f;
+            const unsigned hi = g_sbr[rf].hdr;
             const HeaacSbrHeader &h = g_hdr[hi < n_hdr ? hi : n_hdr - 1];
             const int top = h.kx + h.m;             // ff_ps_apply(..., sbr->kx[1] + sbr->m[1])
             float *XL = g_X + (f * 2) * HE_X_CHANNEL;
-            ps_frame<GENERAL>(W, g_tab, &g_ps[f], top, g_state_in + f * state_words + off_ps,
+            ps_frame<GENERAL>(W, g_tab, &g_ps[rf], top, g_state_in + f * state_words + off_ps,
                               g_state_out + f * state_words + off_ps, XL, lane, wave, no_cols);
         }
     }
@@ -78,12 +79,14 @@ void k_ps(const float *__restrict__ g_tab, const HeaacPsFrame *__restrict__ g_ps
 #define HFPS_QUEUE_CHUNK 1      // frames per queue ticket
 #define HFPS_C_WORDS (HF_REC_WORDS > 20 * 33 ? HF_REC_WORDS : 20 * 33)
 
+// STRIDED (heaac_he_decode_streams): frame f's SBR and PS records are at f * rstride; W, X, xtop and state at f.
+template <bool STRIDED>
 __global__ __launch_bounds__(HFPS_WAVES * WAVE)
 void k_hfps(const float *__restrict__ g_tab, const HeaacSbrFrame *__restrict__ g_sbr,
             const HeaacSbrHeader *__restrict__ g_hdr, unsigned n_hdr, const HeaacPsFrame *__restrict__ g_ps,
             const float *g_W, const float *g_state_in, float *g_state_out, int state_words,
             int off_sbr, int off_ps, float *g_X, unsigned long long n_frames, unsigned *g_queue,
-            unsigned char *__restrict__ g_xtop, int skip_fast)
+            unsigned char *__restrict__ g_xtop, int skip_fast, unsigned long long rstride)
 {
     using WT = PsWaveT<false>;
     static_assert(WT::SCR <= HF_XLOW_WORDS, "|s|^2 / subL / subR lie over X_low");
@@ -121,17 +124,18 @@ void k_hfps(const float *__restrict__ g_tab, const HeaacSbrFrame *__restrict__ g
     while (feed.cur < n_frames) {
         const unsigned long long f = feed.cur, f1 = feed.nxt;
         feed.request(lane);
+        const unsigned long long rf = STRIDED ? f * rstride : f, rf1 = STRIDED ? f1 * rstride : f1;
         // slot of the PS loop at which the next frame's SBR and PS records (1.2 KB) are touched into L2
         constexpr int TOUCH_RECORDS_SLOT = 20;
         auto prefetch_next = [&](int n) {
             if (n == TOUCH_RECORDS_SLOT && f1 < n_frames) {
-                l2_touch(&g_sbr[f1], sizeof(HeaacSbrFrame), lane, sink);
-                l2_touch(&g_ps[f1], sizeof(HeaacPsFrame), lane, sink);
+                l2_touch(&g_sbr[rf1], sizeof(HeaacSbrFrame), lane, sink);
+                l2_touch(&g_ps[rf1], sizeof(HeaacPsFrame), lane, sink);
             }
         };
-        const bool base = __builtin_amdgcn_readfirstlane(!ps_frame_is_general(&g_ps[f]));
+        const bool base = __builtin_amdgcn_readfirstlane(!ps_frame_is_general(&g_ps[rf]));
         // the frames k_hfps12 takes (baseline PS on the common SBR configuration) are not this kernel's
-        if (skip_fast && base && __builtin_amdgcn_readfirstlane(hf_frame_is_fast(&g_sbr[f], g_hdr, n_hdr))) {
+        if (skip_fast && base && __builtin_amdgcn_readfirstlane(hf_frame_is_fast(&g_sbr[rf], g_hdr, n_hdr))) {
             feed.advance();
             continue;
         }
@@ -146,7 +150,7 @@ void k_hfps(const float *__restrict__ g_tab, const HeaacSbrFrame *__restrict__ g
         uint32_t preg[3];
         float hist_re = 0.0f, hist_im = 0.0f;
         {
-            const uint32_t *ps_ = reinterpret_cast<const uint32_t *>(&g_ps[f]);
+            const uint32_t *ps_ = reinterpret_cast<const uint32_t *>(&g_ps[rf]);
 #pragma unroll
             for (int r = 0; r < 3; r++) preg[r] = lane + 64 * r < (int)(sizeof(HeaacPsFrame) / 4) ? ps_[lane + 64 * r] : 0;
             if (lane < WT::NLOW * 6) {
@@ -154,7 +158,7 @@ void k_hfps(const float *__restrict__ g_tab, const HeaacSbrFrame *__restrict__ g
                 hist_im = st_in[off_ps + HEAAC_PS_INBUF + 2 * lane + 1];
             }
         }
-        hf_channel(H, s_noise, &g_sbr[f], g_hdr, n_hdr, 0, g_W + f * 2048, st_in + off_sbr, st_out + off_sbr, lane,
+        hf_channel(H, s_noise, &g_sbr[rf], g_hdr, n_hdr, 0, g_W + f * 2048, st_in + off_sbr, st_out + off_sbr, lane,
                    [&](int i, float re, float im) {
                        if (i < 32) {
                            col[i] = v2f{re, im};
@@ -182,8 +186,8 @@ void k_hfps(const float *__restrict__ g_tab, const HeaacSbrFrame *__restrict__ g
             // in EVERY slot if there are no such slots or that range ends inside this one
             const int t_old = H.c[0].t_env_num_env_old;
             const bool x_zero_above = __builtin_amdgcn_readfirstlane(
-                2 * t_old - 32 <= 0 || (int)g_sbr[f].kx_old + (int)g_sbr[f].m_old <= ((top + 15) & ~15));
-            ps_frame<false, true>(W, g_tab, &g_ps[f], top, st_in + off_ps, st_out + off_ps, Xf, lane, wave, col,
+                2 * t_old - 32 <= 0 || (int)g_sbr[rf].kx_old + (int)g_sbr[rf].m_old <= ((top + 15) & ~15));
+            ps_frame<false, true>(W, g_tab, &g_ps[rf], top, st_in + off_ps, st_out + off_ps, Xf, lane, wave, col,
                                   prefetch_next, g_xtop + 2 * f, x_zero_above);
         }
         feed.advance();
@@ -302,37 +306,53 @@ void k_hfps12(const float *__restrict__ g_tab, const HeaacSbrFrame *__restrict__
 #define PS_WAVES_20 8
 #define PS_WAVES_GEN 5
 
-// variants: bit 0 = baseline kernel, bit 1 = general kernel
+// variants: bit 0 = baseline kernel, bit 1 = general kernel.  rstride: records between consecutive frames of the
+// launch (1: the batch form; heaac_he_decode_streams passes its frames per stream)
 extern "C" int heaac_launch_ps(const float *d_tab, const HeaacPsFrame *d_ps, const HeaacSbrFrame *d_sbr,
                                const HeaacSbrHeader *d_hdr, unsigned n_hdr, const float *d_state_in, float *d_state_out,
-                               int state_words, int off_ps, float *d_ws_X, size_t n, int variants,
+                               int state_words, int off_ps, float *d_ws_X, size_t n, int variants, size_t rstride,
                                hipStream_t s)
 {
     if (!n) return HEAAC_OK;
+    const unsigned long long rs = rstride;
     unsigned long long g = (n + PS_WAVES_20 - 1) / PS_WAVES_20;
     if (g > 256) g = 256;
-    if (variants & 1)
+    if ((variants & 1) && rs == 1)
         hipLaunchKernelGGL((k_ps<false, PS_WAVES_20>), dim3((unsigned)g), dim3(PS_WAVES_20 * WAVE), 0, s, d_tab,
                            d_ps, d_sbr, d_hdr, n_hdr, d_state_in, d_state_out, state_words, off_ps, d_ws_X,
-                           (unsigned long long)n);
+                           (unsigned long long)n, rs);
+    else if (variants & 1)
+        return HEAAC_ERR_ARG;                       // (the unfused A/B path has no streams form)
     g = (n + PS_WAVES_GEN - 1) / PS_WAVES_GEN;
     if (g > 256) g = 256;
-    if (variants & 2)
+    if ((variants & 2) && rs == 1)
         hipLaunchKernelGGL((k_ps<true, PS_WAVES_GEN>), dim3((unsigned)g), dim3(PS_WAVES_GEN * WAVE), 0, s, d_tab,
                            d_ps, d_sbr, d_hdr, n_hdr, d_state_in, d_state_out, state_words, off_ps, d_ws_X,
-                           (unsigned long long)n);
+                           (unsigned long long)n, rs);
+    else if (variants & 2)
+        hipLaunchKernelGGL((k_ps<true, PS_WAVES_GEN, true>), dim3((unsigned)g), dim3(PS_WAVES_GEN * WAVE), 0, s, d_tab,
+                           d_ps, d_sbr, d_hdr, n_hdr, d_state_in, d_state_out, state_words, off_ps, d_ws_X,
+                           (unsigned long long)n, rs);
     return hipGetLastError() == hipSuccess ? HEAAC_OK : HEAAC_ERR_HIP;
 }
 
-// HF adjustment of the mono core channel fused with baseline Parametric Stereo
+// HF adjustment of the mono core channel fused with baseline Parametric Stereo (rstride: as heaac_launch_ps)
 extern "C" int heaac_launch_hfps(const float *d_tab, const HeaacSbrFrame *d_sbr, const HeaacSbrHeader *d_hdr,
                                  unsigned n_hdr, const HeaacPsFrame *d_ps, const float *d_ws_W,
                                  const float *d_state_in, float *d_state_out, int state_words,
                                  int off_sbr, int off_ps, float *d_ws_X, size_t n, unsigned *d_queue,
-                                 unsigned char *d_xtop, hipStream_t s)
+                                 unsigned char *d_xtop, size_t rstride, hipStream_t s)
 {
     if (!n) return HEAAC_OK;
     int skip_fast = 0;
+    unsigned long long g = (n + HFPS_WAVES - 1) / HFPS_WAVES;
+    if (g > 256) g = 256;
+    if (rstride != 1) {
+        hipLaunchKernelGGL(k_hfps<true>, dim3((unsigned)g), dim3(HFPS_WAVES * WAVE), 0, s, d_tab, d_sbr, d_hdr, n_hdr, d_ps,
+                           d_ws_W, d_state_in, d_state_out, state_words, off_sbr, off_ps, d_ws_X,
+                           (unsigned long long)n, d_queue, d_xtop, 0, (unsigned long long)rstride);
+        return hipGetLastError() == hipSuccess ? HEAAC_OK : HEAAC_ERR_HIP;
+    }
 #ifdef HEAAC_TUNING
     // Measurement builds only (profiles/r04_experiments.md E1): HEAAC_HFPS12=1 hands the frames with the baseline PS layout
     // on the common SBR configuration to the twelve-wave kernel first (queue head [0]); k_hfps then takes the rest
@@ -348,11 +368,9 @@ extern "C" int heaac_launch_hfps(const float *d_tab, const HeaacSbrFrame *d_sbr,
         skip_fast = 1;
     }
 #endif
-    unsigned long long g = (n + HFPS_WAVES - 1) / HFPS_WAVES;
-    if (g > 256) g = 256;
-    hipLaunchKernelGGL(k_hfps, dim3((unsigned)g), dim3(HFPS_WAVES * WAVE), 0, s, d_tab, d_sbr, d_hdr, n_hdr, d_ps,
+    hipLaunchKernelGGL(k_hfps<false>, dim3((unsigned)g), dim3(HFPS_WAVES * WAVE), 0, s, d_tab, d_sbr, d_hdr, n_hdr, d_ps,
                        d_ws_W, d_state_in, d_state_out, state_words, off_sbr, off_ps, d_ws_X,
-                       (unsigned long long)n, d_queue + (skip_fast ? 3 : 0), d_xtop, skip_fast);
+                       (unsigned long long)n, d_queue + (skip_fast ? 3 : 0), d_xtop, skip_fast, 1ull);
     return hipGetLastError() == hipSuccess ? HEAAC_OK : HEAAC_ERR_HIP;
 }
 

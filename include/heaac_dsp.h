@@ -346,6 +346,26 @@ int heaac_he_decode_batch_ex(HeaacDevice *dev, int cfg, int flags,
                              void *d_pcm, int pcm_format,
                              size_t n, void *stream);
 
+/* Several consecutive frames of each stream in one call ("streams form"): S streams x T frames each.
+ *   The per-frame arrays have the layout of heaac_he_decode_batch_ex with n = S * T, frame t of stream s at
+ *   index s * T + t:  d_coeffs [S][T][ncore][1024], d_ics [S][T][ncore], d_sbr [S][T], d_ps [S][T] (HEV2, else
+ *   NULL), d_pcm [S][T][...] as the batch call.  The state is per stream: d_state_in [S][HEAAC_STATE_WORDS_*] holds
+ *   each stream's state before its frame 0, d_state_out the state after its frame T - 1 (they may alias).
+ * PCM and final state are bit-identical to T chained heaac_he_decode_batch_ex calls, for every cfg, PCM format and
+ * flags.  Same contract as the batch call: no allocation, no synchronisation, capturable into a hipGraph, and the
+ * same rule for calls on different streams (refused with HEAAC_ERR_ARG while another stream's HE work is in flight).
+ * The device works through whole streams, floor(chunk / T) per workspace set, where chunk = min(max_frames, 262144)
+ * and at least 64 (max_frames as given to heaac_device_create); several sets alternate between the device's lanes
+ * as in the batch call.  Returns HEAAC_ERR_ARG for frames_per_stream == 0 or > chunk; n_streams == 0 is HEAAC_OK. */
+int heaac_he_decode_streams(HeaacDevice *dev, int cfg, int flags,
+                            const float *d_coeffs, const HeaacIcs *d_ics,
+                            const HeaacSbrFrame *d_sbr,
+                            const HeaacSbrHeader *d_hdr, size_t n_hdr,
+                            const HeaacPsFrame *d_ps,
+                            const float *d_state_in, float *d_state_out,
+                            void *d_pcm, int pcm_format,
+                            size_t n_streams, size_t frames_per_stream, void *stream);
+
 /* Record validation.  The batched entry points take records from ANY parser (the library's own, heaac_parse.h,
  * only writes records that pass), so the per-frame records are where malformed data would arrive; the rules are the reference parser's own rejections
  * (read_sbr_grid aacsbr.c:609-745, sbr_make_f_master / sbr_make_f_derived :296-593, ff_ps_read_data

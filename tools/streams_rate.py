@@ -1,0 +1,95 @@
+"""The streams form (heaac_he_decode_streams: S streams x T consecutive frames, state in once and out once per stream)
+against the batch form (heaac_he_decode_batch_ex: every frame an independent unit with its own state record in and
+out) on the same 262 144 frames.  A and B alternate, each timed with HIP events on the launch stream; the best of
+`reps` is kept.  roofline.frac uses the same algorithmic bytes per frame as bench.py for both forms (85 284 for
+HE-AACv2, 83 976 for HE-AACv1: SURVEY s8d -- never a smaller denominator for the streams form).
+One JSON line per (workload, T).
+usage: python tools/streams_rate.py [--frames 262144] [--reps 5] [--T 1,2,4,8] [--workloads hev2,hev2_s16,hev1]"""
+import argparse
+import importlib
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import numpy as np
+import torch
+import __graft_entry__ as G
+
+pkg = G.load_package()
+synth = importlib.import_module("ffmpeg_heaac_amd.synth")
+
+WORKLOADS = {"hev2": ("CFG_HEV2", "PCM_F32"), "hev2_s16": ("CFG_HEV2", "PCM_S16"), "hev1": ("CFG_HEV1", "PCM_F32")}
+
+
+def timed(fn):
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--frames", type=int, default=262144)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--T", default="1,2,4,8")
+    ap.add_argument("--workloads", default="hev2,hev2_s16,hev1")
+    ap.add_argument("--pool", type=int, default=1024, help="distinct streams generated; the rest are copies")
+    a = ap.parse_args()
+    n = a.frames
+    dev = pkg.Device(n)
+    hdr = synth.default_headers(pkg)
+    d_hdr = pkg.to_device(hdr)
+    Ts = [int(x) for x in a.T.split(",")]
+    for wl in a.workloads.split(","):
+        cfg_name, fmt_name = WORKLOADS[wl]
+        cfg, fmt = getattr(pkg, cfg_name), getattr(pkg, fmt_name)
+        words, nout = pkg.STATE_WORDS[cfg], pkg.OUT_CH[cfg]
+        rng = np.random.default_rng(5)
+        frs = list(synth.he_stream(rng, cfg, a.pool, max(Ts), hdr, ps_mode="20"))
+        pcm = (torch.empty((n, nout, 2048), device="cuda") if fmt == pkg.PCM_F32
+               else torch.empty((n, 2048, nout), dtype=torch.int16, device="cuda"))
+        for T in Ts:
+            S = n // T
+            assert S * T == n and S % a.pool == 0
+            # [pool][T] frames, stream s = pool stream s % pool; frame (s, t) at s * T + t
+            def stack(k):
+                x = np.stack([f[k] for f in frs[:T]], axis=1)
+                x = np.tile(x, (S // a.pool,) + (1,) * (x.ndim - 1))
+                return np.ascontiguousarray(x.reshape((n,) + x.shape[2:]))
+            coeffs = torch.from_numpy(stack("coeffs")).cuda()
+            ics, sbr = pkg.to_device(stack("ics")), pkg.to_device(stack("sbr"))
+            ps = pkg.to_device(stack("ps")) if cfg == pkg.CFG_HEV2 else None
+            st_s = torch.zeros((S, words), device="cuda")
+            st_s2 = torch.empty_like(st_s)
+            st_b = torch.zeros((n, words), device="cuda")
+            st_b2 = torch.empty_like(st_b)
+            run_a = lambda: dev.he_decode_streams(cfg, coeffs, ics, sbr, d_hdr, ps, st_s, T, state_out=st_s2, pcm=pcm,
+                                                  pcm_format=fmt)
+            run_b = lambda: dev.he_decode(cfg, coeffs, ics, sbr, d_hdr, ps, st_b, state_out=st_b2, pcm=pcm, pcm_format=fmt)
+            run_a(); run_b()                               # warm-up
+            ta, tb = [], []
+            for _ in range(a.reps):
+                ta.append(timed(run_a))
+                tb.append(timed(run_b))
+            ms_a, ms_b = min(ta), min(tb)
+            bpf = pkg.ALGO_BYTES[cfg] - (nout * 2048 * 2 if fmt != pkg.PCM_F32 else 0)
+            rec = dict(workload=wl, T=T, streams=S, frames=n, streams_ms=round(ms_a, 4), batch_ms=round(ms_b, 4),
+                       speedup=round(ms_b / ms_a, 4), streams_frames_per_s=round(n / (ms_a * 1e-3)),
+                       batch_frames_per_s=round(n / (ms_b * 1e-3)), bytes_per_frame=bpf,
+                       roofline={"frac": round(bpf * n / (ms_a * 1e-3) / 8e12, 4),
+                                 "batch_frac": round(bpf * n / (ms_b * 1e-3) / 8e12, 4)},
+                       samples_ms={"streams": [round(x, 4) for x in ta], "batch": [round(x, 4) for x in tb]})
+            print(json.dumps(rec), flush=True)
+            del coeffs, ics, sbr, ps, st_s, st_s2, st_b, st_b2
+            torch.cuda.empty_cache()
+    dev.close()
+
+
+if __name__ == "__main__":
+    main()

@@ -33,8 +33,10 @@ __device__ __forceinline__ float exp2_half_normal(int twice)
 }
 __device__ __forceinline__ float exp2_half(int twice)
 {
-    // outside the normal range (never reached by legal scalefactors): saturate
-    // like exp2f does; the denormal side is rounded once more than libm's.
+    // outside the normal range: saturate like exp2f does.  uint8 records reach
+    // both sides (tests/test_edge_reach.py checks every such argument against
+    // libm bit for bit, subnormal results included); an odd argument below
+    // -252 would be rounded once more than libm's, and no record forms one.
     // (No recursion: a recursive helper is not inlined and every call then
     // saves and restores registers.)
     if (twice > 255) return __uint_as_float(0x7F800000u);

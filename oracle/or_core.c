@@ -524,8 +524,10 @@ int oracle_float_to_int16_one(float f)
     /* dsputil.c:3975-3980.  For a NEGATIVE float the reference's `0x43c0ffff - tmp` overflows int (undefined in C;
      * the two's-complement wrap is what a plain sub / sar pair computes): written out with unsigned arithmetic
      * here so that no optimiser can pick another answer.  Only reachable more than 385 full scales below zero. */
-    if (tmp & 0xf0000)
+    if (tmp & 0xf0000) {
         tmp = (int32_t)(0x43c0ffffu - (uint32_t)tmp) >> 31;
+        OR_COUNT(tmp ? OR_BR_S16_HIGH : OR_BR_S16_LOW);
+    }
     return (int16_t)(tmp - 0x8000);
 }
 
@@ -534,10 +536,29 @@ int oracle_float_to_int16_one(float f)
 int oracle_float_to_int16_sse2(float f)
 {
     long v;
-    if (!(fabsf(f) < 2147483648.0f))
+    if (!(fabsf(f) < 2147483648.0f)) {
+        OR_COUNT(OR_BR_S16_SSE2_LOW);
         return -32768;
+    }
     v = lrintf(f);
+    if (v < -32768 || v > 32767)
+        OR_COUNT(v > 0 ? OR_BR_S16_SSE2_HIGH : OR_BR_S16_SSE2_LOW);
     return v < -32768 ? -32768 : v > 32767 ? 32767 : (int)v;
+}
+
+unsigned long long or_branch_count[OR_BR_COUNT];
+
+void oracle_branch_reset(void)
+{
+    memset(or_branch_count, 0, sizeof(or_branch_count));
+}
+
+int oracle_branch_read(unsigned long long *dst, int max)
+{
+    int i;
+    for (i = 0; i < OR_BR_COUNT && i < max; i++)
+        dst[i] = or_branch_count[i];
+    return OR_BR_COUNT;
 }
 
 /* dsputil.c:3989-4001 */

@@ -43,6 +43,17 @@ typedef struct {
 /* ------------------------------------------------------------------ */
 /* a10 sbr_dequant, aacsbr.c:1089-1128                                  */
 /* ------------------------------------------------------------------ */
+/* exp2f, counting the results outside the normal range (the value is libm's) */
+static float dq_exp2f(float x)
+{
+    const float r = exp2f(x);
+    if (isinf(r))
+        OR_COUNT(OR_BR_EXP2_INF);
+    else if (r != 0.0f && fabsf(r) < FLT_MIN)
+        OR_COUNT(OR_BR_EXP2_SUBNORMAL);
+    return r;
+}
+
 static void dequant(const HeaacSbrFrame *fr, const HeaacSbrHeader *h, int cpe, sbr_ch *d0, sbr_ch *d1)
 {
     int k, e, ch;
@@ -63,8 +74,8 @@ static void dequant(const HeaacSbrFrame *fr, const HeaacSbrHeader *h, int cpe, s
         float pan_offset = c0->bs_amp_res ? 12.0f : 24.0f;
         for (e = 1; e <= c0->bs_num_env; e++) {
             for (k = 0; k < h->n[c0->bs_freq_res[e]]; k++) {
-                float temp1 = exp2f(d0->env_facs[e][k] * alpha + 7.0f);
-                float temp2 = exp2f((pan_offset - d1->env_facs[e][k]) * alpha);
+                float temp1 = dq_exp2f(d0->env_facs[e][k] * alpha + 7.0f);
+                float temp2 = dq_exp2f((pan_offset - d1->env_facs[e][k]) * alpha);
                 float fac   = temp1 / (1.0f + temp2);
                 d0->env_facs[e][k] = fac;
                 d1->env_facs[e][k] = fac * temp2;
@@ -72,8 +83,8 @@ static void dequant(const HeaacSbrFrame *fr, const HeaacSbrHeader *h, int cpe, s
         }
         for (e = 1; e <= c0->bs_num_noise; e++) {
             for (k = 0; k < h->n_q; k++) {
-                float temp1 = exp2f(NOISE_FLOOR_OFFSET - d0->noise_facs[e][k] + 1);
-                float temp2 = exp2f(12 - d1->noise_facs[e][k]);
+                float temp1 = dq_exp2f(NOISE_FLOOR_OFFSET - d0->noise_facs[e][k] + 1);
+                float temp2 = dq_exp2f(12 - d1->noise_facs[e][k]);
                 float fac   = temp1 / (1.0f + temp2);
                 d0->noise_facs[e][k] = fac;
                 d1->noise_facs[e][k] = fac * temp2;
@@ -86,10 +97,10 @@ static void dequant(const HeaacSbrFrame *fr, const HeaacSbrHeader *h, int cpe, s
             float alpha = c->bs_amp_res ? 1.0f : 0.5f;
             for (e = 1; e <= c->bs_num_env; e++)
                 for (k = 0; k < h->n[c->bs_freq_res[e]]; k++)
-                    d->env_facs[e][k] = exp2f(alpha * d->env_facs[e][k] + 6.0f);
+                    d->env_facs[e][k] = dq_exp2f(alpha * d->env_facs[e][k] + 6.0f);
             for (e = 1; e <= c->bs_num_noise; e++)
                 for (k = 0; k < h->n_q; k++)
-                    d->noise_facs[e][k] = exp2f(NOISE_FLOOR_OFFSET - d->noise_facs[e][k]);
+                    d->noise_facs[e][k] = dq_exp2f(NOISE_FLOOR_OFFSET - d->noise_facs[e][k]);
         }
     }
 }
@@ -269,6 +280,7 @@ static void hf_inverse_filter(float (*alpha0)[2], float (*alpha1)[2],
              (phi[1][1][0] * phi[1][1][0] + phi[1][1][1] * phi[1][1][1]) / 1.000001f;
 
         if (!dk) {
+            OR_COUNT(OR_BR_DK_ZERO);
             alpha1[k][0] = 0;
             alpha1[k][1] = 0;
         } else {
@@ -284,6 +296,7 @@ static void hf_inverse_filter(float (*alpha0)[2], float (*alpha1)[2],
         }
 
         if (!phi[1][0][0]) {
+            OR_COUNT(OR_BR_PHI100_ZERO);
             alpha0[k][0] = 0;
             alpha0[k][1] = 0;
         } else {
@@ -298,6 +311,7 @@ static void hf_inverse_filter(float (*alpha0)[2], float (*alpha1)[2],
 
         if (alpha1[k][0] * alpha1[k][0] + alpha1[k][1] * alpha1[k][1] >= 16.0f ||
             alpha0[k][0] * alpha0[k][0] + alpha0[k][1] * alpha0[k][1] >= 16.0f) {
+            OR_COUNT(OR_BR_ALPHA_RESET);
             alpha1[k][0] = 0;
             alpha1[k][1] = 0;
             alpha0[k][0] = 0;
@@ -525,9 +539,15 @@ static void gain_calc(const HeaacSbrHeader *h, const HeaacSbrChannel *c, sbr_ch 
                 sum[1] += s->e_curr[e][m];
             }
             gain_max = limgain[h->bs_limiter_gains] * sqrtf((FLT_EPSILON + sum[0]) / (FLT_EPSILON + sum[1]));
+            if (!(100000 > gain_max))
+                OR_COUNT(OR_BR_GAIN_MAX_1E5);
             gain_max = FFMIN(100000, gain_max);
             for (m = m0; m < m1; m++) {
                 float q_m_max  = s->q_m[e][m] * gain_max / s->gain[e][m];
+                if (s->q_m[e][m] > q_m_max)
+                    OR_COUNT(OR_BR_QM_CLAMP);
+                if (s->gain[e][m] > gain_max)
+                    OR_COUNT(OR_BR_GAIN_CLAMP);
                 s->q_m[e][m]   = FFMIN(s->q_m[e][m], q_m_max);
                 s->gain[e][m]  = FFMIN(s->gain[e][m], gain_max);
             }
@@ -539,6 +559,8 @@ static void gain_calc(const HeaacSbrHeader *h, const HeaacSbrChannel *c, sbr_ch 
                           + (delta && !s->s_m[e][m]) * s->q_m[e][m] * s->q_m[e][m];
             }
             gain_boost = sqrtf((FLT_EPSILON + sum[0]) / (FLT_EPSILON + sum[1]));
+            if (!(1.584893192 > gain_boost))
+                OR_COUNT(OR_BR_BOOST_CAP);
             gain_boost = FFMIN(1.584893192, gain_boost);
             for (m = m0; m < m1; m++) {
                 s->gain[e][m] *= gain_boost;

@@ -9,6 +9,7 @@
  */
 #include <string.h>
 #include <math.h>
+#include <float.h>
 #include "oracle.h"
 
 /* butterflies_float_c, dsputil.c:3899-3908 */
@@ -174,6 +175,11 @@ static float flt16_trunc(float pf)
     return t.f;
 }
 
+static int or_subnormal(float f)
+{
+    return f != 0.0f && fabsf(f) < FLT_MIN;
+}
+
 /* predict, aacdec.c:1271-1297 (0.5 is a double literal there: the var updates are summed in double) */
 static void or_predict(HeaacPredictorState *ps, float *coef, int output_enable)
 {
@@ -186,6 +192,8 @@ static void or_predict(HeaacPredictorState *ps, float *coef, int output_enable)
 
     k1 = ps->var0 > 1 ? ps->cor0 * flt16_even(a / ps->var0) : 0;
     k2 = ps->var1 > 1 ? ps->cor1 * flt16_even(a / ps->var1) : 0;
+    if (!(ps->var0 > 1) || !(ps->var1 > 1))
+        OR_COUNT(OR_BR_PRED_VAR_LE1);
 
     pv = flt16_round(k1 * ps->r0 + k2 * ps->r1);
     if (output_enable)
@@ -201,6 +209,9 @@ static void or_predict(HeaacPredictorState *ps, float *coef, int output_enable)
 
     ps->r1 = flt16_trunc(a * (ps->r0 - k1 * e0));
     ps->r0 = flt16_trunc(a * e0);
+    if (or_subnormal(ps->r0) || or_subnormal(ps->r1) || or_subnormal(ps->cor0) || or_subnormal(ps->cor1) ||
+        or_subnormal(ps->var0) || or_subnormal(ps->var1))
+        OR_COUNT(OR_BR_PRED_SUBNORMAL);
 }
 
 static void or_reset_predict_state(HeaacPredictorState *ps)

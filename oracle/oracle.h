@@ -132,6 +132,32 @@ int oracle_he_decode_debug(int cfg, const float *coeffs, const HeaacIcs *ics,
                            float *dump_Xhigh, float *dump_Y, float *dump_Xsbr,
                            float *dump_X);
 
+/* ---- branch counters (tests only) ----
+ * How often the edge branches of the restated path were taken since the last reset: which branches an input reaches
+ * (tests/test_edge_reach.py).  Plain static counters, NOT thread-safe; counting changes no result. */
+enum {
+    OR_BR_DK_ZERO,            /* hf_inverse_filter: dk == 0                                   (aacsbr.c:1262) */
+    OR_BR_PHI100_ZERO,        /* hf_inverse_filter: phi[1][0][0] == 0                         (:1277) */
+    OR_BR_ALPHA_RESET,        /* hf_inverse_filter: |alpha1|^2 >= 16 or |alpha0|^2 >= 16      (:1290) */
+    OR_BR_GAIN_MAX_1E5,       /* gain_calc: gain_max > 100000, clamped                        (:1579) */
+    OR_BR_GAIN_CLAMP,         /* gain_calc: gain > gain_max taken                             (:1583) */
+    OR_BR_QM_CLAMP,           /* gain_calc: q_m > q_m_max taken                               (:1582) */
+    OR_BR_BOOST_CAP,          /* gain_calc: gain_boost capped at 1.584893192                  (:1597) */
+    OR_BR_EXP2_INF,           /* sbr_dequant: an exp2f result that is +inf                    (:1099-1125) */
+    OR_BR_EXP2_SUBNORMAL,     /* sbr_dequant: an exp2f result that is subnormal */
+    OR_BR_S16_HIGH,           /* float_to_int16_one clips to 32767                            (dsputil.c:3975-3980) */
+    OR_BR_S16_LOW,            /* float_to_int16_one clips to -32768 */
+    OR_BR_S16_SSE2_HIGH,      /* the SSE2 conversion saturates to 32767 */
+    OR_BR_S16_SSE2_LOW,       /* the SSE2 conversion saturates to -32768 (NaN included) */
+    OR_BR_PRED_VAR_LE1,       /* predict: var0 or var1 <= 1, k1 / k2 = 0                      (aacdec.c:1279-1280) */
+    OR_BR_PRED_SUBNORMAL,     /* predict: a state word (r, cor, var) left subnormal */
+    OR_BR_COUNT
+};
+extern unsigned long long or_branch_count[OR_BR_COUNT];
+#define OR_COUNT(i) (or_branch_count[i]++)
+void oracle_branch_reset(void);
+int  oracle_branch_read(unsigned long long *dst, int max);   /* returns OR_BR_COUNT */
+
 /* Host-side SBR header derivation, independent restatement of
  * aacsbr.c:146-205,296-593 (used to cross-check heaac_sbr_make_header). */
 int oracle_sbr_make_header(HeaacSbrHeader *h, int sample_rate,

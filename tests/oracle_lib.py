@@ -307,6 +307,26 @@ def he_decode_debug(cfg, coeffs, ics, sbr, hdr, ps, state_in):
     return d
 
 
+# branch counters, oracle.h (same order as the OR_BR_* enum)
+BRANCHES = ("dk_zero", "phi100_zero", "alpha_reset", "gain_max_1e5", "gain_clamp", "q_m_clamp", "gain_boost_cap",
+            "exp2_inf", "exp2_subnormal", "s16_high", "s16_low", "s16_sse2_high", "s16_sse2_low",
+            "pred_var_le1", "pred_subnormal")
+
+
+def branch_reset():
+    lib().oracle_branch_reset()
+
+
+def branch_counts(reset=False):
+    """{name: times taken} of the oracle's edge branches since the last reset (process-wide, not thread-safe)."""
+    buf = np.zeros(64, np.uint64)
+    n = lib().oracle_branch_read(_p(buf), C.c_int(64))
+    assert n == len(BRANCHES), (n, len(BRANCHES))
+    if reset:
+        branch_reset()
+    return {k: int(v) for k, v in zip(BRANCHES, buf[:n])}
+
+
 def sbr_make_header(sample_rate=48000, start_freq=5, stop_freq=9, xover=0, freq_scale=2,
                     alter_scale=1, noise_bands=2, limiter_bands=2, limiter_gains=2,
                     interpol_freq=1, smoothing_mode=1, amp_res=1):

@@ -112,7 +112,7 @@ assert SBR_FRAME_DT.itemsize == 680 and PS_FRAME_DT.itemsize == 532
 EXPORTED = [
     # heaac_dsp.h
     "heaac_device_create", "heaac_device_destroy", "heaac_device_workspace_bytes",
-    "heaac_strerror", "heaac_imdct_half_batch", "heaac_lc_decode_batch",
+    "heaac_strerror", "heaac_imdct_half_batch", "heaac_lc_decode_batch", "heaac_lc_decode_streams",
     "heaac_he_decode_batch", "heaac_he_decode_batch_ex", "heaac_he_decode_streams", "heaac_qmf_analysis_batch", "heaac_qmf_synthesis_batch",
     "heaac_qmf_synthesis_ds_batch",
     "heaac_sbr_make_header", "heaac_build_info", "heaac_spectral_tools_batch",
@@ -340,6 +340,39 @@ class Device:
         _check(lib().heaac_lc_decode_batch(self._h, channels, _ptr(coeffs), _ptr(ics), _ptr(state_in),
                                            _ptr(state_out), _ptr(pcm), pcm_format, C.c_size_t(n), _stream()),
                "heaac_lc_decode_batch")
+        return pcm, state_out
+
+    def lc_decode_streams(self, channels, coeffs, ics, state_in, frames_per_stream, state_out=None, pcm=None,
+                          pcm_format=PCM_F32):
+        """heaac_lc_decode_streams: S streams x T = frames_per_stream consecutive frames each.  The per-frame tensors
+        are laid out as for lc_decode with n = S * T (frame t of stream s at s * T + t); state_in / state_out hold ONE
+        saved[] record of channels * 512 floats per stream (before frame 0 / after frame T - 1).  Returns
+        (pcm, state_out)."""
+        import torch
+        T = int(frames_per_stream)
+        words = channels * 512
+        S = state_in.numel() // words
+        n = S * T
+        # a wrong-length tensor would be a silent device out-of-bounds access: check them all here
+        assert state_in.dtype == torch.float32 and state_in.numel() == S * words, "state_in"
+        assert coeffs.dtype == torch.float32 and coeffs.numel() == n * channels * 1024, "coeffs"
+        assert ics.numel() * ics.element_size() == n * channels * ICS_DT.itemsize, "ics"
+        if state_out is None:
+            state_out = torch.empty_like(state_in)
+        else:
+            assert state_out.dtype == torch.float32 and state_out.numel() == state_in.numel(), "state_out"
+        if pcm is None:
+            if pcm_format == PCM_F32:
+                pcm = torch.empty((n, channels, 1024), dtype=torch.float32, device=coeffs.device)
+            else:
+                pcm = torch.empty((n, 1024, channels), dtype=torch.int16, device=coeffs.device)
+        else:
+            assert pcm.numel() == n * channels * 1024 and \
+                pcm.dtype == (torch.float32 if pcm_format == PCM_F32 else torch.int16), "pcm"
+        _check(lib().heaac_lc_decode_streams(self._h, channels, _ptr(coeffs), _ptr(ics), _ptr(state_in),
+                                             _ptr(state_out), _ptr(pcm), pcm_format, C.c_size_t(S), C.c_size_t(T),
+                                             _stream()),
+               "heaac_lc_decode_streams")
         return pcm, state_out
 
     # -- spectral tools before the IMDCT (M/S, intensity stereo, TNS), in place --

@@ -4,6 +4,7 @@
 // fallback exists -- if no HIP device is usable every entry point fails with
 // HEAAC_ERR_NODEVICE / HEAAC_ERR_HIP.
 #include <hip/hip_runtime.h>
+#include <stdint.h>
 #include <stdlib.h>
 #include <string.h>
 #include "heaac_dsp.h"
@@ -226,6 +227,32 @@ extern "C" int heaac_lc_decode_batch(HeaacDevice *dev, int channels,
         return HEAAC_ERR_ARG;
     return heaac_launch_lc(dev->d_tab, dev->d_rev, channels, d_coeffs, d_ics, d_state_in, d_state_out,
                            d_pcm, pcm_format, n, (hipStream_t)stream);
+}
+
+extern "C" int heaac_lc_decode_streams(HeaacDevice *dev, int channels,
+                                       const float *d_coeffs, const HeaacIcs *d_ics,
+                                       const float *d_state_in, float *d_state_out,
+                                       void *d_pcm, int pcm_format,
+                                       size_t n_streams, size_t frames_per_stream, void *stream)
+{
+    if (!dev || channels < 1 || channels > 2 ||
+        (pcm_format != HEAAC_PCM_F32_PLANAR && pcm_format != HEAAC_PCM_S16_INTERLEAVED &&
+         pcm_format != HEAAC_PCM_S16_INTERLEAVED_SSE2) || frames_per_stream == 0)
+        return HEAAC_ERR_ARG;
+    if (n_streams == 0)
+        return HEAAC_OK;
+    if (!d_coeffs || !d_ics || !d_state_in || !d_state_out || !d_pcm)
+        return HEAAC_ERR_ARG;
+    // S * T frames of channels x 1024 floats must be addressable
+    const size_t frame_bytes = (size_t)channels * 1024 * sizeof(float);
+    if (n_streams > SIZE_MAX / frames_per_stream || n_streams * frames_per_stream > SIZE_MAX / frame_bytes)
+        return HEAAC_ERR_ARG;
+    // one frame per stream: the per-frame arrays and the state are exactly the batch call's
+    if (frames_per_stream == 1)
+        return heaac_launch_lc(dev->d_tab, dev->d_rev, channels, d_coeffs, d_ics, d_state_in, d_state_out,
+                               d_pcm, pcm_format, n_streams, (hipStream_t)stream);
+    return heaac_launch_lc_streams(dev->d_tab, dev->d_rev, channels, d_coeffs, d_ics, d_state_in, d_state_out,
+                                   d_pcm, pcm_format, n_streams, frames_per_stream, (hipStream_t)stream);
 }
 
 extern "C" int heaac_spectral_tools_batch(HeaacDevice *dev, int channels, float *d_coeffs,

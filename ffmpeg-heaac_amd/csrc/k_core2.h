@@ -256,13 +256,43 @@ __device__ __forceinline__ void imdct_half_regs(const CoreTabs &L, const float *
     imdct_half_regs_tw<false>(L, in, T, eight, hl, none);
 }
 
+// Where core2_window reads the old overlap (saved[512], aacdec.c:1763) and writes the new one, as eight rows of 64:
+// row j of lane l is saved[64 j + l].  store(row, pos, v) writes saved[pos]; row = pos / 64 whenever pos is one of the
+// lane's own positions.
+//   OverlapHbm   in / out in global memory (may alias).  A row may be written mirrored (lane l stores position
+//                63 - l of it): the value is the one the lane has just formed for its own output position.
+//   OverlapRegs  row j in the lane's sv[j]: a channel's overlap carried in registers across consecutive frames
+//                (k_lc_decode_streams).  Every lane stores only its own positions, so the mirrored rows are formed
+//                by the lane that keeps them, from the same LDS operands -- no permute, no extra LDS.
+struct OverlapHbm {
+    const float *in;
+    float *out;
+    static constexpr bool kMirror = true;
+    __device__ __forceinline__ void load(float (&sv)[8], int lane) const
+    {
+#pragma unroll
+        for (int t = 0; t < 8; t++) sv[t] = in[64 * t + lane];
+    }
+    __device__ __forceinline__ void store(int, int pos, float v) const { out[pos] = v; }
+};
+struct OverlapRegs {
+    float (&sv)[8];
+    static constexpr bool kMirror = false;
+    __device__ __forceinline__ void load(float (&s)[8], int) const
+    {
+#pragma unroll
+        for (int t = 0; t < 8; t++) s[t] = sv[t];
+    }
+    __device__ __forceinline__ void store(int row, int, float v) const { sv[row] = v; }   // (pos = 64 row + lane)
+};
+
 // Windowing, overlap-add and the new overlap (aacdec.c:1763-1805) for one channel, whole
-// wave.  buf: the channel's buf[1024] in LDS; saved in / out in HBM (may alias).
+// wave.  buf: the channel's buf[1024] in LDS; ov: the old overlap in, the new one out (above).
 // emit(q, v) receives out[q]; within one call every lane's q is distinct and a group of
 // 64 consecutive positions (ascending or descending with the lane).
-template <class Emit>
+template <class Ovl, class Emit>
 __device__ __forceinline__ void core2_window(const CoreTabs &L, HeaacIcs ics, float bias, const float *buf,
-                                             const float *g_saved_in, float *g_saved_out, int lane, Emit emit)
+                                             const Ovl &ov, int lane, Emit emit)
 {
     const int ws0 = ics.window_sequence[0], ws1 = ics.window_sequence[1];
     const bool eight = ws0 == HEAAC_EIGHT_SHORT_SEQUENCE;
@@ -275,8 +305,7 @@ __device__ __forceinline__ void core2_window(const CoreTabs &L, HeaacIcs ics, fl
 
     // every read of the old overlap is issued before the new one is written (in place)
     float sv[8];
-#pragma unroll
-    for (int t = 0; t < 8; t++) sv[t] = g_saved_in[64 * t + lane];
+    ov.load(sv, lane);
 
     // ff_vector_fmul_window_c (dsputil.c:3832-3845), one (p, 2 len - 1 - p) pair per lane
     auto window64 = [&](int o, float a, const float *s1, const float *w, float &hi) {
@@ -306,7 +335,13 @@ __device__ __forceinline__ void core2_window(const CoreTabs &L, HeaacIcs ics, fl
             // temp[0..127] of the reference: first half -> out[960..1023], second half (minus
             // bias) -> saved[0..63]
             window64(960, buf[3 * 128 + 64 + lane], buf + 512, swindow, hi);
-            g_saved_out[63 - lane] = hi - bias;
+            if constexpr (Ovl::kMirror) {
+                ov.store(0, 63 - lane, hi - bias);
+            } else {
+                const int p = 63 - lane;      // window64's pair p, as formed by the lane that keeps saved[63 - p]
+                const float a = buf[3 * 128 + 64 + p], b = buf[512 + 63 - p], wi = swindow[p], wj = swindow[127 - p];
+                ov.store(0, lane, a * wi + b * wj + bias - bias);
+            }
         } else {
             float hi;
             window64(448, sv[7], buf, swindow_prev, hi);
@@ -315,24 +350,31 @@ __device__ __forceinline__ void core2_window(const CoreTabs &L, HeaacIcs ics, fl
             for (int t = 9; t < 16; t++) emit(64 * t + lane, buf[64 * t + lane - 512] + bias);
         }
     }
-    // buffer update (aacdec.c:1793-1805), straight to HBM
+    // buffer update (aacdec.c:1793-1805): positions 64 + 128 j + p and 64 + 128 j + 127 - p are rows 1 + 2 j
+    // (lane p) and 2 + 2 j (lane 63 - p)
     if (eight) {
 #pragma unroll
         for (int j = 0; j < 3; j++) {
             const int p = lane;
             const float a = buf[(4 + j) * 128 + 64 + p], b = buf[(5 + j) * 128 + 63 - p];
             const float wi = swindow[p], wj = swindow[127 - p];
-            g_saved_out[64 + 128 * j + p]       = a * wj - b * wi + 0.0f;
-            g_saved_out[64 + 128 * j + 127 - p] = a * wi + b * wj + 0.0f;
+            ov.store(1 + 2 * j, 64 + 128 * j + p, a * wj - b * wi + 0.0f);
+            if constexpr (Ovl::kMirror) {
+                ov.store(2 + 2 * j, 64 + 128 * j + 127 - p, a * wi + b * wj + 0.0f);
+            } else {
+                const int q = 63 - lane;
+                const float a2 = buf[(4 + j) * 128 + 64 + q], b2 = buf[(5 + j) * 128 + 63 - q];
+                ov.store(2 + 2 * j, 128 + 128 * j + lane, a2 * swindow[q] + b2 * swindow[127 - q] + 0.0f);
+            }
         }
-        g_saved_out[448 + lane] = buf[7 * 128 + 64 + lane];
+        ov.store(7, 448 + lane, buf[7 * 128 + 64 + lane]);
     } else if (ws0 == HEAAC_LONG_START_SEQUENCE) {
 #pragma unroll
-        for (int t = 0; t < 7; t++) g_saved_out[64 * t + lane] = buf[512 + 64 * t + lane];
-        g_saved_out[448 + lane] = buf[7 * 128 + 64 + lane];
+        for (int t = 0; t < 7; t++) ov.store(t, 64 * t + lane, buf[512 + 64 * t + lane]);
+        ov.store(7, 448 + lane, buf[7 * 128 + 64 + lane]);
     } else {
 #pragma unroll
-        for (int t = 0; t < 8; t++) g_saved_out[64 * t + lane] = buf[512 + 64 * t + lane];
+        for (int t = 0; t < 8; t++) ov.store(t, 64 * t + lane, buf[512 + 64 * t + lane]);
     }
 }
 

@@ -182,12 +182,11 @@ void k_core_ana(const float *__restrict__ g_tab, const uint16_t *__restrict__ g_
 #pragma unroll
             for (int t = 0; t < 5; t++) xh[t] = 64 * t + lane < 288 ? xh_in[64 * t + lane] : 0.0f;
             const float *buf = reinterpret_cast<const float *>(c ? T1 : T0);
+            const OverlapHbm ov{ st_in + off_saved, st_out + off_saved };
             if (scale != 1.0f)
-                core2_window(L, c ? ics1 : ics0, 0.0f, buf, st_in + off_saved, st_out + off_saved, lane,
-                             [&](int q, float v) { x[288 + q] = v * scale; });
+                core2_window(L, c ? ics1 : ics0, 0.0f, buf, ov, lane, [&](int q, float v) { x[288 + q] = v * scale; });
             else
-                core2_window(L, c ? ics1 : ics0, 0.0f, buf, st_in + off_saved, st_out + off_saved, lane,
-                             [&](int q, float v) { x[288 + q] = v; });
+                core2_window(L, c ? ics1 : ics0, 0.0f, buf, ov, lane, [&](int q, float v) { x[288 + q] = v; });
 #pragma unroll
             for (int t = 0; t < 5; t++) if (64 * t + lane < 288) x[64 * t + lane] = xh[t];
         }

@@ -6,6 +6,7 @@
 //
 // Persistent workgroups of 12 wavefronts; each wavefront owns two channels at a time (one per
 // half-wave, FFT in registers: k_core2.h), tables live in LDS for the life of the workgroup.
+// k_lc_decode_streams walks T consecutive frames per stream with each channel's overlap in registers.
 // HBM traffic per frame is the algorithmic minimum: coefficients and overlap read once, PCM and
 // overlap written once.  The LDS-FFT kernels further down serve the stage-level
 // heaac_imdct_half_batch and the FFTContext shim.
@@ -35,6 +36,34 @@ struct Lc2Wave {
     cpx T[2][C2_TSTRIDE];         // per channel: coefficients, transposes, then buf[1024]
     uint16_t pcm0[1024];          // left channel of an interleaved int16 pair
 };
+
+// Windowing, overlap and PCM of unit c of a wave's pair (u: the unit's coefficient / ICS row, u0: the pair's first).
+// c == 1 of an interleaved int16 CPE takes the left channel's samples that c == 0 left in w.pcm0.
+template <int CH, int FMT, class Ovl>
+__device__ __forceinline__ void lc2_window(const CoreTabs &LT, HeaacIcs ics, const float *buf, const Ovl &ov, int lane,
+                                           int c, unsigned long long u, unsigned long long u0, void *g_pcm, Lc2Wave &w)
+{
+    // add_bias: 385 for the C conversion, 0 for the SIMD configuration (aacdec.c:573-581)
+    constexpr float LC_BIAS = FMT == HEAAC_PCM_S16_INTERLEAVED_SSE2 ? 0.0f : HEAAC_ADD_BIAS;
+    if (FMT == HEAAC_PCM_F32_PLANAR) {
+        float *o = reinterpret_cast<float *>(g_pcm) + u * 1024;
+        core2_window(LT, ics, LC_BIAS, buf, ov, lane, [&](int q, float v) { LC_ST(o + q, v); });
+    } else if (CH == 1) {
+        int16_t *o = reinterpret_cast<int16_t *>(g_pcm) + u * 1024;
+        core2_window(LT, ics, LC_BIAS, buf, ov, lane,
+                     [&](int q, float v) { LC_ST(o + q, (int16_t)pcm_int16<FMT>(v)); });
+    } else if (c == 0) {
+        core2_window(LT, ics, LC_BIAS, buf, ov, lane,
+                     [&](int q, float v) { w.pcm0[q] = (uint16_t)pcm_int16<FMT>(v); });
+        wave_sync();
+    } else {
+        // float_to_int16_interleave (dsputil.c:3989-4001): L from LDS, R fresh
+        uint32_t *o = reinterpret_cast<uint32_t *>(g_pcm) + (u0 / 2) * 1024;
+        core2_window(LT, ics, LC_BIAS, buf, ov, lane, [&](int q, float v) {
+            LC_ST(o + q, (uint32_t)w.pcm0[q] | ((uint32_t)(pcm_int16<FMT>(v) & 0xffff) << 16));
+        });
+    }
+}
 
 template <int CH, int FMT>
 __global__ __launch_bounds__(LC2_WAVES * WAVE)
@@ -68,36 +97,99 @@ void k_lc_decode(const float *__restrict__ g_tab, const uint16_t *__restrict__ g
             const bool eight = (half ? ics1.window_sequence[0] : ics0.window_sequence[0]) == HEAAC_EIGHT_SHORT_SEQUENCE;
             imdct_half_regs(LT, reinterpret_cast<const float *>(w.T[half]), w.T[half], eight, hl);
         }
-        // add_bias: 385 for the C conversion, 0 for the SIMD configuration (aacdec.c:573-581)
-        constexpr float LC_BIAS = FMT == HEAAC_PCM_S16_INTERLEAVED_SSE2 ? 0.0f : HEAAC_ADD_BIAS;
 #pragma unroll
         for (int c = 0; c < 2; c++) {
             if (c == 1 && !have1) break;
             const unsigned long long u = c ? u1 : u0;
-            const HeaacIcs ics = c ? ics1 : ics0;
-            const float *buf = reinterpret_cast<const float *>(w.T[c]);
-            const float *sin_ = g_state_in + u * 512;
-            float *sout = g_state_out + u * 512;
-            if (FMT == HEAAC_PCM_F32_PLANAR) {
-                float *o = reinterpret_cast<float *>(g_pcm) + u * 1024;
-                core2_window(LT, ics, LC_BIAS, buf, sin_, sout, lane, [&](int q, float v) { LC_ST(o + q, v); });
-            } else if (CH == 1) {
-                int16_t *o = reinterpret_cast<int16_t *>(g_pcm) + u * 1024;
-                core2_window(LT, ics, LC_BIAS, buf, sin_, sout, lane,
-                             [&](int q, float v) { LC_ST(o + q, (int16_t)pcm_int16<FMT>(v)); });
-            } else if (c == 0) {
-                core2_window(LT, ics, LC_BIAS, buf, sin_, sout, lane,
-                             [&](int q, float v) { w.pcm0[q] = (uint16_t)pcm_int16<FMT>(v); });
-                wave_sync();
-            } else {
-                // float_to_int16_interleave (dsputil.c:3989-4001): L from LDS, R fresh
-                uint32_t *o = reinterpret_cast<uint32_t *>(g_pcm) + (u0 / 2) * 1024;
-                core2_window(LT, ics, LC_BIAS, buf, sin_, sout, lane, [&](int q, float v) {
-                    LC_ST(o + q, (uint32_t)w.pcm0[q] | ((uint32_t)(pcm_int16<FMT>(v) & 0xffff) << 16));
-                });
-            }
+            const OverlapHbm ov{ g_state_in + u * 512, g_state_out + u * 512 };
+            lc2_window<CH, FMT>(LT, c ? ics1 : ics0, reinterpret_cast<const float *>(w.T[c]), ov, lane, c, u, u0,
+                                g_pcm, w);
         }
         wave_sync();
+    }
+}
+
+// ---------------------------------------------------------------------------
+// k_lc_decode_streams: S streams x T consecutive frames, frame t of stream s at s * T + t of the per-frame arrays,
+// one state record per stream (read before frame 0, written after frame T - 1).  A wave walks its two units' chains
+// in t order, as k_lc_decode's two half-waves:
+//   CH 2  the two channels of one stream;
+//   CH 1  streams 2 k and 2 k + 1, in lockstep (the batch kernel's pair of consecutive frames would be dependent
+//         here).  With odd S the last wave's second half repeats the first stream, its stores masked (have1).
+// Each unit's overlap is read once into the sv[8] registers core2_window works on and stays there across the T
+// frames (OverlapRegs): per frame only coefficients, ICS and PCM move through HBM.
+// ---------------------------------------------------------------------------
+// Waves per workgroup, per instantiation.  The 16 carry registers do not fit in k_lc_decode's 168 VGPRs (12 waves,
+// three per SIMD): at 12 the f32 and mono forms spill 25 - 37 VGPRs and lose their gain over the batch call, so they
+// run 8 (two per SIMD, up to 256 VGPRs, no spill); stereo int16 spills 10 - 13 at 12 and is as fast or faster there
+// than at 8 (A/B in profiles/r06_lc_streams_waves_ab.jsonl, DESIGN s4).  -DLCS_WAVES=<n> builds every instantiation
+// with n waves, for that A/B.
+template <int CH, int FMT>
+constexpr int lcs_waves()
+{
+#ifdef LCS_WAVES
+    return LCS_WAVES;
+#else
+    return CH == 2 && FMT != HEAAC_PCM_F32_PLANAR ? 12 : 8;
+#endif
+}
+
+template <int CH, int FMT>
+__global__ __launch_bounds__((lcs_waves<CH, FMT>() * WAVE))
+void k_lc_decode_streams(const float *__restrict__ g_tab, const uint16_t *__restrict__ g_rev,
+                         const float *__restrict__ g_coeffs, const HeaacIcs *__restrict__ g_ics,
+                         const float *g_state_in, float *g_state_out,
+                         void *__restrict__ g_pcm, unsigned long long S, unsigned long long T)
+{
+    constexpr int NW = lcs_waves<CH, FMT>();
+    __shared__ Core2Lds L;
+    __shared__ Lc2Wave W[NW];
+    core2_lds_init(L, g_tab, g_rev);
+    const CoreTabs LT = core2_tabs(L);
+    __syncthreads();
+
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / WAVE), lane = threadIdx.x % WAVE;
+    Lc2Wave &w = W[wave];
+    const unsigned long long chains = CH == 2 ? S : (S + 1) / 2;
+
+    for (unsigned long long pr = (unsigned long long)blockIdx.x * NW + wave; pr < chains;
+         pr += (unsigned long long)gridDim.x * NW) {
+        // state records of 512 floats: CH 2 -> channel c of stream pr, CH 1 -> stream 2 pr + c
+        const bool have1 = CH == 2 || 2 * pr + 1 < S;                   // uniform
+        const unsigned long long r0 = 2 * pr, r1 = have1 ? r0 + 1 : r0;
+        // unit (coefficient / ICS row) of frame t: base + CH * t
+        const unsigned long long base0 = r0 * T;
+        const unsigned long long base1 = CH == 2 ? r0 * T + 1 : r1 * T;
+        float sv[2][8];
+#pragma unroll
+        for (int j = 0; j < 8; j++) {
+            sv[0][j] = g_state_in[r0 * 512 + 64 * j + lane];
+            sv[1][j] = g_state_in[r1 * 512 + 64 * j + lane];
+        }
+        for (unsigned long long t = 0; t < T; t++) {
+            const unsigned long long u0 = base0 + CH * t, u1 = base1 + CH * t;
+            const HeaacIcs ics0 = g_ics[u0], ics1 = g_ics[u1];
+            core2_stage_coeffs(reinterpret_cast<float *>(w.T[0]), g_coeffs + u0 * 1024, lane);
+            core2_stage_coeffs(reinterpret_cast<float *>(w.T[1]), g_coeffs + u1 * 1024, lane);
+            wave_sync();
+            {
+                const int half = lane >> 5, hl = lane & 31;
+                const bool eight = (half ? ics1.window_sequence[0] : ics0.window_sequence[0]) == HEAAC_EIGHT_SHORT_SEQUENCE;
+                imdct_half_regs(LT, reinterpret_cast<const float *>(w.T[half]), w.T[half], eight, hl);
+            }
+#pragma unroll
+            for (int c = 0; c < 2; c++) {
+                if (c == 1 && !have1) break;
+                lc2_window<CH, FMT>(LT, c ? ics1 : ics0, reinterpret_cast<const float *>(w.T[c]), OverlapRegs{ sv[c] },
+                                    lane, c, c ? u1 : u0, u0, g_pcm, w);
+            }
+            wave_sync();
+        }
+#pragma unroll
+        for (int j = 0; j < 8; j++) {
+            g_state_out[r0 * 512 + 64 * j + lane] = sv[0][j];
+            if (have1) g_state_out[r1 * 512 + 64 * j + lane] = sv[1][j];
+        }
     }
 }
 
@@ -235,6 +327,30 @@ extern "C" int heaac_launch_lc(const float *d_tab, const uint16_t *d_rev, int ch
 #define LAUNCH(CH, FMT) \
     hipLaunchKernelGGL((k_lc_decode<CH, FMT>), dim3(grid), b, 0, s, d_tab, d_rev, d_coeffs, d_ics, \
                        d_state_in, d_state_out, d_pcm, (unsigned long long)n)
+    if (channels == 1 && pcm_format == HEAAC_PCM_F32_PLANAR) LAUNCH(1, HEAAC_PCM_F32_PLANAR);
+    else if (channels == 1 && pcm_format == HEAAC_PCM_S16_INTERLEAVED) LAUNCH(1, HEAAC_PCM_S16_INTERLEAVED);
+    else if (channels == 2 && pcm_format == HEAAC_PCM_F32_PLANAR) LAUNCH(2, HEAAC_PCM_F32_PLANAR);
+    else if (channels == 2 && pcm_format == HEAAC_PCM_S16_INTERLEAVED) LAUNCH(2, HEAAC_PCM_S16_INTERLEAVED);
+    else if (channels == 1 && pcm_format == HEAAC_PCM_S16_INTERLEAVED_SSE2) LAUNCH(1, HEAAC_PCM_S16_INTERLEAVED_SSE2);
+    else if (channels == 2 && pcm_format == HEAAC_PCM_S16_INTERLEAVED_SSE2) LAUNCH(2, HEAAC_PCM_S16_INTERLEAVED_SSE2);
+    else return HEAAC_ERR_ARG;
+#undef LAUNCH
+    return hipGetLastError() == hipSuccess ? HEAAC_OK : HEAAC_ERR_HIP;
+}
+
+extern "C" int heaac_launch_lc_streams(const float *d_tab, const uint16_t *d_rev, int channels,
+                                       const float *d_coeffs, const HeaacIcs *d_ics,
+                                       const float *d_state_in, float *d_state_out,
+                                       void *d_pcm, int pcm_format, size_t n_streams, size_t frames_per_stream,
+                                       hipStream_t s)
+{
+    if (n_streams == 0) return HEAAC_OK;
+    const unsigned long long S = n_streams, T = frames_per_stream;
+    const unsigned long long chains = channels == 2 ? S : (S + 1) / 2;
+#define LAUNCH(CH, FMT) \
+    hipLaunchKernelGGL((k_lc_decode_streams<CH, FMT>), dim3(grid_for(chains, lcs_waves<CH, FMT>(), 1)), \
+                       dim3(lcs_waves<CH, FMT>() * WAVE), 0, s, d_tab, d_rev, d_coeffs, d_ics, \
+                       d_state_in, d_state_out, d_pcm, S, T)
     if (channels == 1 && pcm_format == HEAAC_PCM_F32_PLANAR) LAUNCH(1, HEAAC_PCM_F32_PLANAR);
     else if (channels == 1 && pcm_format == HEAAC_PCM_S16_INTERLEAVED) LAUNCH(1, HEAAC_PCM_S16_INTERLEAVED);
     else if (channels == 2 && pcm_format == HEAAC_PCM_F32_PLANAR) LAUNCH(2, HEAAC_PCM_F32_PLANAR);

@@ -277,6 +277,23 @@ int heaac_lc_decode_batch(HeaacDevice *dev, int channels,
                           void *d_pcm, int pcm_format,
                           size_t n, void *stream);
 
+/* Several consecutive frames of each stream in one call ("streams form"): S streams x T frames each.
+ *   The per-frame arrays have the layout of heaac_lc_decode_batch with n = S * T, frame t of stream s at index
+ *   s * T + t:  d_coeffs [S][T][channels][1024], d_ics [S][T][channels], d_pcm [S][T][channels][1024] (F32) or
+ *   [S][T][1024][channels] (S16).  The state is per stream: d_state_in [S][channels*512] holds each stream's saved[]
+ *   before its frame 0, d_state_out the saved[] after its frame T - 1 (they may alias).
+ * PCM and final state are bit-identical to T chained heaac_lc_decode_batch calls, for channels 1 and 2 and every PCM
+ * format.  The overlap stays on chip between a stream's frames, so HBM carries it once per call instead of twice per
+ * frame.  Same contract as the batch call: no allocation, no synchronisation, capturable into a hipGraph, and no
+ * use of the device workspace (LC calls on other streams stay legal).  T has no upper bound.
+ * Returns HEAAC_ERR_ARG for channels other than 1 or 2, a bad pcm_format, frames_per_stream == 0, a NULL pointer
+ * (n_streams > 0) or S * T * channels * 1024 floats that do not fit a size_t; n_streams == 0 is HEAAC_OK. */
+int heaac_lc_decode_streams(HeaacDevice *dev, int channels,
+                            const float *d_coeffs, const HeaacIcs *d_ics,
+                            const float *d_state_in, float *d_state_out,
+                            void *d_pcm, int pcm_format,
+                            size_t n_streams, size_t frames_per_stream, void *stream);
+
 /* AFTER_IMDCT independent channel coupling: apply_independent_coupling()
  * (aacdec.c:1849-1862) the way spectral_to_sample() applies it to an SCE / CPE once the element's own
  * IMDCT is done (:1929-1930, apply_channel_coupling :1870-1898), AAC-LC (no SBR: len = 1024):

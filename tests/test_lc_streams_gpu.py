@@ -1,0 +1,245 @@
+"""heaac_lc_decode_streams (S streams x T consecutive AAC-LC frames in one call) on the GPU: every PCM word and the final
+state bit-exact against the oracle chained frame by frame, and word for word against T chained lc_decode calls."""
+import ctypes as C
+import importlib
+
+import numpy as np
+import pytest
+
+import edge_signals as E
+
+pytestmark = pytest.mark.gpu
+
+FMTS = ("PCM_F32", "PCM_S16", "PCM_S16_SSE2")
+
+
+def _synth():
+    return importlib.import_module("ffmpeg_heaac_amd.synth")
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+def _frames(S, T, channels, seed, loud=200.0):
+    """lc_stream steps stacked per stream: coeffs [S][T][channels][1024], ics [S][T][channels]"""
+    rng = np.random.default_rng(seed)
+    steps = list(_synth().lc_stream(rng, S, T, channels))
+    coeffs = np.stack([c for c, _ in steps], axis=1)
+    ics = np.stack([i for _, i in steps], axis=1)
+    coeffs[::17] *= loud                       # loud streams now and then so the int16 saturation branch runs
+    return np.ascontiguousarray(coeffs), np.ascontiguousarray(ics)
+
+
+def _flat(a):
+    return np.ascontiguousarray(a.reshape((a.shape[0] * a.shape[1],) + a.shape[2:]))
+
+
+def _oracle_chain(oracle, channels, coeffs, ics, state, fmt):
+    """oracle.lc_decode_batch frame position by frame position: PCM [S][T][...] and the state after the last frame"""
+    pcms = []
+    for t in range(coeffs.shape[1]):
+        p, state = oracle.lc_decode_batch(channels, np.ascontiguousarray(coeffs[:, t]), np.ascontiguousarray(ics[:, t]),
+                                          state, fmt)
+        pcms.append(p)
+    return np.stack(pcms, axis=1), state
+
+
+def _streams(pkg, dev, channels, coeffs, ics, state, fmt, in_place=False):
+    import torch
+    S, T = coeffs.shape[:2]
+    d_state = torch.from_numpy(np.ascontiguousarray(state)).cuda()
+    pcm, st = dev.lc_decode_streams(channels, torch.from_numpy(_flat(coeffs)).cuda(), pkg.to_device(_flat(ics)),
+                                    d_state, T, state_out=d_state if in_place else None, pcm_format=fmt)
+    if in_place:
+        assert st.data_ptr() == d_state.data_ptr()
+    torch.cuda.synchronize()
+    return pcm.cpu().numpy().reshape((S, T) + pcm.shape[1:]), st.cpu().numpy()
+
+
+def _assert_same(pkg, fmt, got, ref, what):
+    if fmt == pkg.PCM_F32:
+        d = _bits(got) != _bits(ref)
+    else:
+        d = got != ref
+    assert not d.any(), "%s: %d words differ, first at %s" % (what, int(d.sum()), np.argwhere(d)[:3].tolist())
+
+
+def _state0(rng, S, channels):
+    return (rng.standard_normal((S, channels * 512)) * 1e-3).astype(np.float32)
+
+
+@pytest.mark.parametrize("T", [1, 2, 3, 8])
+@pytest.mark.parametrize("fmtname", FMTS)
+@pytest.mark.parametrize("channels", [1, 2])
+def test_lc_streams_match_oracle(pkg, oracle, dev, channels, fmtname, T):
+    fmt = getattr(pkg, fmtname)
+    S = 97
+    # the SSE2 configuration's samples come out on a scale 32768 times smaller: louder still to saturate
+    coeffs, ics = _frames(S, T, channels, 300 + 10 * channels + T,
+                          loud=200.0 * (32768 if fmt == pkg.PCM_S16_SSE2 else 1))
+    state = _state0(np.random.default_rng(T), S, channels)
+    ref_pcm, ref_state = _oracle_chain(oracle, channels, coeffs, ics, state, fmt)
+    got_pcm, got_state = _streams(pkg, dev, channels, coeffs, ics, state, fmt)
+    for t in range(T):
+        _assert_same(pkg, fmt, got_pcm[:, t], ref_pcm[:, t], "frame %d PCM" % t)
+    _assert_same(pkg, pkg.PCM_F32, got_state, ref_state, "final state")
+    if fmt != pkg.PCM_F32:
+        assert (np.abs(ref_pcm.astype(int)) == 32767).any() or (ref_pcm == -32768).any()
+
+
+@pytest.mark.parametrize("channels", [1, 2])
+def test_lc_streams_see_every_window_transition(pkg, oracle, dev, channels):
+    """one call over 8 frames: ONLY_LONG->ONLY_LONG, ->START, START->SHORT, SHORT->SHORT / STOP, STOP->LONG all inside
+    the chain, where the carried overlap (and the mirrored rows of EIGHT_SHORT) feed the next frame"""
+    S, T = 97, 8
+    coeffs, ics = _frames(S, T, channels, 77 + channels)
+    seen = set(map(tuple, ics["window_sequence"][:, 1:].reshape(-1, 2)))
+    assert {(0, 0), (1, 0), (2, 1), (3, 2), (0, 3)} <= seen
+    state = _state0(np.random.default_rng(5), S, channels)
+    ref_pcm, ref_state = _oracle_chain(oracle, channels, coeffs, ics, state, pkg.PCM_F32)
+    got_pcm, got_state = _streams(pkg, dev, channels, coeffs, ics, state, pkg.PCM_F32)
+    _assert_same(pkg, pkg.PCM_F32, got_pcm, ref_pcm, "PCM")
+    _assert_same(pkg, pkg.PCM_F32, got_state, ref_state, "final state")
+
+
+def test_lc_streams_equal_chained_batch_calls(pkg, dev):
+    """S x T = 262 144 stereo frames: the streams call equals T chained lc_decode calls word for word"""
+    import torch
+    S, T, pool = 32768, 8, 512
+    coeffs, ics = _frames(pool, T, 2, 9)
+    reps = S // pool
+    d_coeffs = torch.from_numpy(coeffs).cuda().repeat(reps, 1, 1, 1)          # [S][T][2][1024]
+    d_ics = pkg.to_device(ics).reshape(pool, T, -1).repeat(reps, 1, 1)
+    state = torch.from_numpy(_state0(np.random.default_rng(1), pool, 2)).cuda().repeat(reps, 1)
+    state[pool:] *= torch.linspace(0.5, 2.0, S - pool, device="cuda")[:, None]   # distinct states per copy
+    pcm_s, st_s = dev.lc_decode_streams(2, d_coeffs.reshape(S * T, 2, 1024).contiguous(),
+                                        d_ics.reshape(-1).contiguous(), state.contiguous(), T)
+    st = state.clone()
+    pcm_b = torch.empty((S, T, 2, 1024), device="cuda")
+    for t in range(T):
+        p, st = dev.lc_decode(2, d_coeffs[:, t].contiguous(), d_ics[:, t].reshape(-1).contiguous(), st)
+        pcm_b[:, t] = p
+    torch.cuda.synchronize()
+    assert torch.equal(pcm_s.view(torch.int32).reshape(S, T, 2, 1024), pcm_b.view(torch.int32))
+    assert torch.equal(st_s.view(torch.int32), st.view(torch.int32))
+
+
+@pytest.mark.parametrize("channels,S", [(1, 33), (2, 20)])
+def test_lc_streams_in_place(pkg, oracle, dev, channels, S):
+    T = 5
+    coeffs, ics = _frames(S, T, channels, 60 + channels)
+    state = _state0(np.random.default_rng(S), S, channels)
+    ref_pcm, ref_state = _oracle_chain(oracle, channels, coeffs, ics, state, pkg.PCM_S16)
+    got_pcm, got_state = _streams(pkg, dev, channels, coeffs, ics, state, pkg.PCM_S16, in_place=True)
+    _assert_same(pkg, pkg.PCM_S16, got_pcm, ref_pcm, "PCM")
+    _assert_same(pkg, pkg.PCM_F32, got_state, ref_state, "final state")
+
+
+@pytest.mark.parametrize("channels,S", [(1, 1), (1, 2), (1, 5), (2, 1), (2, 3)])
+def test_lc_streams_long_chain(pkg, oracle, dev, channels, S):
+    """T = 150: one wave walks a whole stream (S = 1: one wave walks everything)"""
+    T = 150
+    coeffs, ics = _frames(S, T, channels, 150 + S)
+    state = np.zeros((S, channels * 512), np.float32)
+    ref_pcm, ref_state = _oracle_chain(oracle, channels, coeffs, ics, state, pkg.PCM_F32)
+    got_pcm, got_state = _streams(pkg, dev, channels, coeffs, ics, state, pkg.PCM_F32)
+    _assert_same(pkg, pkg.PCM_F32, got_pcm, ref_pcm, "PCM")
+    _assert_same(pkg, pkg.PCM_F32, got_state, ref_state, "final state")
+
+
+@pytest.mark.parametrize("channels", [1, 2])
+def test_lc_streams_position_independent(pkg, dev, channels):
+    """a stream decoded alone equals the same stream decoded among 4099 others, wherever it sits"""
+    S, T = 4099, 4
+    coeffs, ics = _frames(S, T, channels, 21 + channels)
+    state = _state0(np.random.default_rng(2), S, channels)
+    all_pcm, all_state = _streams(pkg, dev, channels, coeffs, ics, state, pkg.PCM_F32)
+    for s in (0, 1, 2, 1000, 2047, 4097, 4098):
+        p, st = _streams(pkg, dev, channels, coeffs[s:s + 1], ics[s:s + 1], state[s:s + 1], pkg.PCM_F32)
+        _assert_same(pkg, pkg.PCM_F32, p[0], all_pcm[s], "stream %d PCM" % s)
+        _assert_same(pkg, pkg.PCM_F32, st[0], all_state[s], "stream %d state" % s)
+
+
+def _assert_words(got, ref, what):
+    """f32 words bit for bit; a NaN of the reference is matched by any NaN (as tests/test_edges_gpu.py)"""
+    got, ref = np.asarray(got, np.float32), np.asarray(ref, np.float32)
+    ok = (_bits(got) == _bits(ref)) | (np.isnan(got) & np.isnan(ref))
+    assert ok.all(), "%s: %d words differ, first at %s" % (what, int((~ok).sum()), np.argwhere(~ok)[:3].tolist())
+
+
+@pytest.mark.parametrize("fmtname", FMTS[:2])
+@pytest.mark.parametrize("channels", [1, 2])
+@pytest.mark.parametrize("profile", E.CORE_PROFILES)
+def test_lc_streams_edges(pkg, oracle, dev, profile, channels, fmtname):
+    fmt = getattr(pkg, fmtname)
+    S, T = E.STREAMS + 1, E.min_steps(profile)
+    frames = E.lc_frames(_synth(), profile, S, T, E.SEED, channels)
+    coeffs = np.stack([c for c, _ in frames], axis=1)
+    ics = np.stack([i for _, i in frames], axis=1)
+    state = np.zeros((S, channels * 512), np.float32)
+    ref_pcm, ref_state = _oracle_chain(oracle, channels, coeffs, ics, state, fmt)
+    got_pcm, got_state = _streams(pkg, dev, channels, coeffs, ics, state, fmt)
+    for t in range(T):
+        if fmt == pkg.PCM_F32:
+            _assert_words(got_pcm[:, t], ref_pcm[:, t], "frame %d PCM" % t)
+        else:
+            assert np.array_equal(got_pcm[:, t], ref_pcm[:, t]), "frame %d PCM" % t
+    _assert_words(got_state, ref_state, "final state")
+
+
+def test_lc_streams_argument_errors(pkg, dev):
+    import torch
+    f = pkg.lib().heaac_lc_decode_streams
+    f.restype = C.c_int
+    f.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.c_int, C.c_size_t, C.c_size_t, C.c_void_p]
+    buf = torch.zeros(4 * 2 * 1024, device="cuda")
+    p = C.c_void_p(buf.data_ptr())
+    ERR = -1
+
+    def call(channels=2, fmt=pkg.PCM_F32, S=2, T=2, ptrs=None):
+        ptrs = ptrs or [p] * 5
+        return f(dev._h, channels, *ptrs, fmt, S, T, None)
+    for ch in (0, 3, -1):
+        assert call(channels=ch) == ERR
+    for fmt in (-1, 3, 99):
+        assert call(fmt=fmt) == ERR
+    assert call(T=0) == ERR
+    assert call(S=0, T=0) == ERR
+    for k in range(5):
+        ptrs = [p] * 5
+        ptrs[k] = None
+        assert call(ptrs=ptrs) == ERR, k
+    big = 1 << 62
+    assert call(S=big, T=4) == ERR                 # S * T overflows
+    assert call(S=1 << 43, T=1 << 10) == ERR       # S * T fits, S * T * channels * 1024 does not
+    assert call(S=0, T=3) == 0                     # no streams: nothing to do
+    assert call(S=0, T=3, ptrs=[None] * 5) == 0
+    torch.cuda.synchronize()
+    assert not buf.any()                           # nothing ran
+
+
+def test_lc_streams_graph_capture(pkg, oracle, dev):
+    import torch
+    S, T, channels = 7, 4, 2
+    coeffs, ics = _frames(S, T, channels, 43)
+    state = _state0(np.random.default_rng(3), S, channels)
+    ref_pcm, ref_state = _oracle_chain(oracle, channels, coeffs, ics, state, pkg.PCM_S16)
+    d_coeffs, d_ics = torch.from_numpy(_flat(coeffs)).cuda(), pkg.to_device(_flat(ics))
+    st_in = torch.from_numpy(state).cuda()
+    st_out = torch.empty_like(st_in)
+    pcm = torch.empty((S * T, 1024, channels), dtype=torch.int16, device="cuda")
+    s = torch.cuda.Stream()
+    with torch.cuda.stream(s):
+        dev.lc_decode_streams(channels, d_coeffs, d_ics, st_in, T, state_out=st_out, pcm=pcm, pcm_format=pkg.PCM_S16)
+        s.synchronize()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g, stream=s):
+            dev.lc_decode_streams(channels, d_coeffs, d_ics, st_in, T, state_out=st_out, pcm=pcm,
+                                  pcm_format=pkg.PCM_S16)
+    pcm.zero_()
+    st_out.zero_()
+    g.replay()
+    torch.cuda.synchronize()
+    assert np.array_equal(pcm.cpu().numpy().reshape(ref_pcm.shape), ref_pcm)
+    _assert_same(pkg, pkg.PCM_F32, st_out.cpu().numpy(), ref_state, "final state")

@@ -1,10 +1,12 @@
-"""The streams form (heaac_he_decode_streams: S streams x T consecutive frames, state in once and out once per stream)
-against the batch form (heaac_he_decode_batch_ex: every frame an independent unit with its own state record in and
-out) on the same 262 144 frames.  A and B alternate, each timed with HIP events on the launch stream; the best of
+"""The streams form (heaac_he_decode_streams / heaac_lc_decode_streams: S streams x T consecutive frames, state in once
+and out once per stream) against the batch form (heaac_he_decode_batch_ex / heaac_lc_decode_batch: every frame an
+independent unit with its own state record in and out) on the same 262 144 frames.  A and B alternate, each timed with HIP events on the launch stream; the best of
 `reps` is kept.  roofline.frac uses the same algorithmic bytes per frame as bench.py for both forms (85 284 for
-HE-AACv2, 83 976 for HE-AACv1: SURVEY s8d -- never a smaller denominator for the streams form).
+HE-AACv2, 83 976 for HE-AACv1, 24 584 / 12 292 / 20 488 for AAC-LC stereo / mono / stereo int16: SURVEY s8d -- never a
+smaller denominator for the streams form).
 One JSON line per (workload, T).
-usage: python tools/streams_rate.py [--frames 262144] [--reps 5] [--T 1,2,4,8] [--workloads hev2,hev2_s16,hev1]"""
+usage: python tools/streams_rate.py [--frames 262144] [--reps 5] [--warmup 1] [--T 1,2,4,8]
+                                    [--workloads hev2,hev2_s16,hev1,lc_stereo,lc_mono,lc_stereo_s16]"""
 import argparse
 import importlib
 import json
@@ -21,6 +23,12 @@ pkg = G.load_package()
 synth = importlib.import_module("ffmpeg_heaac_amd.synth")
 
 WORKLOADS = {"hev2": ("CFG_HEV2", "PCM_F32"), "hev2_s16": ("CFG_HEV2", "PCM_S16"), "hev1": ("CFG_HEV1", "PCM_F32")}
+# AAC-LC: channels, PCM format (the batch form's algorithmic bytes per frame: coefficients, overlap in and out, PCM, ICS)
+LC_WORKLOADS = {"lc_stereo": (2, "PCM_F32"), "lc_mono": (1, "PCM_F32"), "lc_stereo_s16": (2, "PCM_S16")}
+
+
+def lc_bytes_per_frame(channels, fmt):
+    return channels * (4096 + 2048 + 2048 + (4096 if fmt == pkg.PCM_F32 else 2048) + 4)
 
 
 def timed(fn):
@@ -37,6 +45,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=262144)
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=1, help="untimed A, B calls before the timed reps")
     ap.add_argument("--T", default="1,2,4,8")
     ap.add_argument("--workloads", default="hev2,hev2_s16,hev1")
     ap.add_argument("--pool", type=int, default=1024, help="distinct streams generated; the rest are copies")
@@ -47,6 +56,9 @@ def main():
     d_hdr = pkg.to_device(hdr)
     Ts = [int(x) for x in a.T.split(",")]
     for wl in a.workloads.split(","):
+        if wl in LC_WORKLOADS:
+            run_lc(a, dev, wl, Ts)
+            continue
         cfg_name, fmt_name = WORKLOADS[wl]
         cfg, fmt = getattr(pkg, cfg_name), getattr(pkg, fmt_name)
         words, nout = pkg.STATE_WORDS[cfg], pkg.OUT_CH[cfg]
@@ -72,7 +84,8 @@ def main():
             run_a = lambda: dev.he_decode_streams(cfg, coeffs, ics, sbr, d_hdr, ps, st_s, T, state_out=st_s2, pcm=pcm,
                                                   pcm_format=fmt)
             run_b = lambda: dev.he_decode(cfg, coeffs, ics, sbr, d_hdr, ps, st_b, state_out=st_b2, pcm=pcm, pcm_format=fmt)
-            run_a(); run_b()                               # warm-up
+            for _ in range(a.warmup):
+                run_a(); run_b()
             ta, tb = [], []
             for _ in range(a.reps):
                 ta.append(timed(run_a))
@@ -89,6 +102,49 @@ def main():
             del coeffs, ics, sbr, ps, st_s, st_s2, st_b, st_b2
             torch.cuda.empty_cache()
     dev.close()
+
+
+def run_lc(a, dev, wl, Ts):
+    n = a.frames
+    channels, fmt_name = LC_WORKLOADS[wl]
+    fmt = getattr(pkg, fmt_name)
+    bpf = lc_bytes_per_frame(channels, fmt)
+    assert channels != 2 or bpf == pkg.ALGO_BYTES[pkg.CFG_LC_STEREO] - (2048 * 2 if fmt != pkg.PCM_F32 else 0)
+    rng = np.random.default_rng(5)
+    steps = list(synth.lc_stream(rng, a.pool, max(Ts), channels))
+    pcm = (torch.empty((n, channels, 1024), device="cuda") if fmt == pkg.PCM_F32
+           else torch.empty((n, 1024, channels), dtype=torch.int16, device="cuda"))
+    for T in Ts:
+        S = n // T
+        assert S * T == n and S % a.pool == 0
+        # [pool][T] frames, stream s = pool stream s % pool; frame (s, t) at s * T + t
+        def stack(k):
+            x = np.stack([st[k] for st in steps[:T]], axis=1)
+            x = np.tile(x, (S // a.pool,) + (1,) * (x.ndim - 1))
+            return np.ascontiguousarray(x.reshape((n,) + x.shape[2:]))
+        coeffs, ics = torch.from_numpy(stack(0)).cuda(), pkg.to_device(stack(1))
+        st_s = torch.zeros((S, channels * 512), device="cuda")
+        st_s2 = torch.empty_like(st_s)
+        st_b = torch.zeros((n, channels * 512), device="cuda")
+        st_b2 = torch.empty_like(st_b)
+        run_a = lambda: dev.lc_decode_streams(channels, coeffs, ics, st_s, T, state_out=st_s2, pcm=pcm, pcm_format=fmt)
+        run_b = lambda: dev.lc_decode(channels, coeffs, ics, st_b, state_out=st_b2, pcm=pcm, pcm_format=fmt)
+        for _ in range(a.warmup):
+            run_a(); run_b()
+        ta, tb = [], []
+        for _ in range(a.reps):
+            ta.append(timed(run_a))
+            tb.append(timed(run_b))
+        ms_a, ms_b = min(ta), min(tb)
+        rec = dict(workload=wl, T=T, streams=S, frames=n, streams_ms=round(ms_a, 4), batch_ms=round(ms_b, 4),
+                   speedup=round(ms_b / ms_a, 4), streams_frames_per_s=round(n / (ms_a * 1e-3)),
+                   batch_frames_per_s=round(n / (ms_b * 1e-3)), bytes_per_frame=bpf,
+                   roofline={"frac": round(bpf * n / (ms_a * 1e-3) / 8e12, 4),
+                             "batch_frac": round(bpf * n / (ms_b * 1e-3) / 8e12, 4)},
+                   samples_ms={"streams": [round(x, 4) for x in ta], "batch": [round(x, 4) for x in tb]})
+        print(json.dumps(rec), flush=True)
+        del coeffs, ics, st_s, st_s2, st_b, st_b2
+        torch.cuda.empty_cache()
 
 
 if __name__ == "__main__":

@@ -115,7 +115,7 @@ EXPORTED = [
     "heaac_strerror", "heaac_imdct_half_batch", "heaac_lc_decode_batch", "heaac_lc_decode_streams",
     "heaac_he_decode_batch", "heaac_he_decode_batch_ex", "heaac_he_decode_streams", "heaac_qmf_analysis_batch", "heaac_qmf_synthesis_batch",
     "heaac_qmf_synthesis_ds_batch",
-    "heaac_sbr_make_header", "heaac_build_info", "heaac_spectral_tools_batch",
+    "heaac_sbr_make_header", "heaac_build_info", "heaac_spectral_tools_batch", "heaac_spectral_tools_streams",
     "heaac_validate_frame", "heaac_he_check_batch", "heaac_couple_after_imdct_batch",
     # heaac_fft.h
     "ff_fft_init", "ff_fft_end", "ff_fft_permute", "ff_fft_calc",
@@ -391,6 +391,42 @@ class Device:
                                                 _ptr(pred) if pred is not None else None,
                                                 _ptr(pred) if pred is not None else None,
                                                 C.c_size_t(n), _stream()), "heaac_spectral_tools_batch")
+        return coeffs
+
+    def spectral_tools_streams(self, channels, coeffs, tools, frames_per_stream, rng=None, pred=None, rng_out=None,
+                               pred_out=None):
+        """heaac_spectral_tools_streams: S streams x T = frames_per_stream consecutive frames each, in place on coeffs.
+        coeffs / tools are laid out as for spectral_tools with n = S * T (frame t of stream s at s * T + t).  rng: int32
+        [S] generator states, pred: float32 [S][channels][672][6] predictor states -- one record per stream, before
+        frame 0; the states after frame T - 1 go to rng_out / pred_out, or in place when those are None.  Returns
+        coeffs."""
+        import torch
+        T = int(frames_per_stream)
+        assert T > 0, "frames_per_stream"
+        assert coeffs.dtype == torch.float32 and coeffs.numel() % (channels * 1024) == 0, "coeffs"
+        n = coeffs.numel() // (channels * 1024)
+        # a wrong-length tensor would be a silent device out-of-bounds access: check them all here
+        assert n % T == 0, "coeffs: %d frames are not a multiple of frames_per_stream = %d" % (n, T)
+        S = n // T
+        assert tools.dtype == torch.uint8 and tools.numel() == n * TOOLS_FRAME_DT.itemsize, "tools"
+        pred_words = S * channels * MAX_PREDICTORS * 6
+        assert rng is None or (rng.dtype == torch.int32 and rng.numel() == S), "rng"
+        assert pred is None or (pred.dtype == torch.float32 and pred.numel() == pred_words), "pred"
+        assert rng_out is None or (rng is not None and rng_out.dtype == torch.int32 and rng_out.numel() == S), \
+            "rng_out"
+        assert pred_out is None or (pred is not None and pred_out.dtype == torch.float32 and
+                                    pred_out.numel() == pred_words), "pred_out"
+        if rng is not None and rng_out is None:
+            rng_out = rng
+        if pred is not None and pred_out is None:
+            pred_out = pred
+        _check(lib().heaac_spectral_tools_streams(self._h, channels, _ptr(coeffs), _ptr(tools),
+                                                  _ptr(rng) if rng is not None else None,
+                                                  _ptr(rng_out) if rng is not None else None,
+                                                  _ptr(pred) if pred is not None else None,
+                                                  _ptr(pred_out) if pred is not None else None,
+                                                  C.c_size_t(S), C.c_size_t(T), _stream()),
+               "heaac_spectral_tools_streams")
         return coeffs
 
     def spectral_tools_ex(self, channels, stages, coeffs, tools, rng=None, pred=None, cce=None, cce_coeffs=None):

@@ -284,6 +284,39 @@ extern "C" int heaac_spectral_tools_batch_ex(HeaacDevice *dev, int channels, int
                                        stages, d_cce, d_cce_coeffs, n_cce, n, (hipStream_t)stream);
 }
 
+extern "C" int heaac_spectral_tools_streams(HeaacDevice *dev, int channels, float *d_coeffs,
+                                            const HeaacToolsFrame *d_tools,
+                                            const int32_t *d_rng_in, int32_t *d_rng_out,
+                                            const HeaacPredictorState *d_pred_in, HeaacPredictorState *d_pred_out,
+                                            size_t n_streams, size_t frames_per_stream, void *stream)
+{
+    if (!dev || channels < 1 || channels > 2 || frames_per_stream == 0 || (d_rng_in && !d_rng_out) ||
+        (d_pred_in && !d_pred_out))
+        return HEAAC_ERR_ARG;
+    if (n_streams == 0)
+        return HEAAC_OK;
+    if (!d_coeffs || !d_tools)
+        return HEAAC_ERR_ARG;
+    // S * T frames of coefficients and records must be addressable, and k_tns's grid (3 filters per channel, 256
+    // lanes per block) must stay within its 2^31 - 1 blocks
+    if (n_streams > SIZE_MAX / frames_per_stream)
+        return HEAAC_ERR_ARG;
+    const size_t n = n_streams * frames_per_stream;
+    if (n > SIZE_MAX / ((size_t)channels * 1024 * sizeof(float)) || n > SIZE_MAX / sizeof(HeaacToolsFrame) ||
+        n > 0x7fffffffull * 256 / (3 * (size_t)channels))
+        return HEAAC_ERR_ARG;
+    // one frame per stream: the per-frame arrays and the state are exactly the batch call's
+    if (frames_per_stream == 1)
+        return heaac_launch_spectral_tools(channels, d_coeffs, d_tools, d_rng_in, d_rng_out, d_pred_in, d_pred_out,
+                                           HEAAC_TOOLS_ALL, NULL, NULL, 0, n_streams, (hipStream_t)stream);
+    // no state: every frame stands alone, one batch call over the S * T frames
+    if (!d_rng_in && !d_pred_in)
+        return heaac_launch_spectral_tools(channels, d_coeffs, d_tools, NULL, NULL, NULL, NULL, HEAAC_TOOLS_ALL,
+                                           NULL, NULL, 0, n, (hipStream_t)stream);
+    return heaac_launch_spectral_tools_streams(channels, d_coeffs, d_tools, d_rng_in, d_rng_out, d_pred_in,
+                                               d_pred_out, n_streams, frames_per_stream, (hipStream_t)stream);
+}
+
 extern "C" int heaac_he_decode_batch_ex(HeaacDevice *dev, int cfg, int flags,
                                         const float *d_coeffs, const HeaacIcs *d_ics,
                                         const HeaacSbrFrame *d_sbr,

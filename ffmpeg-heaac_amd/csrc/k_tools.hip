@@ -156,11 +156,31 @@ __device__ __forceinline__ float flt16_trunc(float pf)
     return __uint_as_float(__float_as_uint(pf) & 0xFFFF0000u);
 }
 
+// Where tools_prediction reads a channel's 672 predictor states and writes them back.  Lane l owns predictors
+// k = l + 64 j, j = 0 .. 10 (the last row: lanes 0 .. 31).
+//   PredHbm   in / out in global memory (may alias): k_spectral_tools, state in and out on every frame.
+//   PredRegs  row j in the lane's ps[j], 66 VGPRs per channel: the state carried in registers across a stream's
+//             consecutive frames (k_spectral_tools_streams).
+#define PRED_ROWS ((HEAAC_MAX_PREDICTORS + WAVE - 1) / WAVE)
+struct PredHbm {
+    const HeaacPredictorState *in;
+    HeaacPredictorState *out;
+    static constexpr bool kRegs = false;
+    __device__ __forceinline__ HeaacPredictorState load(int, int k) const { return in[k]; }
+    __device__ __forceinline__ void store(int, int k, const HeaacPredictorState &ps) const { out[k] = ps; }
+};
+struct PredRegs {
+    HeaacPredictorState (&ps)[PRED_ROWS];
+    static constexpr bool kRegs = true;
+    __device__ __forceinline__ HeaacPredictorState load(int j, int) const { return ps[j]; }
+    __device__ __forceinline__ void store(int j, int, const HeaacPredictorState &v) const { ps[j] = v; }
+};
+
 // apply_prediction (aacdec.c:1302-1322) for one channel: the 672 predictors are independent, one
 // per lane and pass.  predict() (:1271-1297) is restated with its mixed precision: the two
 // variance updates add a float product to 0.5 * (double) -- the literal is a double there.
-__device__ __forceinline__ void tools_prediction(ToolsWave &w, int ch, const HeaacPredictorState *g_in,
-                                                 HeaacPredictorState *g_out, int lane)
+template <class Pred>
+__device__ __forceinline__ void tools_prediction(ToolsWave &w, int ch, const Pred &st, int lane)
 {
     const HeaacToolsIcs &ics = w.t.ch[ch].ics;
     const HeaacPrediction &pr = w.t.ch[ch].pred;
@@ -169,8 +189,8 @@ __device__ __forceinline__ void tools_prediction(ToolsWave &w, int ch, const Hea
     const int group = pr.predictor_reset_group;
     const float sf_scale = HEAAC_SF_SCALE;
     const float a = 0.953125f, alpha = 0.90625f;
-    for (int k = lane; k < HEAAC_MAX_PREDICTORS; k += WAVE) {
-        HeaacPredictorState ps = g_in[k];
+    auto one = [&](int j, int k) {
+        HeaacPredictorState ps = st.load(j, k);
         if (k < limit) {
             // scalefactor band of line k (bands are at most 96 wide: walk from a coarse guess)
             int sfb = 0;
@@ -197,7 +217,14 @@ __device__ __forceinline__ void tools_prediction(ToolsWave &w, int ch, const Hea
             ps.cor0 = ps.cor1 = ps.r0 = ps.r1 = 0.0f;
             ps.var0 = ps.var1 = 1.0f;
         }
-        g_out[k] = ps;
+        st.store(j, k, ps);
+    };
+    if constexpr (Pred::kRegs) {
+#pragma unroll
+        for (int j = 0; j < PRED_ROWS; j++)
+            if (lane + WAVE * j < HEAAC_MAX_PREDICTORS) one(j, lane + WAVE * j);
+    } else {
+        for (int k = lane; k < HEAAC_MAX_PREDICTORS; k += WAVE) one(0, k);
     }
     wave_sync();
 }
@@ -458,15 +485,15 @@ void k_spectral_tools(float *g_coeffs, const HeaacToolsFrame *__restrict__ g_too
         if (pre && g_pred_in && !common) {      // decode_ics, aacdec.c:1381-1382
 #pragma unroll
             for (int c = 0; c < CH; c++)
-                tools_prediction(w, c, g_pred_in + (f * CH + c) * HEAAC_MAX_PREDICTORS,
-                                 g_pred_out + (f * CH + c) * HEAAC_MAX_PREDICTORS, lane);
+                tools_prediction(w, c, PredHbm{ g_pred_in + (f * CH + c) * HEAAC_MAX_PREDICTORS,
+                                                g_pred_out + (f * CH + c) * HEAAC_MAX_PREDICTORS }, lane);
         }
         if (CH == 2 && pre) {
             if (w.t.common_window && w.t.ms_present) { tools_mid_side(w, lane); wave_sync(); }
             if (g_pred_in && common) {          // decode_cpe, aacdec.c:1486-1489
                 for (int c = 0; c < 2; c++)
-                    tools_prediction(w, c, g_pred_in + (f * 2 + c) * HEAAC_MAX_PREDICTORS,
-                                     g_pred_out + (f * 2 + c) * HEAAC_MAX_PREDICTORS, lane);
+                    tools_prediction(w, c, PredHbm{ g_pred_in + (f * 2 + c) * HEAAC_MAX_PREDICTORS,
+                                                    g_pred_out + (f * 2 + c) * HEAAC_MAX_PREDICTORS }, lane);
             }
             tools_intensity(w, lane);
             wave_sync();
@@ -492,6 +519,122 @@ void k_spectral_tools(float *g_coeffs, const HeaacToolsFrame *__restrict__ g_too
             for (int i = 0; i < 4 * CH; i++) c4[lane + 64 * i] = d4[lane + 64 * i];
         }
         wave_sync();
+    }
+}
+
+// ---------------------------------------------------------------------------
+// k_spectral_tools_streams: the PRE half of k_spectral_tools (noise substitution, AAC-Main prediction, M/S, intensity)
+// for S streams x T consecutive frames, frame t of stream s at s * T + t of the per-frame arrays, one state record per
+// stream.  A wave owns a stream and walks its T frames in order, each through the wave's ToolsWave slice as in the
+// batch kernel.  The generator state (wave-uniform: tools_pns returns it so) and, with PRED, each channel's 672
+// predictors (PredRegs, 66 VGPRs per channel) stay in registers from frame 0 to frame T - 1: read once, written once.
+// TNS is stateless and runs behind it as k_tns over the S * T frames.
+// ---------------------------------------------------------------------------
+// Waves per workgroup, per instantiation.  Without prediction the carry is one register and the batch kernel's 10 waves
+// hold; mono with prediction (66 carry VGPRs) needs 147 and keeps them too.  Stereo with prediction (132) needs 251: at
+// 10 waves (three per SIMD, 168 VGPRs) it spills and is 2 - 7 % slower than at 8 (two per SIMD), so it runs 8 (A/B in
+// profiles/r07_tools_streams_waves_ab.jsonl, DESIGN s4).  -DTSS_WAVES=<n> builds every instantiation with n waves.
+template <int CH, bool PRED>
+constexpr int tss_waves()
+{
+#ifdef TSS_WAVES
+    return TSS_WAVES;
+#else
+    return CH == 2 && PRED ? 8 : TL_WAVES;
+#endif
+}
+
+// the predictor rows a wave carries: [CH][PRED_ROWS] with PRED, nothing without
+template <int CH, bool PRED> struct PredCarry { HeaacPredictorState ps[CH][PRED_ROWS]; };
+template <int CH> struct PredCarry<CH, false> {};
+
+template <int CH, bool PRED>
+__global__ __launch_bounds__((tss_waves<CH, PRED>() * WAVE))
+void k_spectral_tools_streams(float *g_coeffs, const HeaacToolsFrame *__restrict__ g_tools,
+                              const int *g_rng_in, int *g_rng_out,
+                              const HeaacPredictorState *g_pred_in, HeaacPredictorState *g_pred_out,
+                              unsigned long long S, unsigned long long T)
+{
+    constexpr int NW = tss_waves<CH, PRED>();
+    __shared__ ToolsWave W[NW];
+    __shared__ LcgSkip K;
+    if (threadIdx.x == 0) {
+        unsigned a = 1u, c = 0u;                 // identity, then compose one step at a time
+        for (int j = 0; j < LCG_SKIP; j++) {
+            K.mulA[j] = a; K.addC[j] = c;
+            a = a * 1664525u;
+            c = c * 1664525u + 1013904223u;
+        }
+    }
+    __syncthreads();
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / WAVE), lane = threadIdx.x % WAVE;
+    ToolsWave &w = W[wave];
+    for (unsigned long long s = (unsigned long long)blockIdx.x * NW + wave; s < S;
+         s += (unsigned long long)gridDim.x * NW) {
+        // every read of the stream's state is issued before its frames run; the writes follow the last frame (in and
+        // out may alias)
+        unsigned rs = g_rng_in ? (unsigned)g_rng_in[s] : 0u;
+        PredCarry<CH, PRED> pc;
+        if constexpr (PRED) {
+#pragma unroll
+            for (int c = 0; c < CH; c++)
+#pragma unroll
+                for (int j = 0; j < PRED_ROWS; j++)
+                    if (lane + WAVE * j < HEAAC_MAX_PREDICTORS)
+                        pc.ps[c][j] = g_pred_in[(s * CH + c) * HEAAC_MAX_PREDICTORS + lane + WAVE * j];
+        }
+        for (unsigned long long t = 0; t < T; t++) {
+            const unsigned long long f = s * T + t;
+            float *gc = g_coeffs + f * CH * 1024;
+            {
+                const float4 *c4 = reinterpret_cast<const float4 *>(gc);
+                float4 *d4 = reinterpret_cast<float4 *>(&w.coef[0][0]);
+#pragma unroll
+                for (int i = 0; i < 4 * CH; i++) d4[lane + 64 * i] = c4[lane + 64 * i];
+                const uint32_t *src = reinterpret_cast<const uint32_t *>(&g_tools[f]);
+                uint32_t *d = reinterpret_cast<uint32_t *>(&w.t);
+                for (int i = lane; i < (int)(sizeof(HeaacToolsFrame) / 4); i += WAVE) d[i] = src[i];
+            }
+            wave_sync();
+            if (g_rng_in) {
+#pragma unroll
+                for (int c = 0; c < CH; c++) rs = tools_pns(w, K, c, rs, lane);
+            }
+            const bool common = CH == 2 && w.t.common_window;
+            if constexpr (PRED) {
+                if (!common) {                  // decode_ics, aacdec.c:1381-1382
+#pragma unroll
+                    for (int c = 0; c < CH; c++) tools_prediction(w, c, PredRegs{ pc.ps[c] }, lane);
+                }
+            }
+            if (CH == 2) {
+                if (w.t.common_window && w.t.ms_present) { tools_mid_side(w, lane); wave_sync(); }
+                if constexpr (PRED) {
+                    if (common) {               // decode_cpe, aacdec.c:1486-1489
+#pragma unroll
+                        for (int c = 0; c < CH; c++) tools_prediction(w, c, PredRegs{ pc.ps[c] }, lane);
+                    }
+                }
+                tools_intensity(w, lane);
+            }
+            wave_sync();
+            {
+                float4 *c4 = reinterpret_cast<float4 *>(gc);
+                const float4 *d4 = reinterpret_cast<const float4 *>(&w.coef[0][0]);
+#pragma unroll
+                for (int i = 0; i < 4 * CH; i++) c4[lane + 64 * i] = d4[lane + 64 * i];
+            }
+            wave_sync();
+        }
+        if (g_rng_in && lane == 0) g_rng_out[s] = (int)rs;
+        if constexpr (PRED) {
+#pragma unroll
+            for (int c = 0; c < CH; c++)
+#pragma unroll
+                for (int j = 0; j < PRED_ROWS; j++)
+                    if (lane + WAVE * j < HEAAC_MAX_PREDICTORS)
+                        g_pred_out[(s * CH + c) * HEAAC_MAX_PREDICTORS + lane + WAVE * j] = pc.ps[c][j];
+        }
     }
 }
 
@@ -525,5 +668,33 @@ extern "C" int heaac_launch_spectral_tools(int channels, float *d_coeffs, const 
         if (channels == 2) hipLaunchKernelGGL(k_tns<2>, dim3((unsigned)blocks), dim3(256), 0, s, d_coeffs, d_tools, (unsigned long long)n);
         else               hipLaunchKernelGGL(k_tns<1>, dim3((unsigned)blocks), dim3(256), 0, s, d_coeffs, d_tools, (unsigned long long)n);
     }
+    return hipGetLastError() == hipSuccess ? HEAAC_OK : HEAAC_ERR_HIP;
+}
+
+// S streams x T frames (T > 1, some state given: the caller routes the other cases to heaac_launch_spectral_tools).
+// The chain kernel runs the PRE half one wave per stream; TNS follows as k_tns over the S * T frames.
+extern "C" int heaac_launch_spectral_tools_streams(int channels, float *d_coeffs, const HeaacToolsFrame *d_tools,
+                                                   const int *d_rng_in, int *d_rng_out,
+                                                   const HeaacPredictorState *d_pred_in, HeaacPredictorState *d_pred_out,
+                                                   size_t n_streams, size_t frames_per_stream, hipStream_t s)
+{
+    if (n_streams == 0) return HEAAC_OK;
+    if (channels != 1 && channels != 2) return HEAAC_ERR_ARG;
+    const unsigned long long S = n_streams, T = frames_per_stream, n = S * T;
+    const unsigned long long units = n * channels * TNS_FILTERS, blocks = (units + 255) / 256;
+    if (blocks > 0x7fffffffull) return HEAAC_ERR_ARG;
+#define LAUNCH(CH, PRED)                                                                                                 \
+    do {                                                                                                             \
+        unsigned long long g = (S + tss_waves<CH, PRED>() - 1) / tss_waves<CH, PRED>();                            \
+        if (g > 256) g = 256;                                                                                        \
+        hipLaunchKernelGGL((k_spectral_tools_streams<CH, PRED>), dim3((unsigned)g), dim3(tss_waves<CH, PRED>() * WAVE), \
+                           0, s, d_coeffs, d_tools, d_rng_in, d_rng_out, d_pred_in, d_pred_out, S, T);             \
+    } while (0)
+    const bool pred = d_pred_in != nullptr;
+    if (channels == 2) { if (pred) LAUNCH(2, true); else LAUNCH(2, false); }
+    else               { if (pred) LAUNCH(1, true); else LAUNCH(1, false); }
+#undef LAUNCH
+    if (channels == 2) hipLaunchKernelGGL(k_tns<2>, dim3((unsigned)blocks), dim3(256), 0, s, d_coeffs, d_tools, n);
+    else               hipLaunchKernelGGL(k_tns<1>, dim3((unsigned)blocks), dim3(256), 0, s, d_coeffs, d_tools, n);
     return hipGetLastError() == hipSuccess ? HEAAC_OK : HEAAC_ERR_HIP;
 }

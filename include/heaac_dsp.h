@@ -536,6 +536,28 @@ int heaac_spectral_tools_batch(HeaacDevice *dev, int channels, float *d_coeffs,
                                const HeaacPredictorState *d_pred_in, HeaacPredictorState *d_pred_out,
                                size_t n, void *stream);
 
+/* Several consecutive frames of each stream in one call ("streams form"): S streams x T frames each.
+ *   The per-frame arrays have the layout of heaac_spectral_tools_batch with n = S * T, frame t of stream s at index
+ *   s * T + t:  d_coeffs [S][T][channels][1024] (in place), d_tools [S][T].  The state is per stream: d_rng_in [S]
+ *   holds each stream's generator before its frame 0, d_rng_out [S] the generator after its frame T - 1;
+ *   d_pred_in / d_pred_out [S][channels][672] the same for the AAC-Main predictors (in and out may alias).
+ *   A NULL d_rng_in turns noise substitution off and a NULL d_pred_in prediction, as in the batch call.
+ * Coefficients, generator and predictors are bit-identical to T chained heaac_spectral_tools_batch calls, each over
+ * the S frames of one position, with the state chained; for channels 1 and 2 and every combination of the two.
+ * The device runs the streams in parallel and a stream's frames one after another: S sets the parallelism, not
+ * S * T.  The state stays on chip between a stream's frames (the 672 predictors of a channel are 16 KiB that the
+ * batch call reads and writes on every frame).  Without state the frames are independent and the call is one batch
+ * call over the S * T frames.  Same contract as the batch call: no allocation, no synchronisation, capturable into a
+ * hipGraph, and no use of the device workspace (calls on other streams stay legal).  T has no upper bound.
+ * Returns HEAAC_ERR_ARG, before any launch, for channels other than 1 or 2, frames_per_stream == 0, a NULL d_coeffs
+ * or d_tools (n_streams > 0), an input state without its output, or S * T frames whose coefficients, records or TNS
+ * grid cannot be addressed; n_streams == 0 is HEAAC_OK. */
+int heaac_spectral_tools_streams(HeaacDevice *dev, int channels, float *d_coeffs,
+                                 const HeaacToolsFrame *d_tools,
+                                 const int32_t *d_rng_in, int32_t *d_rng_out,
+                                 const HeaacPredictorState *d_pred_in, HeaacPredictorState *d_pred_out,
+                                 size_t n_streams, size_t frames_per_stream, void *stream);
+
 /* ------------------------------------------------------------------------
  * Dependent channel coupling: a coupling_channel_element whose spectrum is added into its target
  * channels BEFORE the IMDCT -- apply_dependent_coupling (aacdec.c:1813-1843) under apply_channel_coupling

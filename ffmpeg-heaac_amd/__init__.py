@@ -304,11 +304,16 @@ class Device:
         except Exception:
             pass
 
+    def x_bands(self, n):
+        """include/heaac_debug.h: the X bands stored per (frame, channel) by the last HE decode call, uint8 [n][2]."""
+        buf = np.zeros(2 * n, np.uint8)
+        _check(lib().heaac_debug_xbands(self._h, buf.ctypes.data_as(C.c_void_p), C.c_size_t(n)), "heaac_debug_xbands")
+        return buf.reshape(n, 2)
+
     def x_bands_shares(self, n):
         """include/heaac_debug.h: the share of (frame, channel) X records of the last HE decode call that were
         stored with 32 / 48 / 64 bands, as {"32": .., "48": .., "64": ..}."""
-        buf = np.zeros(2 * n, np.uint8)
-        _check(lib().heaac_debug_xbands(self._h, buf.ctypes.data_as(C.c_void_p), C.c_size_t(n)), "heaac_debug_xbands")
+        buf = self.x_bands(n)
         return {str(b): round(float((buf == b).mean()), 4) for b in (32, 48, 64)}
 
     # -- transforms --
@@ -625,7 +630,7 @@ class AdtsHeader(C.Structure):
 COUPLING_DT = np.dtype([("gain", "<f4", (2,)), ("on", "u1", (2,)), ("pad", "u1", (2,))])
 AAC_STREAM_DT = np.dtype([("window_sequence", "u1", (2,)), ("use_kb_window", "u1", (2,)),
                           ("cce_window_sequence", "u1", (16,)), ("cce_use_kb_window", "u1", (16,)),
-                          ("mapped_tag", "u1"), ("pad", "u1", (3,))])
+                          ("mapped_tag", "u1"), ("oc", "u1"), ("pad", "u1", (2,))])
 AAC_INFO_DT = np.dtype([("channels", "<i4"), ("bits_consumed", "<i4"), ("sbr_payload_bit", "<i4"),
                         ("sbr_payload_bytes", "<i4"), ("sbr_crc", "<i4"), ("elem_id", "<i4"), ("n_cce", "<i4"),
                         ("sbr_misplaced", "<i4"), ("refused", "<i4")])

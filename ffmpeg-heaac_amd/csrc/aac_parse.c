@@ -791,10 +791,21 @@ static int output_element_allowed(const HeaacAacConfig *cfg, HeaacAacStream *st,
     if (one_element) {
         if ((type == TYPE_CPE) != (cfg->chan_config == 2)) return REF_FAIL(pg, HEAAC_PARSE_ERR_DATA);
         if (st->mapped_tag && st->mapped_tag != tag + 1) return REF_FAIL(pg, HEAAC_PARSE_ERR_DATA);
-        st->mapped_tag = (uint8_t)(tag + 1);           /* (kept whatever becomes of the unit, as tag_che_map is) */
+        st->mapped_tag = (uint8_t)(tag + 1);           /* (kept whatever becomes of the unit, as tag_che_map is; only an
+                                                          output_configure clears it, see frame_walk) */
     }
     return HEAAC_PARSE_OK;
 }
+
+/* HeaacAacStream.oc: what the reference's output configuration has done to a one-element stream.  Until a unit has
+ * decoded (OC_LOCKED, aac_decode_frame :2100-2101) every ADTS header runs output_configure again (:1942-1955), and
+ * so does the implicit Parametric Stereo of a mono stream at its first SBR payload (:1666-1673): each run clears
+ * tag_che_map (:243-245), so the stream's element may come under another tag.  The raw / AudioSpecificConfig path
+ * configures once, at init (:430), and never again. */
+#define OC_LOCKED 1u                /* output_configured == OC_LOCKED */
+#define OC_NONE   2u                /* an ADTS header without a channel configuration left OC_NONE: the unit does not lock */
+#define OC_PS     4u                /* m4ac.ps is 1: the implicit-PS re-configure has run (an ADTS header sets it back to -1) */
+#define OC_TWO    8u                /* the last output_configure counted two channels for the SCE (it ran with ps == 1) */
 
 /* The walk over one access unit of a one-element stream; `b`, `w`, `pg`, `n_cce_seen` are the caller's so that it
  * can tell, after a refusal, how far the walk had got. */
@@ -808,6 +819,16 @@ static int frame_walk(const HeaacAacConfig *cfg, HeaacAacStream *st, const uint8
         HeaacAdtsHeader h;
         const int hs = heaac_adts_parse_header(&h, au, size);
         if (hs < 0) return HEAAC_PARSE_ERR_DATA;
+        if (!(st->oc & OC_LOCKED)) {
+            /* parse_adts_frame_header before the lock: output_configure with the channel configuration (the tag map
+             * cleared; the SCE counted twice where ps is 1 just now), or OC_NONE without one; then ps = -1 */
+            if (h.chan_config) {
+                st->mapped_tag = 0;
+                st->oc = (st->oc & OC_PS) ? OC_TWO : 0;
+            } else {
+                st->oc = (uint8_t)((st->oc & OC_TWO) | OC_NONE);
+            }
+        }
         /* parse_adts_frame_header (aacdec.c:1935-1971) takes rate and object type from every header and refuses
          * more than one raw data block per frame.  `cfg` is the caller's (read-only, shared by a batch): a header
          * that contradicts it would be dequantised against the wrong band tables, so it is refused instead. */
@@ -904,6 +925,12 @@ static int frame_walk(const HeaacAacConfig *cfg, HeaacAacStream *st, const uint8
                 fi.sbr_payload_bytes = bytes;
                 fi.sbr_crc = crc;
                 fi.sbr_misplaced = prev_type != TYPE_SCE && prev_type != TYPE_CPE;
+                /* decode_extension_payload (:1666-1673): implicit PS in a one-channel stream before the lock sets ps = 1
+                 * and runs output_configure again -- the tag the SCE was just mapped to is forgotten */
+                if (cfg->sbr != 0 && cfg->ps == -1 && cfg->chan_config == 1 && !(st->oc & (OC_LOCKED | OC_PS | OC_TWO))) {
+                    st->oc |= OC_PS | OC_TWO;
+                    st->mapped_tag = 0;
+                }
             }
             break;
         }
@@ -1046,6 +1073,7 @@ int heaac_aac_parse_frame_ex(const HeaacAacConfig *cfg, HeaacAacStream *st,
     memset(tools, 0, sizeof(*tools));
     const int r = frame_walk(cfg, st, au, size, coeff_channels, coeffs, ics, tools, cce, info, &b, w, &pg, &n_cce);
     if (r < 0) unit_refused(cfg, st, &b, w, &pg, n_cce, coeff_channels, coeffs, tools, info);
+    else if (!(st->oc & OC_NONE)) st->oc |= OC_LOCKED;     /* the unit decodes: output_configured = OC_LOCKED */
     return r;
 }
 

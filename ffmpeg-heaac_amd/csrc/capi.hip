@@ -554,7 +554,9 @@ extern "C" int heaac_debug_workspace(HeaacDevice *dev, float **d_W, float **d_X,
 
 extern "C" int heaac_debug_xbands(HeaacDevice *dev, unsigned char *host_out, size_t n_frames)
 {
-    if (!dev || !host_out || n_frames > dev->chunk) return HEAAC_ERR_ARG;
+    // chunk c of a call writes its records at 2 (c mod sets) chunk: for the first `sets` chunks that is 2 f0, so the
+    // records of up to sets x chunk frames lie in frame order
+    if (!dev || !host_out || n_frames > (size_t)(dev->sets > 0 ? dev->sets : 1) * dev->chunk) return HEAAC_ERR_ARG;
     if (hipDeviceSynchronize() != hipSuccess) return HEAAC_ERR_HIP;
     return hipMemcpy(host_out, dev->d_aux + HE_ZERO_BYTES, 2 * n_frames, hipMemcpyDeviceToHost) == hipSuccess
                ? HEAAC_OK : HEAAC_ERR_HIP;

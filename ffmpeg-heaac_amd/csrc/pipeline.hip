@@ -15,7 +15,6 @@
 #include <stdlib.h>
 #include <string.h>
 #include <time.h>
-#include <alloca.h>
 #include <unistd.h>
 #include "heaac_pipeline.h"
 #include "codec_layout.h"        // heaac_sbr_output_mode
@@ -67,6 +66,7 @@ struct HeaacPipeline {
     HeaacSbrHeader *d_hdr; size_t hdr_uploaded;
     HeaacSbrHeaderTable *tab;
     HeaacAacStream *ast; HeaacSbrStream *sst;
+    HeaacSbrStream *sst_tmp;      // HE: [threads] scratch SBR reader states, one per parse slice
     unsigned long submitted, collected;
     float last_ms[4];
     // pool
@@ -85,6 +85,9 @@ static void parse_slice(HeaacPipeline *p, int w)
 {
     const size_t lo = p->n * (size_t)w / (size_t)p->threads, hi = p->n * (size_t)(w + 1) / (size_t)p->threads;
     Set *s = p->job_set;
+    // the slice's scratch copy of one stream's SBR reader state (a copy on the stack inside the loop would only be
+    // released at return: one reader per failed stream, and thousands of them overflow a thread's stack)
+    void *tmp = p->sst_tmp ? (char *)p->sst_tmp + (size_t)w * heaac_sbr_stream_bytes() : NULL;
     for (size_t i = lo; i < hi; i++) {
         HeaacAacFrameInfo fi;
         memset(&fi, 0, sizeof(fi));
@@ -117,7 +120,6 @@ static void parse_slice(HeaacPipeline *p, int w)
             }
             if (p->he) {
                 // the record of "no payload" from a COPY of the stream's SBR state (the call moves kx / m along)
-                void *tmp = alloca(heaac_sbr_stream_bytes());
                 memcpy(tmp, sst_i, heaac_sbr_stream_bytes());
                 heaac_sbr_no_payload((HeaacSbrStream *)tmp, p->ncore, &s->h_sbr[i], s->h_ps ? &s->h_ps[i] : NULL);
             }
@@ -205,7 +207,7 @@ extern "C" void heaac_pipeline_destroy(HeaacPipeline *p)
     if (p->run) (void)hipStreamDestroy(p->run);
     if (p->out) (void)hipStreamDestroy(p->out);
     heaac_sbr_table_destroy(p->tab);
-    free(p->ast); free(p->sst);
+    free(p->ast); free(p->sst); free(p->sst_tmp);
     heaac_device_destroy(p->dev);
     free(p);
 }
@@ -308,7 +310,7 @@ extern "C" int heaac_pipeline_create(HeaacPipeline **out, const HeaacAacConfig *
         pthread_cond_init(&p->cv_go, NULL);
         pthread_cond_init(&p->cv_done, NULL);
         p->tid = (pthread_t *)calloc(threads, sizeof(pthread_t));
-        ok = p->tid != NULL;
+        ok = p->tid != NULL && (!p->he || (p->sst_tmp = (HeaacSbrStream *)malloc(threads * heaac_sbr_stream_bytes())) != NULL);
         for (int t = 1; t < threads && ok; t++) {          // slice 0 is parsed by the submitting thread
             WorkerArg *a = (WorkerArg *)malloc(sizeof(*a));
             if (!a) { ok = false; break; }

@@ -9,11 +9,15 @@
 //     share that order (encoders emit one order; the first good unit sets it).  A stream that deviates, leaves an
 //     element out or fails to parse gets silence for the tick and keeps its decoder state (as heaac_pipeline does);
 //   * SBR per element (explicit signalling: m4ac.sbr = 1), "pure upsampling" where an element has no payload;
-//   * layouts whose program config element names coupling channel elements are not taken here (one
-//     heaac_codec_decode context per such stream): HEAAC_ERR_ARG at create.
+//   * coupling channel elements that a program config element names (up to HEAAC_MAX_CCE): one more batched
+//     individual channel stream per slot (LpCoupled), their places in the unit the same for all streams of a tick.
+// A tick's parse has two phases on the pool: phase 0 parses every unit into the set's records, submit() then drops
+// the units that deviate from the tick (element order, coupling places), and phase 1 moves the host state of the
+// streams that stand (window histories, SBR readers, coupling elements seen): a dropped stream's host state stays
+// where its parked device rows stay.
 // Two buffer sets rotate: the host parses tick t + 1 while tick t is on the link and on the GPU.
 #include <hip/hip_runtime.h>
-#include <alloca.h>
+#include <assert.h>
 #include <pthread.h>
 #include <stdlib.h>
 #include <string.h>
@@ -87,6 +91,13 @@ struct HeaacLayoutPipeline {
     HeaacSbrHeaderTable *tab;
     HeaacAacStream *ast;            // [n][ne]
     HeaacAacLayout *lay;            // [n]: every stream's own tag map
+    // A good unit's effect on the stream's host state waits until submit() has checked it against the tick (element
+    // order, coupling places): the parse (phase 0) leaves the new window histories and where the SBR payloads stand
+    // here, and phase 1 commits them and reads the payloads -- for the streams still standing only.
+    HeaacAacStream *ast_new;        // [n][ne]
+    HeaacAacElementInfo *te_all;    // [n][ne]
+    HeaacAacElementInfo *ce_all;    // [n][K]
+    HeaacSbrStream *sst_tmp;        // HE: [threads] scratch SBR reader states, one per slice (slice 0's also serves submit())
     int have_order; unsigned char order[HEAAC_MAX_ELEMENTS];     // order[seq] = element at that bitstream position
     LpCoupled *cpl;                 // layouts whose program config element names coupling elements (AAC-LC / Main)
     // parked state of the streams whose unit failed
@@ -99,7 +110,7 @@ struct HeaacLayoutPipeline {
     pthread_cond_t cv_go, cv_done;
     unsigned long generation;
     int pending, quit;
-    const uint8_t *const *job_au; const int *job_size; int *job_status; LpSet *job_set;
+    const uint8_t *const *job_au; const int *job_size; int *job_status; LpSet *job_set; int job_phase;
 };
 
 struct LpWorkerArg { HeaacLayoutPipeline *p; int w; };
@@ -109,9 +120,10 @@ static inline HeaacSbrStream *sst_at(HeaacSbrStream *base, size_t i)
     return (HeaacSbrStream *)((char *)base + i * heaac_sbr_stream_bytes());
 }
 
-// neutral records of one stream: silence, no tools, no SBR payload (from a COPY of the SBR reader state).
-// keep_tools: the tools records and spectra are already what a refused unit leaves for the spectral tools.
-static void neutral(HeaacLayoutPipeline *p, LpSet *s, size_t i, bool keep_tools = false)
+// neutral records of one stream: silence, no tools, no SBR payload (from a COPY of the SBR reader state, made in the
+// caller's scratch `tmp`).  keep_tools: the tools records and spectra are already what a refused unit leaves for the
+// spectral tools.
+static void neutral(HeaacLayoutPipeline *p, LpSet *s, size_t i, HeaacSbrStream *tmp, bool keep_tools = false)
 {
     if (p->cpl) {
         const int K = p->cpl->K;
@@ -121,9 +133,8 @@ static void neutral(HeaacLayoutPipeline *p, LpSet *s, size_t i, bool keep_tools 
             memset(&s->h_cics[k][i], 0, sizeof(HeaacIcs));
             memset(&s->h_ctools[k][i], 0, sizeof(HeaacToolsFrame));
             if (p->he) {
-                void *tmp = alloca(heaac_sbr_stream_bytes());
                 memcpy(tmp, sst_at(p->cpl->sst[k], i), heaac_sbr_stream_bytes());
-                heaac_sbr_no_payload((HeaacSbrStream *)tmp, 1, &s->h_csbr[k][i], NULL);
+                heaac_sbr_no_payload(tmp, 1, &s->h_csbr[k][i], NULL);
             }
         }
         memset(s->cpos + i * K * 3, 0, (size_t)K * 3);
@@ -136,18 +147,26 @@ static void neutral(HeaacLayoutPipeline *p, LpSet *s, size_t i, bool keep_tools 
             memset(&s->h_tools[k][i], 0, sizeof(HeaacToolsFrame));
         }
         if (p->he) {
-            void *tmp = alloca(heaac_sbr_stream_bytes());
             memcpy(tmp, sst_at(p->e[k].sst, i), heaac_sbr_stream_bytes());
-            heaac_sbr_no_payload((HeaacSbrStream *)tmp, ch, &s->h_sbr[k][i], s->h_ps[k] ? &s->h_ps[k][i] : NULL);
+            heaac_sbr_no_payload(tmp, ch, &s->h_sbr[k][i], s->h_ps[k] ? &s->h_ps[k][i] : NULL);
         }
     }
 }
 
+static HeaacSbrStream *slice_tmp(HeaacLayoutPipeline *p, int w)
+{
+    return p->sst_tmp ? sst_at(p->sst_tmp, (size_t)w) : NULL;
+}
+
+// Phase 0 of a tick: parse every unit of the slice into the set's records.  A refused unit gets neutral records here;
+// a good one leaves its window histories and payload places in ast_new / te_all / ce_all, and nothing of the stream's
+// host state moves yet (submit() may still drop it, lp_commit_slice then moves what is left).
 static void lp_parse_slice(HeaacLayoutPipeline *p, int w)
 {
     const size_t lo = p->n * (size_t)w / (size_t)p->threads, hi = p->n * (size_t)(w + 1) / (size_t)p->threads;
     LpSet *s = p->job_set;
     const int ne = p->ne;
+    HeaacSbrStream *tmp = slice_tmp(p, w);
     float *tc = (float *)malloc((size_t)ne * 2048 * sizeof(float));
     HeaacIcs *ti = (HeaacIcs *)malloc((size_t)ne * 2 * sizeof(HeaacIcs));
     HeaacToolsFrame *tt = (HeaacToolsFrame *)malloc((size_t)ne * sizeof(HeaacToolsFrame));
@@ -190,6 +209,8 @@ static void lp_parse_slice(HeaacLayoutPipeline *p, int w)
             if (r < 0 && tc && (fi.refused & HEAAC_REFUSED_AS_REFERENCE))
                 for (int k = 0; k < ne; k++) p->ast[i * ne + k] = st[k];
             if (r < 0 && tc && (fi.refused & HEAAC_REFUSED_RUN_TOOLS)) {
+                // (never once a coupling element has been read: lp_park leaves the coupling channels' rows alone)
+                for (int k = 0; k < K; k++) assert(!ce[k].present);
                 s->failed[i] = 2;
                 for (int k = 0; k < ne; k++) {
                     const int ch = p->e[k].channels;
@@ -203,37 +224,19 @@ static void lp_parse_slice(HeaacLayoutPipeline *p, int w)
                     }
                 }
             }
-            neutral(p, s, i, s->failed[i] == 2);
+            neutral(p, s, i, tmp, s->failed[i] == 2);
             continue;
         }
         for (int k = 0; k < K; k++) {
             const HeaacCceFrame &c0 = co.cce[k];            // (the same element in every output slot's row)
             unsigned char *cp = s->cpos + (i * K + k) * 3;
             cp[0] = c0.present; cp[1] = c0.outputs_before; cp[2] = c0.seq;
-            if (c0.present) p->cpl->seen[i * K + k] = 1;
+            p->ce_all[i * K + k] = ce[k];
             for (int e = 0; e < ne; e++) {
                 HeaacCceFrame &o = s->h_cce[e][i * K + k];
                 o = co.cce[e * HEAAC_MAX_CCE + k];
                 // "Dependent coupling is not supported together with LTP" (apply_dependent_coupling :1822-1826 returns)
                 if (p->aac.object_type == 4 && o.coupling_point != HEAAC_CC_AFTER_IMDCT) o.n_links = 0;
-            }
-            if (p->he) {
-                // A coupling channel's own SBR (it goes through ff_sbr_apply when it couples AFTER_IMDCT, aacdec.c:1920-1927).
-                // A payload behind an element that couples in the spectrum is read all the same; without one the
-                // reader's state only moves where the channel is transformed.
-                HeaacSbrStream *cs = sst_at(p->cpl->sst[k], i);
-                const bool after = c0.present && c0.coupling_point == HEAAC_CC_AFTER_IMDCT;
-                if (c0.present && ce[k].sbr_payload_bit >= 0) {
-                    (void)heaac_sbr_parse_payload(cs, p->tab, p->aac.sample_rate, p->job_au[i], p->job_size[i], ce[k].sbr_payload_bit,
-                                                  ce[k].sbr_payload_bytes, ce[k].sbr_crc, 1, ce[k].sbr_misplaced ? HEAAC_SBR_MISPLACED : 0,
-                                                  &s->h_csbr[k][i], NULL, NULL);
-                } else if (after) {
-                    heaac_sbr_no_payload(cs, 1, &s->h_csbr[k][i], NULL);
-                } else {
-                    void *tmp = alloca(heaac_sbr_stream_bytes());
-                    memcpy(tmp, cs, heaac_sbr_stream_bytes());
-                    heaac_sbr_no_payload((HeaacSbrStream *)tmp, 1, &s->h_csbr[k][i], NULL);
-                }
             }
             if (c0.present) {
                 memcpy(s->h_ccoef[k] + i * 1024, co.coeffs + k * 1024, 4096);
@@ -247,26 +250,67 @@ static void lp_parse_slice(HeaacLayoutPipeline *p, int w)
         }
         for (int k = 0; k < ne; k++) {
             const int ch = p->e[k].channels;
-            p->ast[i * ne + k] = st[k];
+            p->ast_new[i * ne + k] = st[k];
+            p->te_all[i * ne + k] = te[k];
             s->seq[i * ne + k] = te[k].seq;
             memcpy(s->h_coeffs[k] + i * (size_t)ch * 1024, tc + (size_t)k * 2048, (size_t)ch * 4096);
             memcpy(s->h_ics[k] + i * ch, ti + k * 2, ch * sizeof(HeaacIcs));
             s->h_tools[k][i] = tt[k];
-            if (p->he) {
-                // a failed payload leaves its degraded record (start = 0) and the decode goes on, as ff_sbr_apply does
-                HeaacPsFrame *ps = s->h_ps[k] ? &s->h_ps[k][i] : NULL;
-                if (te[k].sbr_payload_bit >= 0)
-                    (void)heaac_sbr_parse_payload(sst_at(p->e[k].sst, i), p->tab, p->aac.sample_rate, p->job_au[i], p->job_size[i],
-                                                  te[k].sbr_payload_bit, te[k].sbr_payload_bytes, te[k].sbr_crc, ch,
-                                                  (te[k].sbr_misplaced ? HEAAC_SBR_MISPLACED : 0) | (ps ? HEAAC_SBR_ALLOW_PS : 0),
-                                                  &s->h_sbr[k][i], ps, NULL);
-                else
-                    heaac_sbr_no_payload(sst_at(p->e[k].sst, i), ch, &s->h_sbr[k][i], ps);
-            }
         }
     }
     free(tc); free(ti); free(tt);
     free(co.cce); free(co.coeffs); free(co.ics); free(co.tools);
+}
+
+// Phase 1: the streams whose unit submit() kept -- their window histories, the coupling elements they have carried,
+// and their SBR payloads, read into the set's records (the readers and the header table move on here).
+static void lp_commit_slice(HeaacLayoutPipeline *p, int w)
+{
+    const size_t lo = p->n * (size_t)w / (size_t)p->threads, hi = p->n * (size_t)(w + 1) / (size_t)p->threads;
+    LpSet *s = p->job_set;
+    const int ne = p->ne;
+    const int K = p->cpl ? p->cpl->K : 0;
+    HeaacSbrStream *tmp = slice_tmp(p, w);
+    for (size_t i = lo; i < hi; i++) {
+        if (s->failed[i]) continue;
+        for (int k = 0; k < ne; k++) p->ast[i * ne + k] = p->ast_new[i * ne + k];
+        for (int k = 0; k < K; k++) {
+            const unsigned char *cp = s->cpos + (i * K + k) * 3;
+            const HeaacAacElementInfo &ce = p->ce_all[i * K + k];
+            if (cp[0]) p->cpl->seen[i * K + k] = 1;
+            if (p->he) {
+                // A coupling channel's own SBR (it goes through ff_sbr_apply when it couples AFTER_IMDCT, aacdec.c:1920-1927).
+                // A payload behind an element that couples in the spectrum is read all the same; without one the
+                // reader's state only moves where the channel is transformed.
+                HeaacSbrStream *cs = sst_at(p->cpl->sst[k], i);
+                const bool after = cp[0] && s->h_cce[0][i * K + k].coupling_point == HEAAC_CC_AFTER_IMDCT;
+                if (cp[0] && ce.sbr_payload_bit >= 0) {
+                    (void)heaac_sbr_parse_payload(cs, p->tab, p->aac.sample_rate, p->job_au[i], p->job_size[i], ce.sbr_payload_bit,
+                                                  ce.sbr_payload_bytes, ce.sbr_crc, 1, ce.sbr_misplaced ? HEAAC_SBR_MISPLACED : 0,
+                                                  &s->h_csbr[k][i], NULL, NULL);
+                } else if (after) {
+                    heaac_sbr_no_payload(cs, 1, &s->h_csbr[k][i], NULL);
+                } else {
+                    memcpy(tmp, cs, heaac_sbr_stream_bytes());
+                    heaac_sbr_no_payload(tmp, 1, &s->h_csbr[k][i], NULL);
+                }
+            }
+        }
+        if (!p->he) continue;
+        for (int k = 0; k < ne; k++) {
+            // a failed payload leaves its degraded record (start = 0) and the decode goes on, as ff_sbr_apply does
+            const HeaacAacElementInfo &te = p->te_all[i * ne + k];
+            const int ch = p->e[k].channels;
+            HeaacPsFrame *ps = s->h_ps[k] ? &s->h_ps[k][i] : NULL;
+            if (te.sbr_payload_bit >= 0)
+                (void)heaac_sbr_parse_payload(sst_at(p->e[k].sst, i), p->tab, p->aac.sample_rate, p->job_au[i], p->job_size[i],
+                                              te.sbr_payload_bit, te.sbr_payload_bytes, te.sbr_crc, ch,
+                                              (te.sbr_misplaced ? HEAAC_SBR_MISPLACED : 0) | (ps ? HEAAC_SBR_ALLOW_PS : 0),
+                                              &s->h_sbr[k][i], ps, NULL);
+            else
+                heaac_sbr_no_payload(sst_at(p->e[k].sst, i), ch, &s->h_sbr[k][i], ps);
+        }
+    }
 }
 
 static void *lp_worker(void *arg)
@@ -282,7 +326,8 @@ static void *lp_worker(void *arg)
         if (p->quit) break;
         seen = p->generation;
         pthread_mutex_unlock(&p->mu);
-        lp_parse_slice(p, w);
+        if (p->job_phase) lp_commit_slice(p, w);
+        else lp_parse_slice(p, w);
         pthread_mutex_lock(&p->mu);
         if (--p->pending == 0) pthread_cond_signal(&p->cv_done);
     }
@@ -361,6 +406,7 @@ extern "C" void heaac_layout_pipeline_destroy(HeaacLayoutPipeline *p)
     if (p->run) (void)hipStreamDestroy(p->run);
     heaac_sbr_table_destroy(p->tab);
     free(p->ast); free(p->lay);
+    free(p->ast_new); free(p->te_all); free(p->ce_all); free(p->sst_tmp);
     heaac_device_destroy(p->dev);
     free(p);
 }
@@ -514,7 +560,10 @@ extern "C" int heaac_layout_pipeline_create(HeaacLayoutPipeline **out, const Hea
     p->tab = heaac_sbr_table_create(LP_MAX_HDRS);
     p->ast = (HeaacAacStream *)calloc(n * p->ne, sizeof(HeaacAacStream));
     p->lay = (HeaacAacLayout *)malloc(n * sizeof(HeaacAacLayout));
-    ok = ok && p->tab && p->ast && p->lay;
+    p->ast_new = (HeaacAacStream *)calloc(n * p->ne, sizeof(HeaacAacStream));
+    p->te_all = (HeaacAacElementInfo *)calloc(n * p->ne, sizeof(HeaacAacElementInfo));
+    p->ce_all = (HeaacAacElementInfo *)calloc(n * (size_t)(n_cce_slots ? n_cce_slots : 1), sizeof(HeaacAacElementInfo));
+    ok = ok && p->tab && p->ast && p->lay && p->ast_new && p->te_all && p->ce_all;
     if (ok) {
         for (size_t i = 0; i < n; i++) p->lay[i] = *layout;
         // the null header (table entry 0) is what frames before their element's first header point at
@@ -533,7 +582,7 @@ extern "C" int heaac_layout_pipeline_create(HeaacLayoutPipeline **out, const Hea
         pthread_cond_init(&p->cv_go, NULL);
         pthread_cond_init(&p->cv_done, NULL);
         p->tid = (pthread_t *)calloc(threads, sizeof(pthread_t));
-        ok = p->tid != NULL;
+        ok = p->tid != NULL && (!p->he || (p->sst_tmp = (HeaacSbrStream *)malloc(threads * heaac_sbr_stream_bytes())) != NULL);
         for (int t = 1; t < threads && ok; t++) {          // slice 0 is parsed by the submitting thread
             LpWorkerArg *a = (LpWorkerArg *)malloc(sizeof(*a));
             if (!a) { ok = false; break; }
@@ -566,6 +615,9 @@ __global__ void k_lp_rows(const unsigned *__restrict__ list, unsigned *rows, uns
 // rows of every failed stream: element states, predictors, noise generator -- to / from the parking area, which holds
 // one region of `cap` rows per array.  n_all pairs at d_list: every failed stream; n_full at d_list + 2 n: those whose
 // generator and predictors stay put as well (failed == 1; 2: the tools' side of the stream moves on).
+// The coupling channels' state and predictor rows are not parked.  That is safe only because a failed stream carries
+// all-zero coupling-element records (neutral() writes them, keep_tools or not), and for failed == 2 only because the
+// parser never sets HEAAC_REFUSED_RUN_TOOLS once a coupling element has been read (asserted in lp_parse_slice).
 static int lp_park(HeaacLayoutPipeline *p, LpSet *s, unsigned n_all, unsigned n_full, size_t cap, int restore)
 {
     char *region = (char *)p->d_park;
@@ -587,22 +639,31 @@ static int lp_park(HeaacLayoutPipeline *p, LpSet *s, unsigned n_all, unsigned n_
     return hipGetLastError() == hipSuccess ? HEAAC_OK : HEAAC_ERR_HIP;
 }
 
+// one phase of the tick on the pool: slice 0 on the calling thread, the others on the workers
+static void lp_run_slices(HeaacLayoutPipeline *p, int phase)
+{
+    pthread_mutex_lock(&p->mu);
+    p->job_phase = phase;
+    p->pending = p->threads - 1;
+    p->generation++;
+    pthread_cond_broadcast(&p->cv_go);
+    pthread_mutex_unlock(&p->mu);
+    if (phase) lp_commit_slice(p, 0);
+    else lp_parse_slice(p, 0);
+    pthread_mutex_lock(&p->mu);
+    while (p->pending > 0) pthread_cond_wait(&p->cv_done, &p->mu);
+    pthread_mutex_unlock(&p->mu);
+}
+
 extern "C" int heaac_layout_pipeline_submit(HeaacLayoutPipeline *p, const uint8_t *const *au, const int *size, int *status)
 {
     if (!p || !au || !size) return HEAAC_ERR_ARG;
     if (p->submitted - p->collected >= LP_DEPTH) return HEAAC_ERR_ARG;
     LpSet *s = &p->set[p->submitted % LP_DEPTH];
     // (the set's buffers are free: its last tick has been collected, which waited for its `done`)
-    pthread_mutex_lock(&p->mu);
     p->job_au = au; p->job_size = size; p->job_status = status; p->job_set = s;
-    p->pending = p->threads - 1;
-    p->generation++;
-    pthread_cond_broadcast(&p->cv_go);
-    pthread_mutex_unlock(&p->mu);
-    lp_parse_slice(p, 0);
-    pthread_mutex_lock(&p->mu);
-    while (p->pending > 0) pthread_cond_wait(&p->cv_done, &p->mu);
-    pthread_mutex_unlock(&p->mu);
+    lp_run_slices(p, 0);
+    HeaacSbrStream *tmp = slice_tmp(p, 0);          // (slice 0 is the submitting thread's, and the pool is idle)
 
     const size_t n = p->n;
     const int ne = p->ne;
@@ -615,7 +676,7 @@ extern "C" int heaac_layout_pipeline_submit(HeaacLayoutPipeline *p, const uint8_
             bool same = p->have_order != 0;
             for (int k = 0; same && k < ne; k++)
                 same = s->seq[i * ne + k] == 0xff || (s->seq[i * ne + k] < ne && p->order[s->seq[i * ne + k]] == k);
-            if (!same) { s->failed[i] = 1; neutral(p, s, i); }
+            if (!same) { s->failed[i] = 1; neutral(p, s, i, tmp); }
         }
         if (s->failed[i]) { n_failed++; continue; }
         if (!p->have_order) {
@@ -628,7 +689,7 @@ extern "C" int heaac_layout_pipeline_submit(HeaacLayoutPipeline *p, const uint8_
             s->failed[i] = 1;
             n_failed++;
             if (status) status[i] = HEAAC_PARSE_ERR_UNSUPPORTED;
-            neutral(p, s, i);
+            neutral(p, s, i, tmp);
         }
     }
     // ... and where the coupling elements stand among them, tick by tick: the first good stream of the tick says, the
@@ -648,10 +709,13 @@ extern "C" int heaac_layout_pipeline_submit(HeaacLayoutPipeline *p, const uint8_
             s->failed[i] = 1;
             n_failed++;
             if (status) status[i] = HEAAC_PARSE_ERR_UNSUPPORTED;
-            neutral(p, s, i);
+            neutral(p, s, i, tmp);
         }
     }
     for (int k = 0; k < K; k++) n_cce_tick += cpat[k][0];
+    // the units that stand: now they move their streams' host state (a dropped one leaves it as its device rows are
+    // left, parked -- as if the unit had never arrived)
+    lp_run_slices(p, 1);
     const size_t have = heaac_sbr_table_count(p->tab);
     if (have > LP_MAX_HDRS) return HEAAC_ERR_ARG;
     // H2D (the run stream carries everything: the tick before has the GPU meanwhile)

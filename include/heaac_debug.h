@@ -18,10 +18,14 @@ extern "C" {
  * relies on.  Returns HEAAC_OK, or HEAAC_ERR_ARG for a NULL context. */
 int heaac_debug_workspace(HeaacDevice *dev, float **d_W, float **d_X, size_t *chunk);
 
-/* How many QMF bands of each X row the HF / PS stage stored for the frames of workspace set 0 in the LAST decode call
- * (one byte per frame and output channel: 32, 48 or 64; the bands above are +0 and the synthesis kernel reads them
- * from a page of zeros -- DESIGN.md s4).  Copies 2 * n_frames bytes to host memory after a device synchronisation;
- * n_frames must not exceed the context's chunk.  bench.py reports the shares, since the headline leans on them. */
+/* How many QMF bands of each X row the HF / PS stage stored for the frames of the LAST decode call (one byte per frame
+ * and output channel: 32, 48 or 64; the bands above are +0 and the synthesis kernel reads them from a page of zeros --
+ * DESIGN.md s4).  Copies 2 * n_frames bytes to host memory after a device synchronisation.  n_frames may be up to the
+ * frames the context holds records for: its chunk (min(max_frames, 262144)) times its workspace sets (1, or the two
+ * lanes where max_frames exceeds one chunk); more is HEAAC_ERR_ARG, as is a NULL context or buffer.  Chunk c of a
+ * call leaves its records at byte 2 (c mod sets) chunk: for heaac_he_decode_batch(_ex) byte 2 f + ch is frame f,
+ * channel ch.  heaac_he_decode_streams works in chunks of floor(chunk / T) whole streams, so its records are in frame
+ * order only where T divides the chunk.  bench.py reports the shares, since the headline leans on them. */
 int heaac_debug_xbands(HeaacDevice *dev, unsigned char *host_out, size_t n_frames);
 
 #ifdef __cplusplus

@@ -122,8 +122,13 @@ typedef struct HeaacAacStream {
                                      seen with, 0 before.  get_che maps the one element of a channel configuration 1 / 2
                                      stream to the first tag it meets and to no other (ac->tag_che_map, tags_mapped,
                                      aacdec.c:131-177): a later unit whose element carries another tag is refused
-                                     ("channel element %d.%d is not allocated", :2011-2015) */
-    uint8_t pad[3];
+                                     ("channel element %d.%d is not allocated", :2011-2015).  Until a unit of the
+                                     stream has parsed, each ADTS header clears it (output_configure before OC_LOCKED,
+                                     aacdec.c:1942-1955, 243-245), as does implicit Parametric Stereo at the first SBR
+                                     payload of a mono stream (:1666-1673) */
+    uint8_t oc;                   /* internal: where the reference's output configuration stands (OC_LOCKED and the
+                                     like, aac_parse.c) */
+    uint8_t pad[2];
 } HeaacAacStream;
 
 typedef struct HeaacAacFrameInfo {

@@ -81,10 +81,12 @@ void heaac_pipeline_timing(const HeaacPipeline *p, float ms[4]);
  *             where it couples AFTER_IMDCT.  The coupling POINT may differ from stream to stream; the coupling
  *             elements' PLACES in the unit must be the same for all streams of a tick.
  * The streams must emit their elements in one bitstream order (the noise generator runs through them in that order;
- * the first good access unit sets it).  A stream whose unit does not parse, leaves an element out or deviates from
- * the order (status HEAAC_PARSE_ERR_UNSUPPORTED) gets silence for the tick and keeps its DSP state; window histories,
- * noise generator and predictors are left as the reference's decoder leaves its own where the refusal is the
- * reference's (as for heaac_pipeline_submit above).
+ * the first good access unit sets it).  A stream whose unit does not parse or leaves an element out gets silence for
+ * the tick and keeps its DSP state; window histories, noise generator and predictors are left as the reference's
+ * decoder leaves its own where the refusal is the reference's (as for heaac_pipeline_submit above).  A unit that
+ * parses but deviates from the order, or whose coupling elements stand elsewhere than the tick's, is dropped (status
+ * HEAAC_PARSE_ERR_UNSUPPORTED, silence): its stream is left entirely as it was before the unit -- DSP state, window
+ * histories, SBR readers, the coupling elements it has carried -- as if the unit had never arrived.
  * Two ticks may be in flight.  PCM: [n_streams][len][heaac_layout_pipeline_channels()] int16, pinned, valid until two
  * more submits. */
 typedef struct HeaacLayoutPipeline HeaacLayoutPipeline;

@@ -69,6 +69,25 @@ def test_no_gpu_means_loud_failure(pkg):
     assert pkg.lib().ff_mdct_init(ctx, 11, 1, C.c_double(1.0)) == -1
 
 
+def test_debug_xbands_checks_its_arguments(pkg):
+    """include/heaac_debug.h: a NULL context or buffer is HEAAC_ERR_ARG before anything touches the device (the bound
+    on n_frames needs a device: tests/test_streams_gpu.py)."""
+    lib = pkg.lib()
+    buf = (C.c_uint8 * 16)()
+    assert lib.heaac_debug_xbands(None, buf, C.c_size_t(8)) == -1
+    assert lib.heaac_debug_xbands(None, None, C.c_size_t(0)) == -1
+    h = C.c_void_p()
+    if lib.heaac_device_create(C.byref(h), C.c_size_t(64)) == 0:
+        try:
+            assert lib.heaac_debug_xbands(h, None, C.c_size_t(8)) == -1
+            assert lib.heaac_debug_xbands(h, buf, C.c_size_t(65)) == -1          # past the one chunk of 64 frames
+            assert lib.heaac_debug_xbands(h, buf, C.c_size_t(8)) == 0
+        finally:
+            lib.heaac_device_destroy(h)
+    else:
+        assert not h.value
+
+
 def test_product_does_not_reference_oracle():
     """oracle/ is test infrastructure: nothing under the package may include or link it."""
     bad = []

@@ -15,6 +15,57 @@ import test_layout_gpu as LG
 pytestmark = pytest.mark.gpu
 
 SCE, CPE, CCE, LFE = 0, 1, 2, 3
+UNSUPPORTED = -3                # HEAAC_PARSE_ERR_UNSUPPORTED: also the status of a unit the pipeline drops
+
+
+def _decode(lib, ctx, b, out):
+    from test_shim_gpu import HeaacPacket
+    buf = C.create_string_buffer(b, len(b))
+    pkt = HeaacPacket(C.cast(buf, C.c_void_p), len(b))
+    size = C.c_int(192000)
+    return lib.heaac_codec_decode(C.byref(ctx), out, C.byref(size), C.byref(pkt)), size.value
+
+
+class _NeverGiven:
+    """One heaac_codec_decode context per stream that is never given the units the pipeline drops: a unit that
+    parses but deviates from the tick (element order, coupling places) must leave its stream as if it had never
+    arrived.  feed(unit, status) returns (used, size), or None for a dropped unit.  A unit with status
+    HEAAC_PARSE_ERR_UNSUPPORTED is tried on a fresh context that replays the stream first: where the codec refuses it
+    too, the refusal is the parser's (and moves what the reference's decoder moves), and the fresh context takes
+    over; where the codec decodes it, the pipeline dropped it."""
+    def __init__(self, lib, asc):
+        self.lib, self.asc, self.fed = lib, asc, []
+        self.out = (C.c_int16 * (192000 // 2))()
+        self.ctx = self._open()
+
+    def _open(self):
+        from test_shim_gpu import HeaacCodecContext
+        codec = C.c_void_p.in_dll(self.lib, "heaac_aac_decoder")
+        ctx = HeaacCodecContext(cfg=-1, extradata=self.asc, extradata_size=len(self.asc))
+        assert self.lib.heaac_codec_open(C.byref(ctx), C.c_void_p(C.addressof(codec))) == 0
+        return ctx
+
+    def feed(self, b, status):
+        if status == UNSUPPORTED:
+            ctx = self._open()
+            for u in self.fed:
+                _decode(self.lib, ctx, u, self.out)
+            used, size = _decode(self.lib, ctx, b, self.out)
+            if used >= 0:
+                assert self.lib.heaac_codec_close(C.byref(ctx)) == 0
+                return None
+            assert self.lib.heaac_codec_close(C.byref(self.ctx)) == 0
+            self.ctx = ctx
+        else:
+            used, size = _decode(self.lib, self.ctx, b, self.out)
+        self.fed.append(b)
+        return used, size
+
+    def pcm(self, length, nch):
+        return np.frombuffer(self.out, np.int16, length * nch).reshape(length, nch)
+
+    def close(self):
+        assert self.lib.heaac_codec_close(C.byref(self.ctx)) == 0
 
 
 def _stream_units(pkg, rng, mode, ticks):
@@ -185,6 +236,11 @@ def test_layout_pipeline_and_codec_agree_on_damaged_streams(pkg, dev, mode, seed
         for i in range(n):
             if rng.random() < 0.4:
                 fed[t][i] = _mutate(rng, fed[t][i], pool)
+    # one unit with its first two elements swapped: the codec takes it (the tags are mapped by then), the pipeline
+    # wants the order its first good unit set and drops it
+    import test_parse_layout as TL
+    elems = LG.MODES[mode][1]
+    fed[3][5] = TL.build(np.random.default_rng(3), si, aot, [elems[1], elems[0]] + list(elems[2:]), extras=False)[0]
     pl = pkg.LayoutPipeline(m4, layout, n, threads=3)
     nch, length = pl.ch, pl.len
     got, status = [], []
@@ -192,32 +248,30 @@ def test_layout_pipeline_and_codec_agree_on_damaged_streams(pkg, dev, mode, seed
         status.append(np.array(pl.submit(fed[t])).copy())
         got.append(pl.collect().copy())
     pl.close()
-    codec = C.c_void_p.in_dll(lib, "heaac_aac_decoder")
-    out = (C.c_int16 * (192000 // 2))()
-    refused = after = 0
+    refused = after = dropped = 0
     for i in range(n):
-        ctx = HeaacCodecContext(cfg=-1, extradata=asc, extradata_size=len(asc))
-        assert lib.heaac_codec_open(C.byref(ctx), C.c_void_p(C.addressof(codec))) == 0
+        model = _NeverGiven(lib, asc)
         seen = False
         for t in range(ticks):
-            b = fed[t][i]
-            buf = C.create_string_buffer(b, len(b))
-            pkt = HeaacPacket(C.cast(buf, C.c_void_p), len(b))
-            size = C.c_int(192000)
-            used = lib.heaac_codec_decode(C.byref(ctx), out, C.byref(size), C.byref(pkt))
+            r = model.feed(fed[t][i], int(status[t][i]))
+            if r is None:
+                # dropped (the pipeline wants one element order for all its streams): silence, and from here on the
+                # stream is what a codec context is that never saw the unit
+                assert not got[t][i].any(), (mode, i, t)
+                dropped += 1
+                seen = True
+                continue
+            used, size = r
             if used < 0:
                 assert status[t][i] < 0 and not got[t][i].any(), (mode, i, t, int(status[t][i]))
                 refused += 1
                 seen = True
                 continue
-            if status[t][i] == -3:
-                break           # (the pipeline wants one element order for all its streams: this stream left it)
-            assert status[t][i] == 0 and size.value == length * nch * 2, (mode, i, t, int(status[t][i]))
-            pcm = np.frombuffer(out, np.int16, length * nch).reshape(length, nch)
-            assert np.array_equal(pcm, got[t][i]), (mode, i, t)
+            assert status[t][i] == 0 and size == length * nch * 2, (mode, i, t, int(status[t][i]))
+            assert np.array_equal(model.pcm(length, nch), got[t][i]), (mode, i, t)
             after += seen
-        assert lib.heaac_codec_close(C.byref(ctx)) == 0
-    assert refused > n // 3 and after > n // 2
+        model.close()
+    assert refused > n // 3 and after > n // 2 and dropped >= 1 and status[3][5] == UNSUPPORTED
 
 
 def _coupled_unit(rng, si, aot, elems, tags, at, points, payloads=None, cce_payloads=None, quiet=False):
@@ -247,6 +301,13 @@ def _coupled_unit(rng, si, aot, elems, tags, at, points, payloads=None, cce_payl
                 CR.put_sbr_fill(bw, payloads[pos])
     bw.put(7, 3)
     return bw.bytes()
+
+
+def _moved(at, n_elems):
+    """Other places for the coupling elements (each one output element further on, cyclically)."""
+    moved = sorted((a + 1) % (n_elems + 1) for a in at)
+    assert moved != list(at)
+    return moved
 
 
 @pytest.mark.parametrize("name", ["five_one", "main_three", "pair_dependent", "mono_independent", "he_three_dependent", "he_three_all"])
@@ -290,6 +351,7 @@ def test_layout_pipeline_with_coupling_elements_equals_one_codec_context_per_str
             if rng.random() < 0.25:
                 fed[t][i] = _mutate(rng, fed[t][i], pool)
     fed[4][3] = one(3, cc_tags[:-1], at[:-1])              # a coupling element left out: refused
+    fed[5][6] = one(6, places=_moved(at, len(elems)))      # the coupling elements elsewhere in the unit: dropped
     pl = pkg.LayoutPipeline(m4, layout, n, threads=3)
     assert pl.ch == nch and pl.len == length
     got, status = [], []
@@ -297,29 +359,144 @@ def test_layout_pipeline_with_coupling_elements_equals_one_codec_context_per_str
         status.append(np.array(pl.submit(fed[t])).copy())
         got.append(pl.collect().copy())
     pl.close()
-    codec = C.c_void_p.in_dll(lib, "heaac_aac_decoder")
-    out = (C.c_int16 * (192000 // 2))()
-    decoded = refused = 0
+    decoded = refused = dropped = 0
     for i in range(n):
-        ctx = HeaacCodecContext(cfg=-1, extradata=asc, extradata_size=len(asc))
-        assert lib.heaac_codec_open(C.byref(ctx), C.c_void_p(C.addressof(codec))) == 0
+        model = _NeverGiven(lib, asc)
         for t in range(ticks):
-            b = fed[t][i]
-            buf = C.create_string_buffer(b, len(b))
-            pkt = HeaacPacket(C.cast(buf, C.c_void_p), len(b))
-            size = C.c_int(192000)
-            used = lib.heaac_codec_decode(C.byref(ctx), out, C.byref(size), C.byref(pkt))
+            r = model.feed(fed[t][i], int(status[t][i]))
+            if r is None:
+                # (a unit that moved an element or a coupling element: the pipeline wants one order and one place of the
+                # coupling elements for all streams of a tick) -- silence, and the stream goes on as if it never came
+                assert not got[t][i].any(), (name, i, t)
+                dropped += 1
+                continue
+            used, size = r
             if used < 0:
                 assert status[t][i] < 0 and not got[t][i].any(), (name, i, t, int(status[t][i]))
                 refused += 1
                 continue
-            if status[t][i] == -3:
-                break                   # (a damaged unit moved an element: the pipeline wants one order for all its streams)
             # (a negative status with samples: an SBR payload that failed behind a damaged unit -- SBR off for the unit)
-            assert size.value == length * nch * 2, (name, i, t, int(status[t][i]))
-            pcm = np.frombuffer(out, np.int16, length * nch).reshape(length, nch)
+            assert size == length * nch * 2, (name, i, t, int(status[t][i]))
+            pcm = model.pcm(length, nch)
             assert np.array_equal(pcm, got[t][i]), (name, i, t, np.argwhere(pcm != got[t][i])[:3])
             decoded += 1
-        assert lib.heaac_codec_close(C.byref(ctx)) == 0
-    assert status[4][3] < 0 and decoded > n * ticks // 2 and refused >= 1
+        model.close()
+    assert status[4][3] < 0 and decoded > n * ticks // 2 and refused >= 1 and dropped >= 1
+    assert max(int(np.abs(g.astype(int)).max()) for g in got) > 50
+
+
+def _coupled_streams(pkg, name, seed, n_distinct):
+    """The setup of the coupling tests: (asc, m4, layout, nch, length, unit(i, order=None, places=None))."""
+    import coupled_ref as CR
+    import test_coupling_gpu as TC
+    aot, elems, cc_tags, points = TC.STREAMS[name]
+    rng = np.random.default_rng(seed)
+    he = name.startswith("he_")
+    si = 6 if he else 3
+    asc = CR.asc(aot, si, elems, cc_tags, rng, he=he)
+    r, m4, layout = pkg.asc_layout(asc)
+    assert r == 0
+    if not he:
+        m4.sbr = 0
+    at = [int(x) for x in sorted(rng.integers(0, len(elems) + 1, len(cc_tags)))]
+    uws = [CR.UnitWriter(pkg, rng, si, aot, elems, cc_tags, points, he) for _ in range(n_distinct)]
+
+    def unit(i, order=None, places=None):
+        """Stream i's next unit; `order`: its output elements in this order (a permutation of the layout's list)."""
+        uw = uws[i]
+        order = list(range(len(elems))) if order is None else order
+        pay = {k: uw._payload(w) for k, w in uw.writers.items()}
+        cpay = {g: uw._payload(w) for g, w in uw.cce_writers.items()}
+        return _coupled_unit(rng, si, aot, [elems[k] for k in order], cc_tags, at if places is None else places, points,
+                             {pos: pay.get(k) for pos, k in enumerate(order)}, cpay, quiet=he)
+
+    def writers(i):
+        return list(uws[i].writers.values()) + list(uws[i].cce_writers.values())
+
+    unit.writers, unit.at, unit.n_elems = writers, at, len(elems)
+    return asc, m4, layout, int(layout[0]["channels"]), 2048 if he else 1024, unit
+
+
+@pytest.mark.parametrize("name", ["five_one", "he_three_all"])
+@pytest.mark.parametrize("how", ["swapped_elements", "moved_coupling_element"])
+def test_a_dropped_unit_leaves_its_stream_as_if_it_had_never_come(pkg, dev, name, how):
+    """a unit that parses but deviates from the tick -- two output elements swapped, or the coupling
+    elements at other places than the tick's -- is dropped after the parse (status HEAAC_PARSE_ERR_UNSUPPORTED,
+    silence).  Its stream's host state (window histories, SBR readers, header table entries, coupling elements seen)
+    must stay with its parked device rows: every later tick of that stream is bit for bit a codec context's that was
+    never given the unit, and the other streams of the tick are untouched.  AAC-LC 5.1 with two coupling elements;
+    HE-AAC 3.0 + LFE whose coupling channels also couple behind the IMDCT, through SBR of their own."""
+    import copy
+    lib = pkg.lib()
+    n, ticks, drop_tick, j = 6, 6, 2, 3
+    asc, m4, layout, nch, length, unit = _coupled_streams(pkg, name, sum(map(ord, name + how)), n)
+    fed = []
+    for t in range(ticks):
+        row = []
+        for i in range(n):
+            if (t, i) != (drop_tick, j):
+                row.append(unit(i))
+                continue
+            # (the payload writers of the stream are put back behind the dropped unit: the next unit's SBR payloads
+            # follow the last one the decoder has seen)
+            keep = [copy.deepcopy((w.ch, w.ps, w.header, w.hdr_rec, w.kx_m, w.coupling)) for w in unit.writers(i)]
+            if how == "swapped_elements":
+                order = list(range(unit.n_elems))
+                order[0], order[1] = 1, 0
+                row.append(unit(i, order=order))
+            else:
+                row.append(unit(i, places=_moved(unit.at, unit.n_elems)))
+            for w, k in zip(unit.writers(i), keep):
+                w.ch, w.ps, w.header, w.hdr_rec, w.kx_m, w.coupling = k
+        fed.append(row)
+    pl = pkg.LayoutPipeline(m4, layout, n, threads=3)
+    assert pl.ch == nch and pl.len == length
+    got, status = [], []
+    for t in range(ticks):
+        status.append(np.array(pl.submit(fed[t])).copy())
+        got.append(pl.collect().copy())
+    pl.close()
+    for t in range(ticks):
+        for i in range(n):
+            assert status[t][i] == (UNSUPPORTED if (t, i) == (drop_tick, j) else 0), (t, i, int(status[t][i]))
+    assert not got[drop_tick][j].any()
+    for i in range(n):
+        model = _NeverGiven(lib, asc)
+        for t in range(ticks):
+            r = model.feed(fed[t][i], int(status[t][i]))
+            if (t, i) == (drop_tick, j):
+                assert r is None                    # the codec decodes the unit: only the pipeline drops it
+                continue
+            used, size = r
+            assert used == len(fed[t][i]) and size == length * nch * 2, (t, i, used)
+            pcm = model.pcm(length, nch)
+            assert np.array_equal(pcm, got[t][i]), (how, t, i, np.argwhere(pcm != got[t][i])[:3])
+        model.close()
+    assert all(got[t][j].any() for t in range(drop_tick + 1, ticks))
+
+
+def test_a_tick_of_thousands_of_units_per_slice_with_spectrum_coupling_and_no_payload(pkg, dev):
+    """8 192 HE-AAC streams of a 3.0 + LFE layout on two parser threads (4 096 per slice), every unit with coupling
+    elements that couple in the spectrum and carry no SBR payload of their own -- the case that took a copy of the
+    coupling channel's SBR reader state on the stack for every stream of the slice, every tick.  The streams are
+    copies of 16 distinct ones, each compared with one heaac_codec_decode context per distinct stream."""
+    distinct, n, ticks = 16, 8192, 3
+    lib = pkg.lib()
+    asc, m4, layout, nch, length, unit = _coupled_streams(pkg, "he_three_dependent", 4096, distinct)
+    units = [[unit(j) for j in range(distinct)] for _ in range(ticks)]
+    pl = pkg.LayoutPipeline(m4, layout, n, threads=2)
+    got = []
+    for t in range(ticks):
+        st = np.array(pl.submit([units[t][i % distinct] for i in range(n)])).copy()
+        assert (st == 0).all(), t
+        got.append(pl.collect().copy())
+    pl.close()
+    for j in range(distinct):
+        model = _NeverGiven(lib, asc)
+        for t in range(ticks):
+            used, size = model.feed(units[t][j], 0)
+            assert used == len(units[t][j]) and size == length * nch * 2, (j, t, used)
+            copies = got[t][j::distinct]
+            assert copies.shape[0] == n // distinct and (copies == model.pcm(length, nch)[None]).all(), (j, t)
+        model.close()
     assert max(int(np.abs(g.astype(int)).max()) for g in got) > 50

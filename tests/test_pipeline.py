@@ -213,3 +213,89 @@ def test_a_damaged_access_unit_gives_silence_and_leaves_its_stream_as_it_was(pkg
         for t in range(bad_tick + 1, ticks):
             assert np.array_equal(got[t][i], skip[t - 1][i]), (t, i)
         assert any(got[t][i].any() for t in range(bad_tick + 1, ticks))
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# tick scale: thousands of streams per parser slice
+# ------------------------------------------------------------------------------------------------------------------
+def test_the_parse_slices_take_no_stack_per_stream(pkg):
+    """a copy of the SBR reader state on the stack inside the per-stream loop (alloca) is released only at
+    return -- 3.3 KB per failed stream, so a slice of a few thousand failed streams overflowed an 8 MiB thread stack.
+    No alloca in the library's sources, and no dynamic stack-pointer move in the functions that walk the streams
+    (a register written to %rsp is what a loop-scoped alloca or variable-length array compiles to)."""
+    import glob
+    import os
+    import re
+    import shutil
+    import subprocess
+    csrc = os.path.join(os.path.dirname(os.path.abspath(pkg.__file__)), "csrc")
+    sources = glob.glob(os.path.join(csrc, "*.hip")) + glob.glob(os.path.join(csrc, "*.c"))
+    assert sources
+    for path in sources:
+        with open(path) as f:
+            assert "alloca(" not in f.read(), path
+    objdump = shutil.which("objdump")
+    assert objdump, "binutils' objdump is part of the build toolchain"
+    text = subprocess.run([objdump, "-d", "-C", "--no-show-raw-insn", pkg.LIB_PATH], check=True, capture_output=True,
+                          text=True).stdout
+    fn, seen, moves = None, set(), []
+    walkers = ("parse_slice", "commit_slice", "run_slices", "worker(", "pipeline_submit", "neutral(")
+    for line in text.splitlines():
+        m = re.match(r"^[0-9a-f]+ <(.*)>:$", line)
+        if m:
+            fn = m.group(1) if any(w in m.group(1) for w in walkers) else None
+            if fn:
+                seen.add(fn)
+            continue
+        if fn and re.search(r"\s(mov|sub|lea)\w*\s+[^$\s]\S*,%rsp$", line):
+            moves.append((fn, line.strip()))
+    assert {"parse_slice(HeaacPipeline*, int)", "lp_parse_slice(HeaacLayoutPipeline*, int)"} <= seen, sorted(seen)
+    assert not moves, moves
+
+
+@pytest.mark.gpu
+def test_a_tick_of_thousands_of_refused_units_per_slice_gives_silence_and_the_streams_carry_on(pkg, dev):
+    """8 192 HE-AACv2 streams on two parser threads (4 096 per slice, well past the stack that a per-stream copy of
+    the SBR reader state used to exhaust).  Tick 1 has every unit damaged: every stream is refused and silent.  The
+    streams are copies of 16 distinct ones, and each is compared, tick for tick, with one heaac_codec_decode context
+    per distinct stream fed the same units."""
+    from test_shim_gpu import HeaacCodecContext, HeaacPacket
+    lib = pkg.lib()
+    rng = np.random.default_rng(8192)
+    distinct, n, ticks, bad_tick = 16, 8192, 4, 1
+    units = _ticks(pkg, rng, 1, True, distinct, ticks)
+    damaged = bytes([0x40, 0]) + bytes(8)          # a coupling element in a one-element stream: refused at once
+    fed = [list(u) for u in units]
+    fed[bad_tick] = [damaged] * distinct
+    m4 = TS._he_cfg(pkg, 1, True)
+    pl = pkg.Pipeline(m4, pkg.CFG_HEV2, n, threads=2)
+    got = []
+    for t in range(ticks):
+        st = np.array(pl.submit([fed[t][i % distinct] for i in range(n)])).copy()
+        if t == bad_tick:
+            assert (st < 0).all()
+        got.append(pl.collect().copy())
+    pl.close()
+    assert not got[bad_tick].any()
+    asc = bytes([0xEB, 0x09, 0x88, 0x00])
+    codec = C.c_void_p.in_dll(lib, "heaac_aac_decoder")
+    out = (C.c_int16 * (192000 // 2))()
+    for j in range(distinct):
+        ctx = HeaacCodecContext(cfg=-1, extradata=asc, extradata_size=len(asc))
+        assert lib.heaac_codec_open(C.byref(ctx), C.c_void_p(C.addressof(codec))) == 0
+        for t in range(ticks):
+            b = fed[t][j]
+            buf = C.create_string_buffer(b, len(b))
+            pkt = HeaacPacket(C.cast(buf, C.c_void_p), len(b))
+            size = C.c_int(192000)
+            used = lib.heaac_codec_decode(C.byref(ctx), out, C.byref(size), C.byref(pkt))
+            if t == bad_tick:
+                assert used < 0, j
+                continue
+            assert used == len(b) and size.value == 2048 * 2 * 2, (j, t, used)
+            pcm = np.frombuffer(out, np.int16, 2048 * 2).reshape(2048, 2)
+            copies = got[t][j::distinct]
+            assert copies.shape[0] == n // distinct
+            assert (copies == pcm[None]).all(), (j, t)
+        assert lib.heaac_codec_close(C.byref(ctx)) == 0
+    assert int(np.abs(got[ticks - 1].astype(int)).max()) > 50

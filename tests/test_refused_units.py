@@ -494,3 +494,130 @@ def test_elements_the_configuration_has_no_place_for_fail_the_unit_where_get_che
             assert bool(info["refused"] & pkg.REFUSED_RUN_TOOLS) == bool(model["draws"])
             if model["draws"]:
                 assert sum(_record_draws(out["tools"][0]["ch"][c]) for c in range(ch)) == model["draws"]
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# get_che's tag map and output_configure: before the first unit has decoded, every ADTS header configures the
+# stream again and clears the map (aacdec.c:1942-1955, 243-245; OC_LOCKED :2100-2101)
+# ------------------------------------------------------------------------------------------------------------------
+def _refused_at_ics_info(rng, ch, tag):
+    """A channel element under `tag` whose (first) ics_info has its reserved bit set: get_che has mapped the tag when
+    decode_ics_info refuses (:650); that channel's window history is cleared, nothing else moves."""
+    if ch == 1:
+        bits, _, model = R.sce_element(rng, SI, 2, "reserved_bit", tag=tag)
+        return bits, model
+    bits, _, _ = R.cpe_element(rng, SI, 2, "good", tag=tag)
+    bits = list(bits)
+    assert bits[16] == 0
+    bits[16] = 1                                   # behind the header (7), common_window (1) and global_gain (8)
+    return bits, dict(history=[(0, 0), (0, 0)], draws=0, predicted=[])
+
+
+def _tag_units(rng, ch, adts):
+    """Units of one stream: [refused under tag 3, good under 5, good under 3, good under 5], with their models."""
+    import test_adts_split as TA
+    writer = R.sce_element if ch == 1 else R.cpe_element
+    bad, bad_model = _refused_at_ics_info(rng, ch, 3)
+    units, models = [R._bytes(bad + R.END)], [bad_model]
+    for tag in (5, 3, 5):
+        bits, _, model = writer(rng, SI, 2, "good", tag=tag)
+        units.append(R._bytes(bits + R.END))
+        models.append(model)
+    if adts:
+        units = [TA.adts_frame(u, aot=2, si=SI, chan=ch) for u in units]
+    return units, models
+
+
+@pytest.mark.parametrize("ch", [1, 2])
+@pytest.mark.parametrize("adts", [True, False])
+def test_a_tag_refused_before_the_first_decoded_unit_is_forgotten_at_the_next_adts_header(pkg, ch, adts):
+    """Unit 1 maps tag 3 and is refused.  With ADTS headers the next header configures again: unit 2 under tag 5
+    decodes and locks the stream, so unit 3 under tag 3 is refused as the reference refuses it.  Raw units have been
+    configured once (aac_decode_init, :430): tag 3 stays, unit 2 is refused and unit 3 decodes."""
+    rng = np.random.default_rng(40 + ch)
+    units, models = _tag_units(rng, ch, adts)
+    cfg = TP._cfg(pkg, 2, SI, ch)
+    st = np.zeros(1, pkg.AAC_STREAM_DT)
+    want_ok = [False, True, False, True] if adts else [False, False, True, False]
+    want_tag = [4, 6, 6, 6] if adts else [4, 4, 4, 4]
+    for k, (au, model) in enumerate(zip(units, models)):
+        before = st.copy()
+        r, out = pkg.aac_parse_frame_ex(cfg, st[0:1], au, with_cce=False)
+        info = out["info"][0]
+        assert (r == 0) == want_ok[k], (k, r)
+        assert int(st["mapped_tag"][0]) == want_tag[k], k
+        if r == 0:
+            assert int(info["elem_id"]) == (5 if adts else 3) and int(info["channels"]) == ch
+            assert [_history(st, c) for c in range(ch)] == model["history"]
+        else:
+            assert info["refused"] == pkg.REFUSED_AS_REFERENCE, (k, info["refused"])
+            if k == 0:
+                assert [_history(st, c) for c in range(ch)] == model["history"]
+            else:
+                # get_che finds nothing for the element: nothing of it is read, the history stays
+                assert st["window_sequence"].tobytes() == before["window_sequence"].tobytes()
+                assert st["use_kb_window"].tobytes() == before["use_kb_window"].tobytes()
+
+
+def test_implicit_parametric_stereo_configures_a_mono_stream_again_at_its_first_sbr_payload(pkg):
+    """decode_extension_payload (:1666-1673): m4ac.ps == -1 in a one-channel stream before the lock -> ps = 1 and
+    output_configure, which clears the tag the SCE was just mapped to.  The unit decodes and locks the stream with an
+    empty map: the next unit's tag is the one that stays.  A stream that signals PS explicitly keeps its first tag."""
+    rng = np.random.default_rng(44)
+    fill = [1, 1, 0, 0, 0, 1, 0, 1, 1, 0, 1] + [0] * 12            # FIL, cnt 2: EXT_SBR_DATA and 12 bits of payload
+    units = []
+    for k, tag in enumerate((3, 5, 3, 5)):
+        bits, _, _ = R.sce_element(rng, SI, 2, "good", tag=tag)
+        units.append(R._bytes(bits + (fill if k < 2 else []) + R.END))
+    for ps, want_ok, want_tag in ((-1, [True, True, False, True], [0, 6, 6, 6]),
+                                  (1, [True, False, True, False], [4, 4, 4, 4])):
+        cfg = TP._cfg(pkg, 2, SI, 1)
+        cfg.sbr, cfg.ps = -1, ps
+        st = np.zeros(1, pkg.AAC_STREAM_DT)
+        for k, au in enumerate(units):
+            r, out = pkg.aac_parse_frame_ex(cfg, st[0:1], au, with_cce=False)
+            assert (r == 0) == want_ok[k], (ps, k, r)
+            assert int(st["mapped_tag"][0]) == want_tag[k], (ps, k)
+            if k < 2 and r == 0:
+                assert int(out["info"][0]["sbr_payload_bit"]) >= 0
+            if r < 0:
+                assert out["info"][0]["refused"] == pkg.REFUSED_AS_REFERENCE
+        # with SBR signalled absent the payload is skipped ("SBR signaled to be not-present", :1660-1663): no re-configure
+    cfg = TP._cfg(pkg, 2, SI, 1)
+    cfg.sbr, cfg.ps = 0, -1
+    st = np.zeros(1, pkg.AAC_STREAM_DT)
+    assert [pkg.aac_parse_frame_ex(cfg, st[0:1], au, with_cce=False)[0] == 0 for au in units] == [True, False, True, False]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("ch", [1, 2])
+def test_the_codec_surface_takes_a_new_tag_after_a_refused_first_adts_unit(pkg, oracle, dev, ch):
+    """The stream above as ADTS packets through heaac_codec_decode (the header configures the context): -1 for the
+    refused units, and for the two that decode the oracle's PCM of those two units in a row."""
+    from test_shim_gpu import HeaacCodecContext
+    lib = pkg.lib()
+    units, _ = _tag_units(np.random.default_rng(40 + ch), ch, adts=True)
+    raw, _ = _tag_units(np.random.default_rng(40 + ch), ch, adts=False)
+    cfg = TP._cfg(pkg, 2, SI, ch)
+    # the first unit moves nothing the decode of the others depends on (its window history was cleared, as zero is)
+    want = _expected_run(pkg, oracle, cfg, ch, 2, [[raw[1]], [raw[3]]], -1, {})
+    codec = C.c_void_p.in_dll(lib, "heaac_aac_decoder")
+    out = (C.c_int16 * (192000 // 2))()
+    ctx = HeaacCodecContext(cfg=-1)
+    assert lib.heaac_codec_open(C.byref(ctx), C.c_void_p(C.addressof(codec))) == 0
+    got = []
+    for k, b in enumerate(units):
+        buf = C.create_string_buffer(b, len(b))
+        from test_shim_gpu import HeaacPacket
+        pkt = HeaacPacket(C.cast(buf, C.c_void_p), len(b))
+        size = C.c_int(192000)
+        used = lib.heaac_codec_decode(C.byref(ctx), out, C.byref(size), C.byref(pkt))
+        if k in (0, 2):
+            assert used < 0, k
+            continue
+        assert used == len(b) and size.value == 1024 * ch * 2, (k, used, size.value)
+        got.append(np.frombuffer(out, np.int16, 1024 * ch).reshape(1024, ch).copy())
+    assert lib.heaac_codec_close(C.byref(ctx)) == 0
+    for t in range(2):
+        assert np.array_equal(got[t], want[t][0]), t
+    assert any(g.any() for g in got)

@@ -282,3 +282,36 @@ def test_streams_graph_capture(pkg, oracle, dev):
     assert np.array_equal(pcm.cpu().numpy().reshape(ref_pcm.shape), ref_pcm)
     nbad, where = _mismatch(st_out.cpu().numpy(), ref_state)
     assert nbad == 0, where
+
+
+def test_x_band_records_past_one_chunk_are_the_frames_in_order(pkg):
+    """heaac_debug_xbands for a call of two chunks on two lanes (bench.py asks for it after the timed work of any
+    --frames above 262 144): Device(max_frames=300 000) decodes 300 000 HE-AACv2 frames with mixed headers in one call,
+    and the hook's 600 000 bytes equal the records of the same frames decoded in two calls of at most one chunk.
+    More frames than the device holds records for (two sets of one chunk) are an argument error."""
+    import torch
+    cfg, n, base, chunk = pkg.CFG_HEV2, 300000, 1000, 262144
+    hdr = _synth().default_headers(pkg)
+    fr = _frames(pkg, cfg, base, 2, 43, hdr, ps_mode="mix")
+    flat = {k: np.tile(fr[k][:, 1], (n // base,) + (1,) * (fr[k].ndim - 2)) for k in ("coeffs", "ics", "sbr", "ps")}
+    d_hdr = pkg.to_device(hdr)
+    d = pkg.Device(max_frames=n)
+    try:
+        def run(lo, hi):
+            col = {k: np.ascontiguousarray(flat[k][lo:hi]) for k in flat}
+            st = torch.zeros((hi - lo, pkg.STATE_WORDS[cfg]), device="cuda")
+            d.he_decode(cfg, torch.from_numpy(col["coeffs"]).cuda(), pkg.to_device(col["ics"]), pkg.to_device(col["sbr"]),
+                        d_hdr, pkg.to_device(col["ps"]), st, state_out=st, pcm_format=pkg.PCM_S16)
+            torch.cuda.synchronize()
+            return d.x_bands(hi - lo)
+        whole = run(0, n)
+        parts = np.concatenate([run(0, chunk), run(chunk, n)])
+        assert whole.shape == (n, 2) and whole.tobytes() == parts.tobytes()
+        assert set(np.unique(whole).tolist()) <= {32, 48, 64}
+        # the frames of the first chunk are the first frames of the call, those of the second follow
+        assert np.array_equal(whole[chunk:], run(chunk, n))
+        assert d.x_bands(2 * chunk).shape == (2 * chunk, 2)
+        with pytest.raises(pkg.HeaacError):
+            d.x_bands(2 * chunk + 1)
+    finally:
+        d.close()

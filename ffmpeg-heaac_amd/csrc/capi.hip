@@ -11,6 +11,7 @@
 #include "heaac_debug.h"
 #include "tables.h"
 #include "kernels.h"
+#include "host_common.h"
 
 #define HE_MAX_LANES 4
 #define HE_ZERO_BYTES (2 * 38 * 64 * 4)      // one channel's X record of +0: what k_synth reads for bands that were not stored
@@ -81,6 +82,12 @@ static int he_lanes()
     return l < 1 ? 1 : l > HE_MAX_LANES ? HE_MAX_LANES : l;
 }
 #define HE_LANES he_lanes()
+
+static bool pcm_format_ok(int f)
+{
+    return f == HEAAC_PCM_F32_PLANAR || f == HEAAC_PCM_S16_INTERLEAVED || f == HEAAC_PCM_S16_INTERLEAVED_SSE2;
+}
+static bool he_cfg_ok(int cfg) { return heaac_cfg_shape(cfg).he != 0; }
 
 extern "C" const char *heaac_build_info(void)
 {
@@ -217,9 +224,7 @@ extern "C" int heaac_lc_decode_batch(HeaacDevice *dev, int channels,
                                      const float *d_state_in, float *d_state_out,
                                      void *d_pcm, int pcm_format, size_t n, void *stream)
 {
-    if (!dev || channels < 1 || channels > 2 ||
-        (pcm_format != HEAAC_PCM_F32_PLANAR && pcm_format != HEAAC_PCM_S16_INTERLEAVED &&
-         pcm_format != HEAAC_PCM_S16_INTERLEAVED_SSE2))
+    if (!dev || channels < 1 || channels > 2 || !pcm_format_ok(pcm_format))
         return HEAAC_ERR_ARG;
     if (n == 0)
         return HEAAC_OK;
@@ -235,9 +240,7 @@ extern "C" int heaac_lc_decode_streams(HeaacDevice *dev, int channels,
                                        void *d_pcm, int pcm_format,
                                        size_t n_streams, size_t frames_per_stream, void *stream)
 {
-    if (!dev || channels < 1 || channels > 2 ||
-        (pcm_format != HEAAC_PCM_F32_PLANAR && pcm_format != HEAAC_PCM_S16_INTERLEAVED &&
-         pcm_format != HEAAC_PCM_S16_INTERLEAVED_SSE2) || frames_per_stream == 0)
+    if (!dev || channels < 1 || channels > 2 || !pcm_format_ok(pcm_format) || frames_per_stream == 0)
         return HEAAC_ERR_ARG;
     if (n_streams == 0)
         return HEAAC_OK;
@@ -317,138 +320,30 @@ extern "C" int heaac_spectral_tools_streams(HeaacDevice *dev, int channels, floa
                                                d_pred_out, n_streams, frames_per_stream, (hipStream_t)stream);
 }
 
-extern "C" int heaac_he_decode_batch_ex(HeaacDevice *dev, int cfg, int flags,
-                                        const float *d_coeffs, const HeaacIcs *d_ics,
-                                        const HeaacSbrFrame *d_sbr,
-                                        const HeaacSbrHeader *d_hdr, size_t n_hdr,
-                                        const HeaacPsFrame *d_ps,
-                                        const float *d_state_in, float *d_state_out,
-                                        void *d_pcm, int pcm_format,
-                                        size_t n, void *stream);
-
-extern "C" int heaac_he_decode_batch(HeaacDevice *dev, int cfg,
-                                     const float *d_coeffs, const HeaacIcs *d_ics,
-                                     const HeaacSbrFrame *d_sbr,
-                                     const HeaacSbrHeader *d_hdr, size_t n_hdr,
-                                     const HeaacPsFrame *d_ps,
-                                     const float *d_state_in, float *d_state_out,
-                                     void *d_pcm, int pcm_format,
-                                     size_t n, void *stream)
+// The HE calls behind their argument checks: n_streams streams of T consecutive frames each.  Whole streams per
+// workspace set (a stream's T frames hand W / X over inside one set); with T = 1 a stream is a frame and the
+// per-frame arrays and the state are exactly the batch call's.
+static int he_walk(HeaacDevice *dev, int cfg, int flags, const float *d_coeffs, const HeaacIcs *d_ics,
+                   const HeaacSbrFrame *d_sbr, const HeaacSbrHeader *d_hdr, size_t n_hdr, const HeaacPsFrame *d_ps,
+                   const float *d_state_in, float *d_state_out, void *d_pcm, int pcm_format,
+                   size_t n_streams, size_t T, hipStream_t s)
 {
-    return heaac_he_decode_batch_ex(dev, cfg, 0, d_coeffs, d_ics, d_sbr, d_hdr, n_hdr, d_ps, d_state_in, d_state_out,
-                                    d_pcm, pcm_format, n, stream);
-}
-
-extern "C" int heaac_he_decode_batch_ex(HeaacDevice *dev, int cfg, int flags,
-                                     const float *d_coeffs, const HeaacIcs *d_ics,
-                                     const HeaacSbrFrame *d_sbr,
-                                     const HeaacSbrHeader *d_hdr, size_t n_hdr,
-                                     const HeaacPsFrame *d_ps,
-                                     const float *d_state_in, float *d_state_out,
-                                     void *d_pcm, int pcm_format,
-                                     size_t n, void *stream)
-{
-    if (!dev || (cfg != HEAAC_CFG_HEV1 && cfg != HEAAC_CFG_HEV1_MONO && cfg != HEAAC_CFG_HEV2) ||
-        (pcm_format != HEAAC_PCM_F32_PLANAR && pcm_format != HEAAC_PCM_S16_INTERLEAVED &&
-         pcm_format != HEAAC_PCM_S16_INTERLEAVED_SSE2) ||
-        (flags & ~HEAAC_HE_DOWNSAMPLED))
-        return HEAAC_ERR_ARG;
-    if (n == 0)
-        return HEAAC_OK;
-    if (!d_coeffs || !d_ics || !d_sbr || !d_hdr || !n_hdr || !d_state_in || !d_state_out || !d_pcm ||
-        (cfg == HEAAC_CFG_HEV2 && !d_ps))
-        return HEAAC_ERR_ARG;
-    const int ncore = cfg == HEAAC_CFG_HEV1 ? 2 : 1;
-    const int nout  = cfg == HEAAC_CFG_HEV1_MONO ? 1 : 2;
-    const size_t words = cfg == HEAAC_CFG_HEV1 ? HEAAC_STATE_WORDS_HEV1 :
-                         cfg == HEAAC_CFG_HEV2 ? HEAAC_STATE_WORDS_HEV2 : HEAAC_STATE_WORDS_HEV1_MONO;
-    const size_t pcm_bytes = (size_t)nout * ((flags & HEAAC_HE_DOWNSAMPLED) ? 1024 : 2048) *
+    const HeaacCfgShape shape = heaac_cfg_shape(cfg);
+    const size_t ncore = shape.ncore, words = shape.words;
+    const size_t pcm_bytes = (size_t)shape.nout * ((flags & HEAAC_HE_DOWNSAMPLED) ? 1024 : 2048) *
                              (pcm_format == HEAAC_PCM_F32_PLANAR ? 4 : 2);
     const size_t set_floats = dev->chunk * (WS_W_FLOATS + WS_X_FLOATS);
-    hipStream_t s = (hipStream_t)stream;
+    const size_t per_chunk = dev->chunk / T;
+    const unsigned hdrs = (unsigned)(n_hdr > 0xffffu ? 0x10000u : n_hdr);
     bool capturing = false;
     const int claim = he_claim(dev, s, &capturing);
     if (claim != HEAAC_OK) return claim;
     // one chunk: everything on the caller's stream; more: fork onto the two lanes and join again
     // (event fork / join, so the call stays capturable into a hipGraph)
-    const bool lanes = n > dev->chunk && dev->sets > 1;
+    const bool lanes = n_streams > per_chunk && dev->sets > 1;
     const int nl = lanes ? dev->sets : 1;
     // (every exit behind he_claim goes through the join and he_release below: a failed fork must not leave the
     // workspace claimed or lanes that were already forked unjoined)
-    int rc = HEAAC_OK;
-    int forked = 0;
-    if (lanes) {
-        if (hipEventRecord(dev->fork, s) != hipSuccess) rc = HEAAC_ERR_HIP;
-        for (int k = 0; k < nl && rc == HEAAC_OK; k++) {
-            if (hipStreamWaitEvent(dev->lane[k], dev->fork, 0) != hipSuccess) rc = HEAAC_ERR_HIP;
-            else forked = k + 1;
-        }
-    }
-    size_t c = 0;
-    for (size_t f0 = 0; f0 < n && rc == HEAAC_OK; f0 += dev->chunk, c++) {
-        const size_t nc = n - f0 < dev->chunk ? n - f0 : dev->chunk;
-        const int k = (int)(c % nl);
-        float *ws_W = (float *)dev->d_work + k * set_floats;
-        float *ws_X = ws_W + dev->chunk * WS_W_FLOATS;
-        rc = heaac_launch_he(dev->d_tab, dev->d_rev, cfg,
-                             d_coeffs + f0 * ncore * 1024, d_ics + f0 * ncore,
-                             d_sbr + f0, d_hdr, (unsigned)(n_hdr > 0xffffu ? 0x10000u : n_hdr), d_ps ? d_ps + f0 : NULL,
-                             d_state_in + f0 * words, d_state_out + f0 * words,
-                             (char *)d_pcm + f0 * pcm_bytes, pcm_format,
-                             ws_W, ws_X, dev->d_queue + 16 * k,
-                             dev->d_aux + HE_ZERO_BYTES + 2 * (size_t)k * dev->chunk, (const float *)dev->d_aux,
-                             nc, 0, flags, lanes ? dev->lane[k] : s);
-    }
-    if (lanes) {
-        // always rejoin, also after a failed launch (a capture must not be left forked)
-        for (int k = 0; k < forked; k++)
-            if (hipEventRecord(dev->join[k], dev->lane[k]) != hipSuccess ||
-                hipStreamWaitEvent(s, dev->join[k], 0) != hipSuccess)
-                rc = rc == HEAAC_OK ? HEAAC_ERR_HIP : rc;
-    }
-    return he_release(dev, s, capturing, rc);
-}
-
-extern "C" int heaac_he_decode_streams(HeaacDevice *dev, int cfg, int flags,
-                                       const float *d_coeffs, const HeaacIcs *d_ics,
-                                       const HeaacSbrFrame *d_sbr,
-                                       const HeaacSbrHeader *d_hdr, size_t n_hdr,
-                                       const HeaacPsFrame *d_ps,
-                                       const float *d_state_in, float *d_state_out,
-                                       void *d_pcm, int pcm_format,
-                                       size_t n_streams, size_t frames_per_stream, void *stream)
-{
-    if (!dev || (cfg != HEAAC_CFG_HEV1 && cfg != HEAAC_CFG_HEV1_MONO && cfg != HEAAC_CFG_HEV2) ||
-        (pcm_format != HEAAC_PCM_F32_PLANAR && pcm_format != HEAAC_PCM_S16_INTERLEAVED &&
-         pcm_format != HEAAC_PCM_S16_INTERLEAVED_SSE2) ||
-        (flags & ~HEAAC_HE_DOWNSAMPLED) || frames_per_stream == 0 || frames_per_stream > dev->chunk)
-        return HEAAC_ERR_ARG;
-    if (n_streams == 0)
-        return HEAAC_OK;
-    if (!d_coeffs || !d_ics || !d_sbr || !d_hdr || !n_hdr || !d_state_in || !d_state_out || !d_pcm ||
-        (cfg == HEAAC_CFG_HEV2 && !d_ps))
-        return HEAAC_ERR_ARG;
-    const size_t T = frames_per_stream;
-    // one frame per stream: the per-frame arrays and the state are exactly the batch call's
-    if (T == 1)
-        return heaac_he_decode_batch_ex(dev, cfg, flags, d_coeffs, d_ics, d_sbr, d_hdr, n_hdr, d_ps, d_state_in,
-                                        d_state_out, d_pcm, pcm_format, n_streams, stream);
-    const int ncore = cfg == HEAAC_CFG_HEV1 ? 2 : 1;
-    const int nout  = cfg == HEAAC_CFG_HEV1_MONO ? 1 : 2;
-    const size_t words = cfg == HEAAC_CFG_HEV1 ? HEAAC_STATE_WORDS_HEV1 :
-                         cfg == HEAAC_CFG_HEV2 ? HEAAC_STATE_WORDS_HEV2 : HEAAC_STATE_WORDS_HEV1_MONO;
-    const size_t pcm_bytes = (size_t)nout * ((flags & HEAAC_HE_DOWNSAMPLED) ? 1024 : 2048) *
-                             (pcm_format == HEAAC_PCM_F32_PLANAR ? 4 : 2);
-    const size_t set_floats = dev->chunk * (WS_W_FLOATS + WS_X_FLOATS);
-    // whole streams per workspace set: a stream's T frames hand W / X over inside one set
-    const size_t per_chunk = dev->chunk / T;
-    hipStream_t s = (hipStream_t)stream;
-    bool capturing = false;
-    const int claim = he_claim(dev, s, &capturing);
-    if (claim != HEAAC_OK) return claim;
-    // as heaac_he_decode_batch_ex: one chunk on the caller's stream, more alternate between the lanes
-    const bool lanes = n_streams > per_chunk && dev->sets > 1;
-    const int nl = lanes ? dev->sets : 1;
     int rc = HEAAC_OK;
     int forked = 0;
     if (lanes) {
@@ -465,23 +360,82 @@ extern "C" int heaac_he_decode_streams(HeaacDevice *dev, int cfg, int flags,
         const int k = (int)(c % nl);
         float *ws_W = (float *)dev->d_work + k * set_floats;
         float *ws_X = ws_W + dev->chunk * WS_W_FLOATS;
-        rc = heaac_launch_he_streams(dev->d_tab, dev->d_rev, cfg,
-                                     d_coeffs + f0 * ncore * 1024, d_ics + f0 * ncore,
-                                     d_sbr + f0, d_hdr, (unsigned)(n_hdr > 0xffffu ? 0x10000u : n_hdr),
-                                     d_ps ? d_ps + f0 : NULL,
-                                     d_state_in + s0 * words, d_state_out + s0 * words,
-                                     (char *)d_pcm + f0 * pcm_bytes, pcm_format,
-                                     ws_W, ws_X, dev->d_queue + 16 * k,
-                                     dev->d_aux + HE_ZERO_BYTES + 2 * (size_t)k * dev->chunk, (const float *)dev->d_aux,
-                                     ns, T, flags, lanes ? dev->lane[k] : s);
+        unsigned char *xtop = dev->d_aux + HE_ZERO_BYTES + 2 * (size_t)k * dev->chunk;
+        hipStream_t ls = lanes ? dev->lane[k] : s;
+        rc = T == 1
+            ? heaac_launch_he(dev->d_tab, dev->d_rev, cfg, d_coeffs + f0 * ncore * 1024, d_ics + f0 * ncore,
+                              d_sbr + f0, d_hdr, hdrs, d_ps ? d_ps + f0 : NULL,
+                              d_state_in + s0 * words, d_state_out + s0 * words,
+                              (char *)d_pcm + f0 * pcm_bytes, pcm_format, ws_W, ws_X, dev->d_queue + 16 * k,
+                              xtop, (const float *)dev->d_aux, ns, 0, flags, ls)
+            : heaac_launch_he_streams(dev->d_tab, dev->d_rev, cfg, d_coeffs + f0 * ncore * 1024, d_ics + f0 * ncore,
+                                      d_sbr + f0, d_hdr, hdrs, d_ps ? d_ps + f0 : NULL,
+                                      d_state_in + s0 * words, d_state_out + s0 * words,
+                                      (char *)d_pcm + f0 * pcm_bytes, pcm_format, ws_W, ws_X, dev->d_queue + 16 * k,
+                                      xtop, (const float *)dev->d_aux, ns, T, flags, ls);
     }
     if (lanes) {
+        // always rejoin, also after a failed launch (a capture must not be left forked)
         for (int k = 0; k < forked; k++)
             if (hipEventRecord(dev->join[k], dev->lane[k]) != hipSuccess ||
                 hipStreamWaitEvent(s, dev->join[k], 0) != hipSuccess)
                 rc = rc == HEAAC_OK ? HEAAC_ERR_HIP : rc;
     }
     return he_release(dev, s, capturing, rc);
+}
+
+extern "C" int heaac_he_decode_batch_ex(HeaacDevice *dev, int cfg, int flags,
+                                     const float *d_coeffs, const HeaacIcs *d_ics,
+                                     const HeaacSbrFrame *d_sbr,
+                                     const HeaacSbrHeader *d_hdr, size_t n_hdr,
+                                     const HeaacPsFrame *d_ps,
+                                     const float *d_state_in, float *d_state_out,
+                                     void *d_pcm, int pcm_format,
+                                     size_t n, void *stream)
+{
+    if (!dev || !he_cfg_ok(cfg) || !pcm_format_ok(pcm_format) || (flags & ~HEAAC_HE_DOWNSAMPLED))
+        return HEAAC_ERR_ARG;
+    if (n == 0)
+        return HEAAC_OK;
+    if (!d_coeffs || !d_ics || !d_sbr || !d_hdr || !n_hdr || !d_state_in || !d_state_out || !d_pcm ||
+        (cfg == HEAAC_CFG_HEV2 && !d_ps))
+        return HEAAC_ERR_ARG;
+    return he_walk(dev, cfg, flags, d_coeffs, d_ics, d_sbr, d_hdr, n_hdr, d_ps, d_state_in, d_state_out, d_pcm,
+                   pcm_format, n, 1, (hipStream_t)stream);
+}
+
+extern "C" int heaac_he_decode_batch(HeaacDevice *dev, int cfg,
+                                     const float *d_coeffs, const HeaacIcs *d_ics,
+                                     const HeaacSbrFrame *d_sbr,
+                                     const HeaacSbrHeader *d_hdr, size_t n_hdr,
+                                     const HeaacPsFrame *d_ps,
+                                     const float *d_state_in, float *d_state_out,
+                                     void *d_pcm, int pcm_format,
+                                     size_t n, void *stream)
+{
+    return heaac_he_decode_batch_ex(dev, cfg, 0, d_coeffs, d_ics, d_sbr, d_hdr, n_hdr, d_ps, d_state_in, d_state_out,
+                                    d_pcm, pcm_format, n, stream);
+}
+
+extern "C" int heaac_he_decode_streams(HeaacDevice *dev, int cfg, int flags,
+                                       const float *d_coeffs, const HeaacIcs *d_ics,
+                                       const HeaacSbrFrame *d_sbr,
+                                       const HeaacSbrHeader *d_hdr, size_t n_hdr,
+                                       const HeaacPsFrame *d_ps,
+                                       const float *d_state_in, float *d_state_out,
+                                       void *d_pcm, int pcm_format,
+                                       size_t n_streams, size_t frames_per_stream, void *stream)
+{
+    if (!dev || !he_cfg_ok(cfg) || !pcm_format_ok(pcm_format) || (flags & ~HEAAC_HE_DOWNSAMPLED) ||
+        frames_per_stream == 0 || frames_per_stream > dev->chunk)
+        return HEAAC_ERR_ARG;
+    if (n_streams == 0)
+        return HEAAC_OK;
+    if (!d_coeffs || !d_ics || !d_sbr || !d_hdr || !n_hdr || !d_state_in || !d_state_out || !d_pcm ||
+        (cfg == HEAAC_CFG_HEV2 && !d_ps))
+        return HEAAC_ERR_ARG;
+    return he_walk(dev, cfg, flags, d_coeffs, d_ics, d_sbr, d_hdr, n_hdr, d_ps, d_state_in, d_state_out, d_pcm,
+                   pcm_format, n_streams, frames_per_stream, (hipStream_t)stream);
 }
 
 extern "C" int heaac_qmf_analysis_batch(HeaacDevice *dev, const float *d_in,

@@ -21,10 +21,11 @@
 #include <stdlib.h>
 #include <string.h>
 #include "codec_layout.h"
+#include "host_common.h"
 
 #define LAY_MAX_HDRS 64
 #define CCE_STATE_WORDS HEAAC_STATE_WORDS_HEV1_MONO
-#define LAY_STATE_WORDS (HEAAC_STATE_WORDS_HEV2 > HEAAC_STATE_WORDS_HEV1 ? HEAAC_STATE_WORDS_HEV2 : HEAAC_STATE_WORDS_HEV1)
+#define LAY_STATE_WORDS HEAAC_STATE_WORDS_MAX
 
 struct LayElem {
     int cfg_lc, cfg_he, channels;
@@ -100,7 +101,7 @@ static void coupled_free(LayCoupled *c)
     free(c);
 }
 
-static LayCoupled *coupled_alloc(const HeaacPredictorState *ps_reset)
+static LayCoupled *coupled_alloc(void)
 {
     LayCoupled *c = (LayCoupled *)calloc(1, sizeof(*c));
     if (!c) return NULL;
@@ -110,15 +111,13 @@ static LayCoupled *coupled_alloc(const HeaacPredictorState *ps_reset)
         hipMalloc((void **)&c->d_ics, sizeof(c->h_ics)) == hipSuccess &&
         hipMalloc((void **)&c->d_tools, sizeof(c->h_tools)) == hipSuccess &&
         hipMalloc((void **)&c->d_state, HEAAC_MAX_CCE * CCE_STATE_WORDS * 4) == hipSuccess &&
-        hipMalloc((void **)&c->d_pred, HEAAC_MAX_CCE * HEAAC_MAX_PREDICTORS * sizeof(*ps_reset)) == hipSuccess &&
+        hipMalloc((void **)&c->d_pred, HEAAC_MAX_CCE * HEAAC_MAX_PREDICTORS * sizeof(HeaacPredictorState)) == hipSuccess &&
         hipMalloc((void **)&c->d_ret, HEAAC_MAX_CCE * 2048 * 4) == hipSuccess &&
         hipMalloc((void **)&c->d_gain, 2 * sizeof(HeaacCoupling)) == hipSuccess &&
         hipMalloc((void **)&c->d_sbr, HEAAC_MAX_CCE * sizeof(HeaacSbrFrame)) == hipSuccess &&
-        hipMemset(c->d_state, 0, HEAAC_MAX_CCE * CCE_STATE_WORDS * 4) == hipSuccess;
+        hipMemset(c->d_state, 0, HEAAC_MAX_CCE * CCE_STATE_WORDS * 4) == hipSuccess &&
+        heaac_reset_predictors(c->d_pred, HEAAC_MAX_CCE * HEAAC_MAX_PREDICTORS);
     heaac_sbr_stream_init(c->sst, HEAAC_MAX_CCE);
-    for (int k = 0; ok && k < HEAAC_MAX_CCE; k++)
-        ok = hipMemcpy(c->d_pred + k * HEAAC_MAX_PREDICTORS, ps_reset, HEAAC_MAX_PREDICTORS * sizeof(*ps_reset),
-                       hipMemcpyHostToDevice) == hipSuccess;
     if (!ok) { coupled_free(c); return NULL; }
     return c;
 }
@@ -176,9 +175,7 @@ HeaacLayoutDec *heaac_layout_dec_create(HeaacDevice *dev, const HeaacAacConfig *
     d->tab = heaac_sbr_table_create(LAY_MAX_HDRS);
     d->h_coeffs = (float *)calloc((size_t)d->n * 2048, sizeof(float));
     d->h_tools = (HeaacToolsFrame *)calloc(d->n, sizeof(HeaacToolsFrame));
-    HeaacPredictorState *ps = (HeaacPredictorState *)calloc(2 * HEAAC_MAX_PREDICTORS, sizeof(*ps));
-    bool ok = d->tab && d->h_coeffs && d->h_tools && ps;
-    if (ok) for (int i = 0; i < 2 * HEAAC_MAX_PREDICTORS; i++) ps[i].var0 = ps[i].var1 = 1.0f;   // reset_predict_state, :507-515
+    bool ok = d->tab && d->h_coeffs && d->h_tools;
     for (int i = 0; ok && i < d->n; i++) {
         LayElem &e = d->e[i];
         e.channels = layout->elem[i].channels;
@@ -193,22 +190,20 @@ HeaacLayoutDec *heaac_layout_dec_create(HeaacDevice *dev, const HeaacAacConfig *
              hipMalloc((void **)&e.d_tools, sizeof(HeaacToolsFrame)) == hipSuccess &&
              hipMalloc((void **)&e.d_state, LAY_STATE_WORDS * 4) == hipSuccess &&
              hipMalloc((void **)&e.d_ps, sizeof(HeaacPsFrame)) == hipSuccess &&
-             hipMalloc((void **)&e.d_pred, 2 * HEAAC_MAX_PREDICTORS * sizeof(*ps)) == hipSuccess &&
+             hipMalloc((void **)&e.d_pred, 2 * HEAAC_MAX_PREDICTORS * sizeof(HeaacPredictorState)) == hipSuccess &&
              hipMalloc((void **)&e.d_sbr, sizeof(HeaacSbrFrame)) == hipSuccess &&
              hipMalloc((void **)&e.d_f32, 2 * 2048 * 4) == hipSuccess &&
              hipMemset(e.d_state, 0, LAY_STATE_WORDS * 4) == hipSuccess &&
-             hipMemcpy(e.d_pred, ps, 2 * HEAAC_MAX_PREDICTORS * sizeof(*ps), hipMemcpyHostToDevice) == hipSuccess;
+             heaac_reset_predictors(e.d_pred, 2 * HEAAC_MAX_PREDICTORS);
     }
     for (int id = 0; ok && id < 16; id++)
-        if (layout->slot_of[HEAAC_ELEM_CCE][id] && !d->cpl) ok = (d->cpl = coupled_alloc(ps)) != NULL;
-    free(ps);
-    const int32_t seed = 0x1f2e3d4c;                                   // ac->random_state, aacdec.c:558
+        if (layout->slot_of[HEAAC_ELEM_CCE][id] && !d->cpl) ok = (d->cpl = coupled_alloc()) != NULL;
     for (int i = 0; i < LAY_MAX_HDRS; i++) d->hdr[i].kx = 32;          // kx' = 32, m = 0 (aacsbr.c:130)
     ok = ok && hipMalloc((void **)&d->d_hdr, sizeof(d->hdr)) == hipSuccess &&
          hipMalloc((void **)&d->d_rng, 4) == hipSuccess &&
          hipMalloc((void **)&d->d_pcm, (size_t)most_outs * 2048 * 2) == hipSuccess &&
          hipMemcpy(d->d_hdr, d->hdr, sizeof(d->hdr), hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemcpy(d->d_rng, &seed, 4, hipMemcpyHostToDevice) == hipSuccess;
+         heaac_seed_generators(d->d_rng, 1);
     if (!ok) { heaac_layout_dec_destroy(d); return NULL; }
     return d;
 }
@@ -305,18 +300,7 @@ int heaac_layout_dec_frame(HeaacLayoutDec *d, const uint8_t *buf, int size, void
          hipMemcpy(c->d_tools, c->h_tools, sizeof(c->h_tools), hipMemcpyHostToDevice) != hipSuccess))
         return -1;
     // header records the SBR readers have added to the table since the last upload
-    auto sync_headers = [&]() -> int {
-        const size_t have = heaac_sbr_table_count(d->tab);
-        if (have > d->hdr_uploaded) {
-            memcpy(d->hdr + d->hdr_uploaded, heaac_sbr_table_data(d->tab) + d->hdr_uploaded,
-                   (have - d->hdr_uploaded) * sizeof(HeaacSbrHeader));
-            if (hipMemcpy(d->d_hdr + d->hdr_uploaded, d->hdr + d->hdr_uploaded,
-                          (have - d->hdr_uploaded) * sizeof(HeaacSbrHeader), hipMemcpyHostToDevice) != hipSuccess)
-                return -1;
-            d->hdr_uploaded = have;
-        }
-        return 0;
-    };
+    auto sync_headers = [&]() -> int { return heaac_upload_headers(d->tab, &d->hdr_uploaded, d->d_hdr, d->hdr, NULL); };
     // A coupling element's tools as a whole at its place in the stream (nothing couples INTO it); an output element's
     // first half there, its second half -- coupling, TNS, coupling -- once every coupling element is through.
     auto cce_tools = [&](int outputs_before) -> int {

@@ -1,7 +1,7 @@
 // pipeline.hip -- include/heaac_pipeline.h: access units in host memory -> int16 PCM in host memory, the four
 // stages of consecutive ticks overlapped (host parse || H2D || GPU || D2H).
 //
-//   host parse   persistent pool: worker w owns the streams [n w / W, n (w + 1) / W) (their parser state too)
+//   host parse   the worker pool of host_common.h, one slice of the streams per thread
 //   H2D          stream `in`:  parsed records of the tick's buffer set, pinned -> device
 //   GPU          stream `run`: heaac_spectral_tools_batch + heaac_he_decode_batch, DSP state in place
 //   D2H          stream `out`: int16 PCM of the tick's buffer set, device -> pinned
@@ -10,14 +10,12 @@
 // Event order per set s:  in waits run_done[s] of the tick that used s last (its inputs are free again); run waits
 // in_done[s] and that tick's out_done[s] (its PCM buffer is free); out waits run_done[s].
 #include <hip/hip_runtime.h>
-#include <pthread.h>
-#include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 #include <time.h>
-#include <unistd.h>
 #include "heaac_pipeline.h"
 #include "codec_layout.h"        // heaac_sbr_output_mode
+#include "host_common.h"
 
 #define PL_MAX_HDRS 4096
 #define PL_DEPTH HEAAC_PIPELINE_DEPTH
@@ -34,21 +32,6 @@ struct Set {
                                     // the spectral tools still have to move its noise generator / predictors
     unsigned *h_list, *d_list;      // [2 n] (stream, parking row) pairs of the failed streams, pinned / device
 };
-
-// Rows of the failed streams to the parking area and back (or zeroed): one block per listed stream.  A tick with
-// thousands of damaged units costs a handful of launches, not six copies per stream (tools/damage_rate.py).
-//   mode 0: park[row] = rows[stream];  1: rows[stream] = park[row];  2: rows[stream] = 0
-__global__ void k_rows(const unsigned *__restrict__ list, unsigned *rows, unsigned *park, unsigned long long row_words, int mode)
-{
-    const unsigned stream = list[2 * blockIdx.x], slot = list[2 * blockIdx.x + 1];
-    unsigned *r = rows + stream * row_words;
-    unsigned *q = park ? park + slot * row_words : nullptr;
-    for (unsigned long long w = threadIdx.x; w < row_words; w += blockDim.x) {
-        if (mode == 0) q[w] = r[w];
-        else if (mode == 1) r[w] = q[w];
-        else r[w] = 0u;
-    }
-}
 
 struct HeaacPipeline {
     HeaacAacConfig aac;
@@ -69,19 +52,12 @@ struct HeaacPipeline {
     HeaacSbrStream *sst_tmp;      // HE: [threads] scratch SBR reader states, one per parse slice
     unsigned long submitted, collected;
     float last_ms[4];
-    // pool
-    int threads;
-    pthread_t *tid;
-    pthread_mutex_t mu;
-    pthread_cond_t cv_go, cv_done;
-    unsigned long generation;
-    int pending, quit;
+    HeaacPool *pool; int threads;   // threads: the pool's, the slices of a tick
     const uint8_t *const *job_au; const int *job_size; int *job_status; Set *job_set;
 };
 
-struct WorkerArg { HeaacPipeline *p; int w; };
-
-static void parse_slice(HeaacPipeline *p, int w)
+// (out of line under this name: tests/test_pipeline.py looks the per-stream loop up in the library)
+__attribute__((noinline)) static void parse_slice(HeaacPipeline *p, int w)
 {
     const size_t lo = p->n * (size_t)w / (size_t)p->threads, hi = p->n * (size_t)(w + 1) / (size_t)p->threads;
     Set *s = p->job_set;
@@ -127,62 +103,12 @@ static void parse_slice(HeaacPipeline *p, int w)
     }
 }
 
-static void *worker(void *arg)
-{
-    WorkerArg *a = (WorkerArg *)arg;
-    HeaacPipeline *p = a->p;
-    const int w = a->w;
-    free(a);
-    unsigned long seen = 0;
-    pthread_mutex_lock(&p->mu);
-    for (;;) {
-        while (p->generation == seen && !p->quit) pthread_cond_wait(&p->cv_go, &p->mu);
-        if (p->quit) break;
-        seen = p->generation;
-        pthread_mutex_unlock(&p->mu);
-        parse_slice(p, w);
-        pthread_mutex_lock(&p->mu);
-        if (--p->pending == 0) pthread_cond_signal(&p->cv_done);
-    }
-    pthread_mutex_unlock(&p->mu);
-    return NULL;
-}
-
-// Parser threads when the caller does not say: the CPUs this process may actually use.  Inside a container the CPU
-// bandwidth quota (cgroup v2 cpu.max) can be far below the online count; threads beyond about twice the quota only
-// get throttled (measured on the GPU box: 256 online, quota 16: 32 threads parse a tick in 6 ms, 256 in 18 ms
-// once the copy engines' helper threads compete).
-static int default_threads(void)
-{
-    long online = sysconf(_SC_NPROCESSORS_ONLN);
-    if (online < 1) online = 1;
-    FILE *f = fopen("/sys/fs/cgroup/cpu.max", "r");
-    if (f) {
-        long long quota = 0, period = 0;
-        if (fscanf(f, "%lld %lld", &quota, &period) == 2 && quota > 0 && period > 0) {
-            const long cap = (long)((2 * quota + period - 1) / period);
-            if (cap >= 1 && cap < online) online = cap;
-        }
-        fclose(f);
-    }
-    return (int)online;
-}
-
-static int pinned(void **p, size_t bytes) { return hipHostMalloc(p, bytes, hipHostMallocDefault) == hipSuccess; }
-static int devmem(void **p, size_t bytes) { return hipMalloc(p, bytes) == hipSuccess; }
+static void pl_slice(void *ctx, int w, int) { parse_slice((HeaacPipeline *)ctx, w); }
 
 extern "C" void heaac_pipeline_destroy(HeaacPipeline *p)
 {
     if (!p) return;
-    if (p->tid) {
-        pthread_mutex_lock(&p->mu);
-        p->quit = 1;
-        pthread_cond_broadcast(&p->cv_go);
-        pthread_mutex_unlock(&p->mu);
-        for (int t = 1; t < p->threads; t++) if (p->tid[t]) pthread_join(p->tid[t], NULL);
-        free(p->tid);
-        pthread_cond_destroy(&p->cv_go); pthread_cond_destroy(&p->cv_done); pthread_mutex_destroy(&p->mu);
-    }
+    heaac_pool_destroy(p->pool);
     if (p->in) (void)hipStreamSynchronize(p->in);
     if (p->run) (void)hipStreamSynchronize(p->run);
     if (p->out) (void)hipStreamSynchronize(p->out);
@@ -230,11 +156,8 @@ extern "C" int heaac_pipeline_create(HeaacPipeline **out, const HeaacAacConfig *
     if (mode < 0) { free(p); return HEAAC_ERR_ARG; }
     p->downsampled = mode;
     p->out_len = lc || mode ? 1024 : 2048;
-    p->ncore = (he_cfg == HEAAC_CFG_HEV1 || he_cfg == HEAAC_CFG_LC_STEREO) ? 2 : 1;
-    p->nout = (he_cfg == HEAAC_CFG_HEV1_MONO || he_cfg == HEAAC_CFG_LC_MONO) ? 1 : 2;
-    p->words = he_cfg == HEAAC_CFG_HEV1 ? HEAAC_STATE_WORDS_HEV1 : he_cfg == HEAAC_CFG_HEV2 ? HEAAC_STATE_WORDS_HEV2 :
-               he_cfg == HEAAC_CFG_HEV1_MONO ? HEAAC_STATE_WORDS_HEV1_MONO :
-               he_cfg == HEAAC_CFG_LC_STEREO ? HEAAC_STATE_WORDS_LC_STEREO : HEAAC_STATE_WORDS_LC_MONO;
+    const HeaacCfgShape shape = heaac_cfg_shape(he_cfg);
+    p->ncore = shape.ncore; p->nout = shape.nout; p->words = shape.words;
     p->n = n;
     int rc = heaac_device_create(&p->dev, n);
     if (rc != HEAAC_OK) { free(p); return rc; }
@@ -271,25 +194,11 @@ extern "C" int heaac_pipeline_create(HeaacPipeline **out, const HeaacAacConfig *
          devmem((void **)&p->d_hdr, PL_MAX_HDRS * sizeof(HeaacSbrHeader)) &&
          hipMemset(p->d_state, 0, n * p->words * 4) == hipSuccess;
     if (ok && aac->object_type == HEAAC_AOT_AAC_MAIN) {
-        // reset_predict_state (aacdec.c:507-515) for every predictor of every channel
+        // every predictor of every channel
         const size_t np = n * (size_t)p->ncore * HEAAC_MAX_PREDICTORS;
-        HeaacPredictorState *ps = (HeaacPredictorState *)calloc(np, sizeof(*ps));
-        ok = ps != NULL && devmem((void **)&p->d_pred, np * sizeof(*ps));
-        if (ok) {
-            for (size_t i = 0; i < np; i++) ps[i].var0 = ps[i].var1 = 1.0f;
-            ok = hipMemcpy(p->d_pred, ps, np * sizeof(*ps), hipMemcpyHostToDevice) == hipSuccess;
-        }
-        free(ps);
+        ok = devmem((void **)&p->d_pred, np * sizeof(HeaacPredictorState)) && heaac_reset_predictors(p->d_pred, np);
     }
-    if (ok) {
-        int32_t *seed = (int32_t *)malloc(n * 4);
-        ok = seed != NULL;
-        if (ok) {
-            for (size_t i = 0; i < n; i++) seed[i] = 0x1f2e3d4c;       // ac->random_state, aacdec.c:558
-            ok = hipMemcpy(p->d_rng, seed, n * 4, hipMemcpyHostToDevice) == hipSuccess;
-            free(seed);
-        }
-    }
+    ok = ok && heaac_seed_generators(p->d_rng, n);
     p->tab = heaac_sbr_table_create(PL_MAX_HDRS);
     p->ast = (HeaacAacStream *)calloc(n, sizeof(HeaacAacStream));
     p->sst = (HeaacSbrStream *)malloc(n * heaac_sbr_stream_bytes());
@@ -301,22 +210,13 @@ extern "C" int heaac_pipeline_create(HeaacPipeline **out, const HeaacAacConfig *
         p->hdr_uploaded = 1;
     }
     if (ok) {
-        if (threads <= 0) threads = default_threads();
+        if (threads <= 0) threads = heaac_threads_by_cpu_quota();
         if (threads < 1) threads = 1;
         if (threads > 256) threads = 256;
         if ((size_t)threads > n) threads = (int)n;
-        p->threads = threads;
-        pthread_mutex_init(&p->mu, NULL);
-        pthread_cond_init(&p->cv_go, NULL);
-        pthread_cond_init(&p->cv_done, NULL);
-        p->tid = (pthread_t *)calloc(threads, sizeof(pthread_t));
-        ok = p->tid != NULL && (!p->he || (p->sst_tmp = (HeaacSbrStream *)malloc(threads * heaac_sbr_stream_bytes())) != NULL);
-        for (int t = 1; t < threads && ok; t++) {          // slice 0 is parsed by the submitting thread
-            WorkerArg *a = (WorkerArg *)malloc(sizeof(*a));
-            if (!a) { ok = false; break; }
-            a->p = p; a->w = t;
-            if (pthread_create(&p->tid[t], NULL, worker, a) != 0) { free(a); p->tid[t] = 0; p->threads = t; break; }
-        }
+        ok = (p->pool = heaac_pool_create(threads, pl_slice, p)) != NULL;
+        if (ok) p->threads = heaac_pool_threads(p->pool);
+        ok = ok && (!p->he || (p->sst_tmp = (HeaacSbrStream *)malloc(p->threads * heaac_sbr_stream_bytes())) != NULL);
     }
     if (!ok) { heaac_pipeline_destroy(p); return HEAAC_ERR_NOMEM; }
     *out = p;
@@ -330,7 +230,21 @@ static double now_ms(void)
     return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6;
 }
 
-#define HIP_OK(x) do { if ((x) != hipSuccess) return HEAAC_ERR_HIP; } while (0)
+static size_t pl_pred_row_bytes(const HeaacPipeline *p)
+{
+    return (size_t)p->ncore * HEAAC_MAX_PREDICTORS * sizeof(HeaacPredictorState);
+}
+
+// The state rows of every failed stream, the generator and predictor rows of those that keep them too (the set's
+// two lists, heaac_failed_lists): to the parking area (mode 0) or back (1)
+static void pl_park(HeaacPipeline *p, const Set *s, unsigned n_all, unsigned n_full, int mode)
+{
+    const unsigned *full = s->d_list + 2 * p->n;
+    heaac_rows(p->run, s->d_list, n_all, 256, p->d_state, p->d_park_state, p->words, mode);
+    if (!n_full) return;
+    heaac_rows(p->run, full, n_full, 64, p->d_rng, p->d_park_rng, 1, mode);
+    if (p->d_pred) heaac_rows(p->run, full, n_full, 256, p->d_pred, p->d_park_pred, pl_pred_row_bytes(p) / 4, mode);
+}
 
 extern "C" int heaac_pipeline_submit(HeaacPipeline *p, const uint8_t *const *au, const int *size, int *status)
 {
@@ -340,30 +254,18 @@ extern "C" int heaac_pipeline_submit(HeaacPipeline *p, const uint8_t *const *au,
     // the pinned inputs of this set are free once the H2D of the tick that used it last has finished
     if (s->used) HIP_OK(hipEventSynchronize(s->in_done));
     const double t0 = now_ms();
-    pthread_mutex_lock(&p->mu);
     p->job_au = au; p->job_size = size; p->job_status = status; p->job_set = s;
-    p->pending = p->threads - 1;
-    p->generation++;
-    pthread_cond_broadcast(&p->cv_go);
-    pthread_mutex_unlock(&p->mu);
-    parse_slice(p, 0);
-    pthread_mutex_lock(&p->mu);
-    while (p->pending > 0) pthread_cond_wait(&p->cv_done, &p->mu);
-    pthread_mutex_unlock(&p->mu);
+    heaac_pool_run(p->pool, 0);
     s->parse_ms = (float)(now_ms() - t0);
 
     const size_t n = p->n, nc = n * (size_t)p->ncore;
     // new SBR headers of this tick (the table's storage never moves)
-    const size_t have = heaac_sbr_table_count(p->tab);
-    if (have > PL_MAX_HDRS) return HEAAC_ERR_ARG;
+    if (heaac_sbr_table_count(p->tab) > PL_MAX_HDRS) return HEAAC_ERR_ARG;
     // H2D
     if (s->used) HIP_OK(hipStreamWaitEvent(p->in, s->run_done, 0));
     HIP_OK(hipEventRecord(s->in_start, p->in));
-    if (have > p->hdr_uploaded) {
-        HIP_OK(hipMemcpyAsync(p->d_hdr + p->hdr_uploaded, heaac_sbr_table_data(p->tab) + p->hdr_uploaded,
-                              (have - p->hdr_uploaded) * sizeof(HeaacSbrHeader), hipMemcpyHostToDevice, p->in));
-        p->hdr_uploaded = have;
-    }
+    int rc = heaac_upload_headers(p->tab, &p->hdr_uploaded, p->d_hdr, NULL, p->in);
+    if (rc != HEAAC_OK) return rc;
     HIP_OK(hipMemcpyAsync(s->d_coeffs, s->h_coeffs, nc * 4096, hipMemcpyHostToDevice, p->in));
     HIP_OK(hipMemcpyAsync(s->d_ics, s->h_ics, nc * sizeof(HeaacIcs), hipMemcpyHostToDevice, p->in));
     if (p->ncore == 1) {
@@ -381,49 +283,28 @@ extern "C" int heaac_pipeline_submit(HeaacPipeline *p, const uint8_t *const *au,
     HIP_OK(hipStreamWaitEvent(p->run, s->in_done, 0));
     if (s->used) HIP_OK(hipStreamWaitEvent(p->run, s->out_done, 0));
     // streams whose unit failed: park their state rows (state, noise generator, predictors) before the launches ...
-    size_t n_failed = 0;
-    for (size_t i = 0; i < n; i++) n_failed += s->failed[i] != 0;
-    const size_t pred_row = (size_t)p->ncore * HEAAC_MAX_PREDICTORS;
-    if (n_failed > p->park_rows) {
-        // (grown outside the streams' order: nothing of the old area is in flight once `run` has drained)
-        HIP_OK(hipStreamSynchronize(p->run));
+    unsigned n_all = 0, n_full = 0;
+    rc = heaac_failed_lists(p->run, s->failed, n, s->h_list, s->d_list, &n_all, &n_full);
+    if (rc != HEAAC_OK) return rc;
+    size_t rows;
+    rc = heaac_park_grow(p->run, n_all, p->park_rows, 64, n, &rows);
+    if (rc != HEAAC_OK) return rc;
+    if (rows != p->park_rows) {
         if (p->d_park_state) (void)hipFree(p->d_park_state);
         if (p->d_park_rng) (void)hipFree(p->d_park_rng);
         if (p->d_park_pred) (void)hipFree(p->d_park_pred);
         p->d_park_state = NULL; p->d_park_rng = NULL; p->d_park_pred = NULL; p->park_rows = 0;
-        size_t rows = 64;
-        while (rows < n_failed) rows *= 2;
-        if (rows > n) rows = n;
         if (!devmem((void **)&p->d_park_state, rows * p->words * 4) || !devmem((void **)&p->d_park_rng, rows * 4) ||
-            (p->d_pred && !devmem((void **)&p->d_park_pred, rows * pred_row * sizeof(HeaacPredictorState))))
+            (p->d_pred && !devmem((void **)&p->d_park_pred, rows * pl_pred_row_bytes(p))))
             return HEAAC_ERR_NOMEM;
         p->park_rows = rows;
     }
-    // two lists of (stream, parking row): every failed stream (its DSP state, its PCM row), and those of them whose
-    // generator and predictors stay put as well (failed == 1; 2: the tools' side of the stream moves on)
-    unsigned n_all = 0, n_full = 0;
-    unsigned *list_all = s->h_list, *list_full = s->h_list + 2 * n;
-    if (n_failed) {
-        for (size_t i = 0; i < n; i++) {
-            if (!s->failed[i]) continue;
-            if (s->failed[i] == 1) { list_full[2 * n_full] = (unsigned)i; list_full[2 * n_full + 1] = n_all; n_full++; }
-            list_all[2 * n_all] = (unsigned)i; list_all[2 * n_all + 1] = n_all; n_all++;
-        }
-        HIP_OK(hipMemcpyAsync(s->d_list, list_all, 2 * n_all * sizeof(unsigned), hipMemcpyHostToDevice, p->run));
-        if (n_full)
-            HIP_OK(hipMemcpyAsync(s->d_list + 2 * n, list_full, 2 * n_full * sizeof(unsigned), hipMemcpyHostToDevice, p->run));
-        hipLaunchKernelGGL(k_rows, dim3(n_all), dim3(256), 0, p->run, s->d_list, (unsigned *)p->d_state, (unsigned *)p->d_park_state,
-                           (unsigned long long)p->words, 0);
-        if (n_full) {
-            hipLaunchKernelGGL(k_rows, dim3(n_full), dim3(64), 0, p->run, s->d_list + 2 * n, (unsigned *)p->d_rng, (unsigned *)p->d_park_rng, 1ull, 0);
-            if (p->d_pred)
-                hipLaunchKernelGGL(k_rows, dim3(n_full), dim3(256), 0, p->run, s->d_list + 2 * n, (unsigned *)p->d_pred, (unsigned *)p->d_park_pred,
-                                   (unsigned long long)(pred_row * sizeof(HeaacPredictorState) / 4), 0);
-        }
+    if (n_all) {
+        pl_park(p, s, n_all, n_full, 0);
         HIP_OK(hipGetLastError());
     }
-    int rc = heaac_spectral_tools_batch(p->dev, p->ncore, s->d_coeffs, s->d_tools, p->d_rng, p->d_rng, p->d_pred, p->d_pred, n,
-                                        (void *)p->run);
+    rc = heaac_spectral_tools_batch(p->dev, p->ncore, s->d_coeffs, s->d_tools, p->d_rng, p->d_rng, p->d_pred, p->d_pred, n,
+                                    (void *)p->run);
     if (rc == HEAAC_OK)
         rc = p->he ? heaac_he_decode_batch_ex(p->dev, p->he_cfg, p->downsampled ? HEAAC_HE_DOWNSAMPLED : 0, s->d_coeffs, s->d_ics,
                                               s->d_sbr, p->d_hdr, PL_MAX_HDRS, s->d_ps,
@@ -432,18 +313,10 @@ extern "C" int heaac_pipeline_submit(HeaacPipeline *p, const uint8_t *const *au,
                                            HEAAC_PCM_S16_INTERLEAVED, n, (void *)p->run);
     if (rc != HEAAC_OK) return rc;
     // ... and put them back, with silence where the decode wrote
-    if (n_failed) {
+    if (n_all) {
         const size_t pcm_row = (size_t)p->nout * p->out_len;           // int16: an even count, so whole 32-bit words
-        hipLaunchKernelGGL(k_rows, dim3(n_all), dim3(256), 0, p->run, s->d_list, (unsigned *)p->d_state, (unsigned *)p->d_park_state,
-                           (unsigned long long)p->words, 1);
-        hipLaunchKernelGGL(k_rows, dim3(n_all), dim3(256), 0, p->run, s->d_list, (unsigned *)s->d_pcm, (unsigned *)nullptr,
-                           (unsigned long long)(pcm_row / 2), 2);
-        if (n_full) {
-            hipLaunchKernelGGL(k_rows, dim3(n_full), dim3(64), 0, p->run, s->d_list + 2 * n, (unsigned *)p->d_rng, (unsigned *)p->d_park_rng, 1ull, 1);
-            if (p->d_pred)
-                hipLaunchKernelGGL(k_rows, dim3(n_full), dim3(256), 0, p->run, s->d_list + 2 * n, (unsigned *)p->d_pred, (unsigned *)p->d_park_pred,
-                                   (unsigned long long)(pred_row * sizeof(HeaacPredictorState) / 4), 1);
-        }
+        pl_park(p, s, n_all, n_full, 1);
+        heaac_rows(p->run, s->d_list, n_all, 256, s->d_pcm, NULL, pcm_row / 2, 2);
         HIP_OK(hipGetLastError());
     }
     HIP_OK(hipEventRecord(s->run_done, p->run));

@@ -18,12 +18,11 @@
 // Two buffer sets rotate: the host parses tick t + 1 while tick t is on the link and on the GPU.
 #include <hip/hip_runtime.h>
 #include <assert.h>
-#include <pthread.h>
 #include <stdlib.h>
 #include <string.h>
-#include <unistd.h>
 #include "heaac_pipeline.h"
 #include "codec_layout.h"        // heaac_sbr_output_mode
+#include "host_common.h"
 
 #define LP_DEPTH 2
 #define LP_MAX_HDRS 4096
@@ -101,19 +100,11 @@ struct HeaacLayoutPipeline {
     int have_order; unsigned char order[HEAAC_MAX_ELEMENTS];     // order[seq] = element at that bitstream position
     LpCoupled *cpl;                 // layouts whose program config element names coupling elements (AAC-LC / Main)
     // parked state of the streams whose unit failed
-    float *d_park; size_t park_bytes, park_rows;
+    float *d_park; size_t park_rows;
     unsigned long submitted, collected;
-    // pool
-    int threads;
-    pthread_t *tid;
-    pthread_mutex_t mu;
-    pthread_cond_t cv_go, cv_done;
-    unsigned long generation;
-    int pending, quit;
-    const uint8_t *const *job_au; const int *job_size; int *job_status; LpSet *job_set; int job_phase;
+    HeaacPool *pool; int threads;   // threads: the pool's, the slices of a phase
+    const uint8_t *const *job_au; const int *job_size; int *job_status; LpSet *job_set;
 };
-
-struct LpWorkerArg { HeaacLayoutPipeline *p; int w; };
 
 static inline HeaacSbrStream *sst_at(HeaacSbrStream *base, size_t i)
 {
@@ -161,7 +152,8 @@ static HeaacSbrStream *slice_tmp(HeaacLayoutPipeline *p, int w)
 // Phase 0 of a tick: parse every unit of the slice into the set's records.  A refused unit gets neutral records here;
 // a good one leaves its window histories and payload places in ast_new / te_all / ce_all, and nothing of the stream's
 // host state moves yet (submit() may still drop it, lp_commit_slice then moves what is left).
-static void lp_parse_slice(HeaacLayoutPipeline *p, int w)
+// (this and lp_commit_slice out of line under their names: tests/test_pipeline.py looks the per-stream loops up)
+__attribute__((noinline)) static void lp_parse_slice(HeaacLayoutPipeline *p, int w)
 {
     const size_t lo = p->n * (size_t)w / (size_t)p->threads, hi = p->n * (size_t)(w + 1) / (size_t)p->threads;
     LpSet *s = p->job_set;
@@ -264,7 +256,7 @@ static void lp_parse_slice(HeaacLayoutPipeline *p, int w)
 
 // Phase 1: the streams whose unit submit() kept -- their window histories, the coupling elements they have carried,
 // and their SBR payloads, read into the set's records (the readers and the header table move on here).
-static void lp_commit_slice(HeaacLayoutPipeline *p, int w)
+__attribute__((noinline)) static void lp_commit_slice(HeaacLayoutPipeline *p, int w)
 {
     const size_t lo = p->n * (size_t)w / (size_t)p->threads, hi = p->n * (size_t)(w + 1) / (size_t)p->threads;
     LpSet *s = p->job_set;
@@ -313,45 +305,16 @@ static void lp_commit_slice(HeaacLayoutPipeline *p, int w)
     }
 }
 
-static void *lp_worker(void *arg)
+static void lp_slice(void *ctx, int w, int phase)
 {
-    LpWorkerArg *a = (LpWorkerArg *)arg;
-    HeaacLayoutPipeline *p = a->p;
-    const int w = a->w;
-    free(a);
-    unsigned long seen = 0;
-    pthread_mutex_lock(&p->mu);
-    for (;;) {
-        while (p->generation == seen && !p->quit) pthread_cond_wait(&p->cv_go, &p->mu);
-        if (p->quit) break;
-        seen = p->generation;
-        pthread_mutex_unlock(&p->mu);
-        if (p->job_phase) lp_commit_slice(p, w);
-        else lp_parse_slice(p, w);
-        pthread_mutex_lock(&p->mu);
-        if (--p->pending == 0) pthread_cond_signal(&p->cv_done);
-    }
-    pthread_mutex_unlock(&p->mu);
-    return NULL;
+    if (phase) lp_commit_slice((HeaacLayoutPipeline *)ctx, w);
+    else lp_parse_slice((HeaacLayoutPipeline *)ctx, w);
 }
-
-static int lp_pinned(void **p, size_t bytes) { return hipHostMalloc(p, bytes, hipHostMallocDefault) == hipSuccess; }
-static int lp_devmem(void **p, size_t bytes) { return hipMalloc(p, bytes) == hipSuccess; }
 
 extern "C" void heaac_layout_pipeline_destroy(HeaacLayoutPipeline *p)
 {
     if (!p) return;
-    if (p->tid) {
-        pthread_mutex_lock(&p->mu);
-        p->quit = 1;
-        pthread_cond_broadcast(&p->cv_go);
-        pthread_mutex_unlock(&p->mu);
-        for (int t = 1; t < p->threads; t++) if (p->tid[t]) pthread_join(p->tid[t], NULL);
-        free(p->tid);
-        pthread_mutex_destroy(&p->mu);
-        pthread_cond_destroy(&p->cv_go);
-        pthread_cond_destroy(&p->cv_done);
-    }
+    heaac_pool_destroy(p->pool);
     if (p->run) (void)hipStreamSynchronize(p->run);
     for (int q = 0; q < LP_DEPTH; q++) {
         LpSet *s = &p->set[q];
@@ -448,7 +411,6 @@ extern "C" int heaac_layout_pipeline_create(HeaacLayoutPipeline **out, const Hea
     int rc = heaac_device_create(&p->dev, n);
     if (rc != HEAAC_OK) { free(p); return rc; }
     bool ok = hipStreamCreateWithFlags(&p->run, hipStreamNonBlocking) == hipSuccess;
-    HeaacPredictorState *ps = NULL;
     // explicit SBR with Parametric Stereo on (or left open, which decode_audio_specific_config reads as on,
     // aacdec.c:476-477): every single channel element gives two channels (che_configure :203-206; codec_layout.hip)
     const bool ps_sce = aac->sbr == 1 && aac->ps != 0;
@@ -461,27 +423,18 @@ extern "C" int heaac_layout_pipeline_create(HeaacLayoutPipeline **out, const Hea
         if (ps_sce && layout->elem[k].type == HEAAC_ELEM_SCE) { e.cfg = HEAAC_CFG_HEV2; e.out = 2; }
         e.first_out = k ? p->e[k - 1].first_out + p->e[k - 1].out : 0;
         p->out_channels = e.first_out + e.out;
-        e.words = e.cfg == HEAAC_CFG_HEV1 ? HEAAC_STATE_WORDS_HEV1 : e.cfg == HEAAC_CFG_HEV1_MONO ? HEAAC_STATE_WORDS_HEV1_MONO :
-                  e.cfg == HEAAC_CFG_HEV2 ? HEAAC_STATE_WORDS_HEV2 :
-                  e.cfg == HEAAC_CFG_LC_STEREO ? HEAAC_STATE_WORDS_LC_STEREO : HEAAC_STATE_WORDS_LC_MONO;
-        ok = lp_devmem((void **)&e.d_state, n * (size_t)e.words * 4) && hipMemset(e.d_state, 0, n * (size_t)e.words * 4) == hipSuccess &&
-             lp_devmem((void **)&e.d_f32, n * (size_t)e.out * p->len * 4);
+        e.words = (int)heaac_cfg_shape(e.cfg).words;
+        ok = devmem((void **)&e.d_state, n * (size_t)e.words * 4) && hipMemset(e.d_state, 0, n * (size_t)e.words * 4) == hipSuccess &&
+             devmem((void **)&e.d_f32, n * (size_t)e.out * p->len * 4);
         if (ok && p->he) {
             e.sst = (HeaacSbrStream *)malloc(n * heaac_sbr_stream_bytes());
             ok = e.sst != NULL;
             if (ok) heaac_sbr_stream_init(e.sst, n);
         }
         if (ok && p->main_profile) {
-            // reset_predict_state (aacdec.c:507-515) for every predictor of every channel
+            // every predictor of every channel
             const size_t np = n * (size_t)e.channels * HEAAC_MAX_PREDICTORS;
-            ps = (HeaacPredictorState *)calloc(np, sizeof(*ps));
-            ok = ps != NULL && lp_devmem((void **)&e.d_pred, np * sizeof(*ps));
-            if (ok) {
-                for (size_t i = 0; i < np; i++) ps[i].var0 = ps[i].var1 = 1.0f;
-                ok = hipMemcpy(e.d_pred, ps, np * sizeof(*ps), hipMemcpyHostToDevice) == hipSuccess;
-            }
-            free(ps);
-            ps = NULL;
+            ok = devmem((void **)&e.d_pred, np * sizeof(HeaacPredictorState)) && heaac_reset_predictors(e.d_pred, np);
         }
     }
     if (ok && n_cce_slots) {
@@ -492,14 +445,8 @@ extern "C" int heaac_layout_pipeline_create(HeaacLayoutPipeline **out, const Hea
             c->K = K;
             c->words = p->he ? HEAAC_STATE_WORDS_HEV1_MONO : 512;
             c->seen = (unsigned char *)calloc(n * K, 1);
-            ok = c->seen != NULL && lp_devmem((void **)&c->d_state_tmp, n * (size_t)c->words * 4) &&
-                 lp_devmem((void **)&c->d_plane, n * (size_t)p->len * 4);
-        }
-        HeaacPredictorState *reset = NULL;
-        if (ok && p->main_profile) {
-            reset = (HeaacPredictorState *)calloc(n * HEAAC_MAX_PREDICTORS, sizeof(*reset));
-            ok = reset != NULL;
-            for (size_t i = 0; ok && i < n * HEAAC_MAX_PREDICTORS; i++) reset[i].var0 = reset[i].var1 = 1.0f;
+            ok = c->seen != NULL && devmem((void **)&c->d_state_tmp, n * (size_t)c->words * 4) &&
+                 devmem((void **)&c->d_plane, n * (size_t)p->len * 4);
         }
         for (int k = 0; ok && k < K; k++) {
             const size_t sb = n * (size_t)c->words * 4;
@@ -508,24 +455,23 @@ extern "C" int heaac_layout_pipeline_create(HeaacLayoutPipeline **out, const Hea
                 ok = c->sst[k] != NULL;
                 if (ok) heaac_sbr_stream_init(c->sst[k], n);
             }
-            ok = ok && lp_devmem((void **)&c->d_state[k], sb) && hipMemset(c->d_state[k], 0, sb) == hipSuccess &&
-                 lp_devmem((void **)&c->d_ret[k], n * (size_t)p->len * 4) &&
-                 (!reset || (lp_devmem((void **)&c->d_pred[k], n * HEAAC_MAX_PREDICTORS * sizeof(*reset)) &&
-                             hipMemcpy(c->d_pred[k], reset, n * HEAAC_MAX_PREDICTORS * sizeof(*reset), hipMemcpyHostToDevice) == hipSuccess));
+            ok = ok && devmem((void **)&c->d_state[k], sb) && hipMemset(c->d_state[k], 0, sb) == hipSuccess &&
+                 devmem((void **)&c->d_ret[k], n * (size_t)p->len * 4) &&
+                 (!p->main_profile || (devmem((void **)&c->d_pred[k], n * HEAAC_MAX_PREDICTORS * sizeof(HeaacPredictorState)) &&
+                                       heaac_reset_predictors(c->d_pred[k], n * HEAAC_MAX_PREDICTORS)));
         }
-        free(reset);
         for (int q = 0; q < LP_DEPTH && ok; q++) {
             LpSet *s = &p->set[q];
             for (int e = 0; e < p->ne && ok; e++)
-                ok = lp_pinned((void **)&s->h_cce[e], n * K * sizeof(HeaacCceFrame)) && lp_devmem((void **)&s->d_cce[e], n * K * sizeof(HeaacCceFrame));
+                ok = pinned((void **)&s->h_cce[e], n * K * sizeof(HeaacCceFrame)) && devmem((void **)&s->d_cce[e], n * K * sizeof(HeaacCceFrame));
             for (int k = 0; k < K && ok; k++)
-                ok = lp_pinned((void **)&s->h_ccoef[k], n * 4096) && lp_devmem((void **)&s->d_ccoef[k], n * 4096) &&
-                     lp_pinned((void **)&s->h_cics[k], n * sizeof(HeaacIcs)) && lp_devmem((void **)&s->d_cics[k], n * sizeof(HeaacIcs)) &&
-                     lp_pinned((void **)&s->h_ctools[k], n * sizeof(HeaacToolsFrame)) && lp_devmem((void **)&s->d_ctools[k], n * sizeof(HeaacToolsFrame)) &&
-                     (!p->he || (lp_pinned((void **)&s->h_csbr[k], n * sizeof(HeaacSbrFrame)) && lp_devmem((void **)&s->d_csbr[k], n * sizeof(HeaacSbrFrame))));
+                ok = pinned((void **)&s->h_ccoef[k], n * 4096) && devmem((void **)&s->d_ccoef[k], n * 4096) &&
+                     pinned((void **)&s->h_cics[k], n * sizeof(HeaacIcs)) && devmem((void **)&s->d_cics[k], n * sizeof(HeaacIcs)) &&
+                     pinned((void **)&s->h_ctools[k], n * sizeof(HeaacToolsFrame)) && devmem((void **)&s->d_ctools[k], n * sizeof(HeaacToolsFrame)) &&
+                     (!p->he || (pinned((void **)&s->h_csbr[k], n * sizeof(HeaacSbrFrame)) && devmem((void **)&s->d_csbr[k], n * sizeof(HeaacSbrFrame))));
             const size_t ng = (size_t)p->ne * K * HEAAC_MAX_CCE_LINKS * n * (p->len / 1024);
-            ok = ok && lp_devmem((void **)&s->d_ccoef_fm, n * K * 4096) &&
-                 lp_pinned((void **)&s->h_gain, ng * sizeof(HeaacCoupling)) && lp_devmem((void **)&s->d_gain, ng * sizeof(HeaacCoupling)) &&
+            ok = ok && devmem((void **)&s->d_ccoef_fm, n * K * 4096) &&
+                 pinned((void **)&s->h_gain, ng * sizeof(HeaacCoupling)) && devmem((void **)&s->d_gain, ng * sizeof(HeaacCoupling)) &&
                  (s->cpos = (unsigned char *)calloc(n * K, 3)) != NULL;
         }
     }
@@ -533,30 +479,22 @@ extern "C" int heaac_layout_pipeline_create(HeaacLayoutPipeline **out, const Hea
         LpSet *s = &p->set[q];
         for (int k = 0; k < p->ne && ok; k++) {
             const size_t nc = n * (size_t)p->e[k].channels;
-            ok = lp_pinned((void **)&s->h_coeffs[k], nc * 4096) && lp_devmem((void **)&s->d_coeffs[k], nc * 4096) &&
-                 lp_pinned((void **)&s->h_ics[k], nc * sizeof(HeaacIcs)) && lp_devmem((void **)&s->d_ics[k], nc * sizeof(HeaacIcs)) &&
-                 lp_pinned((void **)&s->h_tools[k], n * sizeof(HeaacToolsFrame)) && lp_devmem((void **)&s->d_tools[k], n * sizeof(HeaacToolsFrame)) &&
-                 (!p->he || (lp_pinned((void **)&s->h_sbr[k], n * sizeof(HeaacSbrFrame)) && lp_devmem((void **)&s->d_sbr[k], n * sizeof(HeaacSbrFrame)))) &&
+            ok = pinned((void **)&s->h_coeffs[k], nc * 4096) && devmem((void **)&s->d_coeffs[k], nc * 4096) &&
+                 pinned((void **)&s->h_ics[k], nc * sizeof(HeaacIcs)) && devmem((void **)&s->d_ics[k], nc * sizeof(HeaacIcs)) &&
+                 pinned((void **)&s->h_tools[k], n * sizeof(HeaacToolsFrame)) && devmem((void **)&s->d_tools[k], n * sizeof(HeaacToolsFrame)) &&
+                 (!p->he || (pinned((void **)&s->h_sbr[k], n * sizeof(HeaacSbrFrame)) && devmem((void **)&s->d_sbr[k], n * sizeof(HeaacSbrFrame)))) &&
                  (p->e[k].cfg != HEAAC_CFG_HEV2 ||
-                  (lp_pinned((void **)&s->h_ps[k], n * sizeof(HeaacPsFrame)) && lp_devmem((void **)&s->d_ps[k], n * sizeof(HeaacPsFrame))));
+                  (pinned((void **)&s->h_ps[k], n * sizeof(HeaacPsFrame)) && devmem((void **)&s->d_ps[k], n * sizeof(HeaacPsFrame))));
         }
         const size_t pcm_bytes = n * (size_t)p->out_channels * p->len * 2;
-        ok = ok && lp_pinned((void **)&s->h_pcm, pcm_bytes) && lp_devmem((void **)&s->d_pcm, pcm_bytes) &&
+        ok = ok && pinned((void **)&s->h_pcm, pcm_bytes) && devmem((void **)&s->d_pcm, pcm_bytes) &&
              (s->failed = (unsigned char *)calloc(n, 1)) != NULL && (s->seq = (unsigned char *)calloc(n * p->ne, 1)) != NULL &&
-             lp_pinned((void **)&s->h_list, (4 + 2 * (size_t)n_cce_slots) * n * sizeof(unsigned)) &&
-             lp_devmem((void **)&s->d_list, (4 + 2 * (size_t)n_cce_slots) * n * sizeof(unsigned)) &&
+             pinned((void **)&s->h_list, (4 + 2 * (size_t)n_cce_slots) * n * sizeof(unsigned)) &&
+             devmem((void **)&s->d_list, (4 + 2 * (size_t)n_cce_slots) * n * sizeof(unsigned)) &&
              hipEventCreate(&s->done) == hipSuccess;
     }
-    ok = ok && lp_devmem((void **)&p->d_rng, n * 4) && lp_devmem((void **)&p->d_hdr, LP_MAX_HDRS * sizeof(HeaacSbrHeader));
-    if (ok) {
-        int32_t *seed = (int32_t *)malloc(n * 4);
-        ok = seed != NULL;
-        if (ok) {
-            for (size_t i = 0; i < n; i++) seed[i] = 0x1f2e3d4c;       // ac->random_state, aacdec.c:558
-            ok = hipMemcpy(p->d_rng, seed, n * 4, hipMemcpyHostToDevice) == hipSuccess;
-            free(seed);
-        }
-    }
+    ok = ok && devmem((void **)&p->d_rng, n * 4) && devmem((void **)&p->d_hdr, LP_MAX_HDRS * sizeof(HeaacSbrHeader)) &&
+         heaac_seed_generators(p->d_rng, n);
     p->tab = heaac_sbr_table_create(LP_MAX_HDRS);
     p->ast = (HeaacAacStream *)calloc(n * p->ne, sizeof(HeaacAacStream));
     p->lay = (HeaacAacLayout *)malloc(n * sizeof(HeaacAacLayout));
@@ -571,45 +509,16 @@ extern "C" int heaac_layout_pipeline_create(HeaacLayoutPipeline **out, const Hea
         p->hdr_uploaded = 1;
     }
     if (ok) {
-        if (threads <= 0) {
-            long online = sysconf(_SC_NPROCESSORS_ONLN);
-            threads = online < 1 ? 1 : online > 32 ? 32 : (int)online;
-        }
+        if (threads <= 0) threads = heaac_threads_online_max32();
         if (threads > 256) threads = 256;
         if ((size_t)threads > n) threads = (int)n;
-        p->threads = threads;
-        pthread_mutex_init(&p->mu, NULL);
-        pthread_cond_init(&p->cv_go, NULL);
-        pthread_cond_init(&p->cv_done, NULL);
-        p->tid = (pthread_t *)calloc(threads, sizeof(pthread_t));
-        ok = p->tid != NULL && (!p->he || (p->sst_tmp = (HeaacSbrStream *)malloc(threads * heaac_sbr_stream_bytes())) != NULL);
-        for (int t = 1; t < threads && ok; t++) {          // slice 0 is parsed by the submitting thread
-            LpWorkerArg *a = (LpWorkerArg *)malloc(sizeof(*a));
-            if (!a) { ok = false; break; }
-            a->p = p; a->w = t;
-            if (pthread_create(&p->tid[t], NULL, lp_worker, a) != 0) { free(a); p->tid[t] = 0; p->threads = t; break; }
-        }
+        ok = (p->pool = heaac_pool_create(threads, lp_slice, p)) != NULL;
+        if (ok) p->threads = heaac_pool_threads(p->pool);
+        ok = ok && (!p->he || (p->sst_tmp = (HeaacSbrStream *)malloc(p->threads * heaac_sbr_stream_bytes())) != NULL);
     }
     if (!ok) { heaac_layout_pipeline_destroy(p); return HEAAC_ERR_NOMEM; }
     *out = p;
     return HEAAC_OK;
-}
-
-#define LP_HIP(x) do { if ((x) != hipSuccess) return HEAAC_ERR_HIP; } while (0)
-
-// Rows of the failed streams to the parking area and back (or zeroed): one block per listed (stream, parking row)
-// pair -- a handful of launches per tick however many units are damaged (pipeline.hip k_rows).
-//   mode 0: park[row] = rows[stream];  1: rows[stream] = park[row];  2: rows[stream] = 0
-__global__ void k_lp_rows(const unsigned *__restrict__ list, unsigned *rows, unsigned *park, unsigned long long row_words, int mode)
-{
-    const unsigned stream = list[2 * blockIdx.x], slot = list[2 * blockIdx.x + 1];
-    unsigned *r = rows + stream * row_words;
-    unsigned *q = park ? park + slot * row_words : nullptr;
-    for (unsigned long long w = threadIdx.x; w < row_words; w += blockDim.x) {
-        if (mode == 0) q[w] = r[w];
-        else if (mode == 1) r[w] = q[w];
-        else r[w] = 0u;
-    }
 }
 
 // rows of every failed stream: element states, predictors, noise generator -- to / from the parking area, which holds
@@ -624,35 +533,15 @@ static int lp_park(HeaacLayoutPipeline *p, LpSet *s, unsigned n_all, unsigned n_
     for (int k = 0; k < p->ne; k++) {
         const LpElem &e = p->e[k];
         const size_t sb = (size_t)e.words * 4, pb = (size_t)e.channels * HEAAC_MAX_PREDICTORS * sizeof(HeaacPredictorState);
-        hipLaunchKernelGGL(k_lp_rows, dim3(n_all), dim3(256), 0, p->run, s->d_list, (unsigned *)e.d_state, (unsigned *)region,
-                           (unsigned long long)e.words, restore);
+        heaac_rows(p->run, s->d_list, n_all, 256, e.d_state, region, e.words, restore);
         region += cap * sb;
         if (e.d_pred) {
-            if (n_full)
-                hipLaunchKernelGGL(k_lp_rows, dim3(n_full), dim3(256), 0, p->run, s->d_list + 2 * p->n, (unsigned *)e.d_pred, (unsigned *)region,
-                                   (unsigned long long)(pb / 4), restore);
+            if (n_full) heaac_rows(p->run, s->d_list + 2 * p->n, n_full, 256, e.d_pred, region, pb / 4, restore);
             region += cap * pb;
         }
     }
-    if (n_full)
-        hipLaunchKernelGGL(k_lp_rows, dim3(n_full), dim3(64), 0, p->run, s->d_list + 2 * p->n, (unsigned *)p->d_rng, (unsigned *)region, 1ull, restore);
+    if (n_full) heaac_rows(p->run, s->d_list + 2 * p->n, n_full, 64, p->d_rng, region, 1, restore);
     return hipGetLastError() == hipSuccess ? HEAAC_OK : HEAAC_ERR_HIP;
-}
-
-// one phase of the tick on the pool: slice 0 on the calling thread, the others on the workers
-static void lp_run_slices(HeaacLayoutPipeline *p, int phase)
-{
-    pthread_mutex_lock(&p->mu);
-    p->job_phase = phase;
-    p->pending = p->threads - 1;
-    p->generation++;
-    pthread_cond_broadcast(&p->cv_go);
-    pthread_mutex_unlock(&p->mu);
-    if (phase) lp_commit_slice(p, 0);
-    else lp_parse_slice(p, 0);
-    pthread_mutex_lock(&p->mu);
-    while (p->pending > 0) pthread_cond_wait(&p->cv_done, &p->mu);
-    pthread_mutex_unlock(&p->mu);
 }
 
 extern "C" int heaac_layout_pipeline_submit(HeaacLayoutPipeline *p, const uint8_t *const *au, const int *size, int *status)
@@ -662,7 +551,7 @@ extern "C" int heaac_layout_pipeline_submit(HeaacLayoutPipeline *p, const uint8_
     LpSet *s = &p->set[p->submitted % LP_DEPTH];
     // (the set's buffers are free: its last tick has been collected, which waited for its `done`)
     p->job_au = au; p->job_size = size; p->job_status = status; p->job_set = s;
-    lp_run_slices(p, 0);
+    heaac_pool_run(p->pool, 0);
     HeaacSbrStream *tmp = slice_tmp(p, 0);          // (slice 0 is the submitting thread's, and the pool is idle)
 
     const size_t n = p->n;
@@ -715,31 +604,27 @@ extern "C" int heaac_layout_pipeline_submit(HeaacLayoutPipeline *p, const uint8_
     for (int k = 0; k < K; k++) n_cce_tick += cpat[k][0];
     // the units that stand: now they move their streams' host state (a dropped one leaves it as its device rows are
     // left, parked -- as if the unit had never arrived)
-    lp_run_slices(p, 1);
-    const size_t have = heaac_sbr_table_count(p->tab);
-    if (have > LP_MAX_HDRS) return HEAAC_ERR_ARG;
+    heaac_pool_run(p->pool, 1);
+    if (heaac_sbr_table_count(p->tab) > LP_MAX_HDRS) return HEAAC_ERR_ARG;
     // H2D (the run stream carries everything: the tick before has the GPU meanwhile)
-    if (have > p->hdr_uploaded) {
-        LP_HIP(hipMemcpyAsync(p->d_hdr + p->hdr_uploaded, heaac_sbr_table_data(p->tab) + p->hdr_uploaded,
-                              (have - p->hdr_uploaded) * sizeof(HeaacSbrHeader), hipMemcpyHostToDevice, p->run));
-        p->hdr_uploaded = have;
-    }
+    int rc = heaac_upload_headers(p->tab, &p->hdr_uploaded, p->d_hdr, NULL, p->run);
+    if (rc != HEAAC_OK) return rc;
     for (int k = 0; k < ne; k++) {
         const size_t nc = n * (size_t)p->e[k].channels;
-        LP_HIP(hipMemcpyAsync(s->d_coeffs[k], s->h_coeffs[k], nc * 4096, hipMemcpyHostToDevice, p->run));
-        LP_HIP(hipMemcpyAsync(s->d_ics[k], s->h_ics[k], nc * sizeof(HeaacIcs), hipMemcpyHostToDevice, p->run));
-        LP_HIP(hipMemcpyAsync(s->d_tools[k], s->h_tools[k], n * sizeof(HeaacToolsFrame), hipMemcpyHostToDevice, p->run));
-        if (p->he) LP_HIP(hipMemcpyAsync(s->d_sbr[k], s->h_sbr[k], n * sizeof(HeaacSbrFrame), hipMemcpyHostToDevice, p->run));
-        if (s->d_ps[k]) LP_HIP(hipMemcpyAsync(s->d_ps[k], s->h_ps[k], n * sizeof(HeaacPsFrame), hipMemcpyHostToDevice, p->run));
+        HIP_OK(hipMemcpyAsync(s->d_coeffs[k], s->h_coeffs[k], nc * 4096, hipMemcpyHostToDevice, p->run));
+        HIP_OK(hipMemcpyAsync(s->d_ics[k], s->h_ics[k], nc * sizeof(HeaacIcs), hipMemcpyHostToDevice, p->run));
+        HIP_OK(hipMemcpyAsync(s->d_tools[k], s->h_tools[k], n * sizeof(HeaacToolsFrame), hipMemcpyHostToDevice, p->run));
+        if (p->he) HIP_OK(hipMemcpyAsync(s->d_sbr[k], s->h_sbr[k], n * sizeof(HeaacSbrFrame), hipMemcpyHostToDevice, p->run));
+        if (s->d_ps[k]) HIP_OK(hipMemcpyAsync(s->d_ps[k], s->h_ps[k], n * sizeof(HeaacPsFrame), hipMemcpyHostToDevice, p->run));
     }
     if (n_cce_tick) {
         for (int e = 0; e < ne; e++)
-            LP_HIP(hipMemcpyAsync(s->d_cce[e], s->h_cce[e], n * K * sizeof(HeaacCceFrame), hipMemcpyHostToDevice, p->run));
+            HIP_OK(hipMemcpyAsync(s->d_cce[e], s->h_cce[e], n * K * sizeof(HeaacCceFrame), hipMemcpyHostToDevice, p->run));
         for (int k = 0; k < K; k++) {
-            LP_HIP(hipMemcpyAsync(s->d_ccoef[k], s->h_ccoef[k], n * 4096, hipMemcpyHostToDevice, p->run));
-            LP_HIP(hipMemcpyAsync(s->d_cics[k], s->h_cics[k], n * sizeof(HeaacIcs), hipMemcpyHostToDevice, p->run));
-            LP_HIP(hipMemcpyAsync(s->d_ctools[k], s->h_ctools[k], n * sizeof(HeaacToolsFrame), hipMemcpyHostToDevice, p->run));
-            if (p->he) LP_HIP(hipMemcpyAsync(s->d_csbr[k], s->h_csbr[k], n * sizeof(HeaacSbrFrame), hipMemcpyHostToDevice, p->run));
+            HIP_OK(hipMemcpyAsync(s->d_ccoef[k], s->h_ccoef[k], n * 4096, hipMemcpyHostToDevice, p->run));
+            HIP_OK(hipMemcpyAsync(s->d_cics[k], s->h_cics[k], n * sizeof(HeaacIcs), hipMemcpyHostToDevice, p->run));
+            HIP_OK(hipMemcpyAsync(s->d_ctools[k], s->h_ctools[k], n * sizeof(HeaacToolsFrame), hipMemcpyHostToDevice, p->run));
+            if (p->he) HIP_OK(hipMemcpyAsync(s->d_csbr[k], s->h_csbr[k], n * sizeof(HeaacSbrFrame), hipMemcpyHostToDevice, p->run));
         }
     }
     unsigned n_all = 0, n_full = 0;
@@ -747,26 +632,17 @@ extern "C" int heaac_layout_pipeline_submit(HeaacLayoutPipeline *p, const uint8_
         size_t row = 4;
         for (int k = 0; k < ne; k++)
             row += (size_t)p->e[k].words * 4 + (p->e[k].d_pred ? (size_t)p->e[k].channels * HEAAC_MAX_PREDICTORS * sizeof(HeaacPredictorState) : 0);
-        if (n_failed > p->park_rows) {
-            LP_HIP(hipStreamSynchronize(p->run));
+        size_t rows;
+        rc = heaac_park_grow(p->run, n_failed, p->park_rows, 16, n, &rows);
+        if (rc != HEAAC_OK) return rc;
+        if (rows != p->park_rows) {
             if (p->d_park) (void)hipFree(p->d_park);
-            p->d_park = NULL; p->park_bytes = 0; p->park_rows = 0;
-            size_t rows = 16;
-            while (rows < n_failed) rows *= 2;
-            if (rows > n) rows = n;
-            if (!lp_devmem((void **)&p->d_park, rows * row)) return HEAAC_ERR_NOMEM;
-            p->park_bytes = rows * row;
+            p->d_park = NULL; p->park_rows = 0;
+            if (!devmem((void **)&p->d_park, rows * row)) return HEAAC_ERR_NOMEM;
             p->park_rows = rows;
         }
-        unsigned *list_all = s->h_list, *list_full = s->h_list + 2 * n;
-        for (size_t i = 0; i < n; i++) {
-            if (!s->failed[i]) continue;
-            if (s->failed[i] == 1) { list_full[2 * n_full] = (unsigned)i; list_full[2 * n_full + 1] = n_all; n_full++; }
-            list_all[2 * n_all] = (unsigned)i; list_all[2 * n_all + 1] = n_all; n_all++;
-        }
-        LP_HIP(hipMemcpyAsync(s->d_list, list_all, 2 * n_all * sizeof(unsigned), hipMemcpyHostToDevice, p->run));
-        if (n_full) LP_HIP(hipMemcpyAsync(s->d_list + 2 * n, list_full, 2 * n_full * sizeof(unsigned), hipMemcpyHostToDevice, p->run));
-        const int rc = lp_park(p, s, n_all, n_full, p->park_rows, 0);
+        rc = heaac_failed_lists(p->run, s->failed, n, s->h_list, s->d_list, &n_all, &n_full);
+        if (rc == HEAAC_OK) rc = lp_park(p, s, n_all, n_full, p->park_rows, 0);
         if (rc != HEAAC_OK) return rc;
     }
     // the spectral tools of the elements in bitstream order (one noise generator per stream).  A coupling element's
@@ -791,7 +667,7 @@ extern "C" int heaac_layout_pipeline_submit(HeaacLayoutPipeline *p, const uint8_
     if (n_cce_tick) {
         // the coupling channels' spectra frame-major, K slots per stream, as the second half reads them
         for (int k = 0; k < K; k++)
-            LP_HIP(hipMemcpy2DAsync(s->d_ccoef_fm + (size_t)k * 1024, (size_t)K * 4096, s->d_ccoef[k], 4096, 4096, n,
+            HIP_OK(hipMemcpy2DAsync(s->d_ccoef_fm + (size_t)k * 1024, (size_t)K * 4096, s->d_ccoef[k], 4096, 4096, n,
                                     hipMemcpyDeviceToDevice, p->run));
         for (int k = 0; k < ne; k++) {
             const LpElem &e = p->e[k];
@@ -829,10 +705,9 @@ extern "C" int heaac_layout_pipeline_submit(HeaacLayoutPipeline *p, const uint8_
                         cnt++;
                     }
                 unsigned *dl = s->d_list + (4 + 2 * (size_t)k) * n;
-                LP_HIP(hipMemcpyAsync(dl, lst, 2 * cnt * sizeof(unsigned), hipMemcpyHostToDevice, p->run));
-                hipLaunchKernelGGL(k_lp_rows, dim3(cnt), dim3(256), 0, p->run, dl, (unsigned *)st, (unsigned *)p->cpl->d_state_tmp,
-                                   (unsigned long long)words, 1);
-                LP_HIP(hipGetLastError());
+                HIP_OK(hipMemcpyAsync(dl, lst, 2 * cnt * sizeof(unsigned), hipMemcpyHostToDevice, p->run));
+                heaac_rows(p->run, dl, cnt, 256, st, p->cpl->d_state_tmp, words, 1);
+                HIP_OK(hipGetLastError());
             }
         }
     }
@@ -873,7 +748,7 @@ extern "C" int heaac_layout_pipeline_submit(HeaacLayoutPipeline *p, const uint8_
                 if (!used[0] && !used[1]) continue;
                 HeaacCoupling *dg = s->d_gain + (g - s->h_gain);
                 if (direct) {
-                    LP_HIP(hipMemcpyAsync(dg, g, n * sub * sizeof(HeaacCoupling), hipMemcpyHostToDevice, p->run));
+                    HIP_OK(hipMemcpyAsync(dg, g, n * sub * sizeof(HeaacCoupling), hipMemcpyHostToDevice, p->run));
                     const int rc2 = heaac_couple_after_imdct_batch(p->dev, sub == 1 ? e.out : 1, e.d_f32, p->cpl->d_ret[kc], dg, NULL,
                                                                    n * sub, (void *)p->run);
                     if (rc2 != HEAAC_OK) return rc2;
@@ -894,15 +769,15 @@ extern "C" int heaac_layout_pipeline_submit(HeaacLayoutPipeline *p, const uint8_
                                 g[i * sub + q].gain[0] = mine ? r.link[l].gain[0] : 0.0f;
                             }
                         }
-                        LP_HIP(hipStreamSynchronize(p->run));      // (the staging area is about to be rewritten for the other channel)
+                        HIP_OK(hipStreamSynchronize(p->run));      // (the staging area is about to be rewritten for the other channel)
                     }
-                    LP_HIP(hipMemcpyAsync(dg, g, n * sub * sizeof(HeaacCoupling), hipMemcpyHostToDevice, p->run));
+                    HIP_OK(hipMemcpyAsync(dg, g, n * sub * sizeof(HeaacCoupling), hipMemcpyHostToDevice, p->run));
                     const size_t row = (size_t)p->len * 4;
-                    LP_HIP(hipMemcpy2DAsync(p->cpl->d_plane, row, e.d_f32 + (size_t)tc2 * p->len, 2 * row, row, n, hipMemcpyDeviceToDevice, p->run));
+                    HIP_OK(hipMemcpy2DAsync(p->cpl->d_plane, row, e.d_f32 + (size_t)tc2 * p->len, 2 * row, row, n, hipMemcpyDeviceToDevice, p->run));
                     const int rc2 = heaac_couple_after_imdct_batch(p->dev, 1, p->cpl->d_plane, p->cpl->d_ret[kc], dg, NULL, n * sub, (void *)p->run);
                     if (rc2 != HEAAC_OK) return rc2;
-                    LP_HIP(hipMemcpy2DAsync(e.d_f32 + (size_t)tc2 * p->len, 2 * row, p->cpl->d_plane, row, row, n, hipMemcpyDeviceToDevice, p->run));
-                    if (used[tc2 ^ 1]) LP_HIP(hipStreamSynchronize(p->run));
+                    HIP_OK(hipMemcpy2DAsync(e.d_f32 + (size_t)tc2 * p->len, 2 * row, p->cpl->d_plane, row, row, n, hipMemcpyDeviceToDevice, p->run));
+                    if (used[tc2 ^ 1]) HIP_OK(hipStreamSynchronize(p->run));
                 }
             }
         }
@@ -911,18 +786,17 @@ extern "C" int heaac_layout_pipeline_submit(HeaacLayoutPipeline *p, const uint8_
             planes[e.first_out + c].frame_stride = (size_t)e.out * p->len;
         }
     }
-    int rc = heaac_pcm_interleave_batch(p->dev, p->out_channels, planes, p->len, HEAAC_PCM_S16_INTERLEAVED, s->d_pcm, n, (void *)p->run);
+    rc = heaac_pcm_interleave_batch(p->dev, p->out_channels, planes, p->len, HEAAC_PCM_S16_INTERLEAVED, s->d_pcm, n, (void *)p->run);
     if (rc != HEAAC_OK) return rc;
     const size_t pcm_row = (size_t)p->out_channels * p->len;
     if (n_failed) {
         rc = lp_park(p, s, n_all, n_full, p->park_rows, 1);
         if (rc != HEAAC_OK) return rc;
-        hipLaunchKernelGGL(k_lp_rows, dim3(n_all), dim3(256), 0, p->run, s->d_list, (unsigned *)s->d_pcm, (unsigned *)nullptr,
-                           (unsigned long long)(pcm_row / 2), 2);      // (len is a multiple of 1024: whole 32-bit words)
-        LP_HIP(hipGetLastError());
+        heaac_rows(p->run, s->d_list, n_all, 256, s->d_pcm, NULL, pcm_row / 2, 2);      // (len is a multiple of 1024: whole 32-bit words)
+        HIP_OK(hipGetLastError());
     }
-    LP_HIP(hipMemcpyAsync(s->h_pcm, s->d_pcm, n * pcm_row * 2, hipMemcpyDeviceToHost, p->run));
-    LP_HIP(hipEventRecord(s->done, p->run));
+    HIP_OK(hipMemcpyAsync(s->h_pcm, s->d_pcm, n * pcm_row * 2, hipMemcpyDeviceToHost, p->run));
+    HIP_OK(hipEventRecord(s->done, p->run));
     s->used = 1;
     p->submitted++;
     return HEAAC_OK;
@@ -934,7 +808,7 @@ extern "C" int heaac_layout_pipeline_collect(HeaacLayoutPipeline *p, const int16
 {
     if (!p || !pcm || p->collected == p->submitted) return HEAAC_ERR_ARG;
     LpSet *s = &p->set[p->collected % LP_DEPTH];
-    LP_HIP(hipEventSynchronize(s->done));
+    HIP_OK(hipEventSynchronize(s->done));
     *pcm = s->h_pcm;
     p->collected++;
     return HEAAC_OK;

@@ -304,6 +304,7 @@ extern "C" void av_fft_end(FFTContext *s) { if (s) { ff_fft_end(s); free(s); } }
 // ---------------------------------------------------------------------------
 #define MAX_HDRS 64
 #include "codec_layout.h"
+#include "host_common.h"
 
 typedef struct HeaacDecoderPriv {
     HeaacDevice *dev;
@@ -336,18 +337,13 @@ typedef struct HeaacDecoderPriv {
 
 static void set_cfg(HeaacDecoderPriv *p, int cfg)
 {
+    const HeaacCfgShape shape = heaac_cfg_shape(cfg);        // ncore = 0: not a configuration
     p->cfg = cfg;
-    switch (cfg) {
-    case HEAAC_CFG_LC_MONO:   p->ncore = 1; p->nout = 1; p->out_len = 1024; p->words = HEAAC_STATE_WORDS_LC_MONO; break;
-    case HEAAC_CFG_LC_STEREO: p->ncore = 2; p->nout = 2; p->out_len = 1024; p->words = HEAAC_STATE_WORDS_LC_STEREO; break;
-    case HEAAC_CFG_HEV1:      p->ncore = 2; p->nout = 2; p->out_len = 2048; p->words = HEAAC_STATE_WORDS_HEV1; break;
-    case HEAAC_CFG_HEV1_MONO: p->ncore = 1; p->nout = 1; p->out_len = 2048; p->words = HEAAC_STATE_WORDS_HEV1_MONO; break;
-    case HEAAC_CFG_HEV2:      p->ncore = 1; p->nout = 2; p->out_len = 2048; p->words = HEAAC_STATE_WORDS_HEV2; break;
-    default:                  p->ncore = 0; break;
-    }
+    p->ncore = shape.ncore; p->nout = shape.nout; p->words = shape.words;
+    p->out_len = shape.he ? 2048 : 1024;
 }
 
-static int cfg_is_he(int cfg) { return cfg == HEAAC_CFG_HEV1 || cfg == HEAAC_CFG_HEV1_MONO || cfg == HEAAC_CFG_HEV2; }
+static int cfg_is_he(int cfg) { return heaac_cfg_shape(cfg).he; }
 
 // The two decisions the reference takes from the configuration's two sample rates: ff_sbr_apply synthesises with the
 // 32-band bank -- 1024 samples per frame -- when ext_sample_rate < sbr->sample_rate = 2 * sample_rate (aacsbr.c:1055,
@@ -393,7 +389,7 @@ static int dec_init_bitstream(HeaacCodecContext *avctx, HeaacDecoderPriv *p)
         if (p->m4ac.sbr == 1 && heaac_sbr_output_mode(&p->m4ac) < 0) return -1;
         p->have_m4ac = 1;
     }
-    const size_t words = HEAAC_STATE_WORDS_HEV2 > HEAAC_STATE_WORDS_HEV1 ? HEAAC_STATE_WORDS_HEV2 : HEAAC_STATE_WORDS_HEV1;
+    const size_t words = HEAAC_STATE_WORDS_MAX;
     p->tab = heaac_sbr_table_create(MAX_HDRS);
     p->h_coeffs = (float *)calloc(2 * 1024, sizeof(float));
     p->h_tools = (HeaacToolsFrame *)calloc(1, sizeof(HeaacToolsFrame));
@@ -410,14 +406,7 @@ static int dec_init_bitstream(HeaacCodecContext *avctx, HeaacDecoderPriv *p)
         hipMalloc((void **)&p->d_pred, 2 * HEAAC_MAX_PREDICTORS * sizeof(HeaacPredictorState)) != hipSuccess)
         return -1;
     if (hipMemset(p->d_state, 0, words * 4) != hipSuccess) return -1;
-    const int32_t seed = 0x1f2e3d4c;                                   // ac->random_state, aacdec.c:558
-    if (hipMemcpy(p->d_rng, &seed, 4, hipMemcpyHostToDevice) != hipSuccess) return -1;
-    HeaacPredictorState *ps = (HeaacPredictorState *)calloc(2 * HEAAC_MAX_PREDICTORS, sizeof(*ps));
-    if (!ps) return -1;
-    for (int i = 0; i < 2 * HEAAC_MAX_PREDICTORS; i++) ps[i].var0 = ps[i].var1 = 1.0f;   // reset_predict_state, :507-515
-    const hipError_t e = hipMemcpy(p->d_pred, ps, 2 * HEAAC_MAX_PREDICTORS * sizeof(*ps), hipMemcpyHostToDevice);
-    free(ps);
-    if (e != hipSuccess) return -1;
+    if (!heaac_seed_generators(p->d_rng, 1) || !heaac_reset_predictors(p->d_pred, 2 * HEAAC_MAX_PREDICTORS)) return -1;
     if (p->have_m4ac && p->have_layout) {
         if (!(p->lay = heaac_layout_dec_create(p->dev, &p->m4ac, &p->layout))) return -1;
         // tentative (output_configure with OC_GLOBAL_HDR); the first access unit settles implicit SBR
@@ -534,15 +523,7 @@ static int dec_frame_bitstream(HeaacCodecContext *avctx, HeaacDecoderPriv *p, vo
         rc = heaac_lc_decode_batch(p->dev, ch, p->d_coeffs, (const HeaacIcs *)d_ics, p->d_state, p->d_state,
                                    p->d_pcm, HEAAC_PCM_S16_INTERLEAVED, 1, NULL);
     } else {
-        const size_t have = heaac_sbr_table_count(p->tab);
-        if (have > p->hdr_uploaded) {
-            memcpy(p->hdr + p->hdr_uploaded, heaac_sbr_table_data(p->tab) + p->hdr_uploaded,
-                   (have - p->hdr_uploaded) * sizeof(HeaacSbrHeader));
-            if (hipMemcpy(p->d_hdr + p->hdr_uploaded, p->hdr + p->hdr_uploaded,
-                          (have - p->hdr_uploaded) * sizeof(HeaacSbrHeader), hipMemcpyHostToDevice) != hipSuccess)
-                return -1;
-            p->hdr_uploaded = have;
-        }
+        if (heaac_upload_headers(p->tab, &p->hdr_uploaded, p->d_hdr, p->hdr, NULL) != HEAAC_OK) return -1;
         if (heaac_validate_frame(p->cfg, &sbr, p->hdr, MAX_HDRS, p->cfg == HEAAC_CFG_HEV2 ? &ps : NULL)) return -1;
         if (hipMemcpy(d_sbr, &sbr, sizeof(sbr), hipMemcpyHostToDevice) != hipSuccess) return -1;
         if (p->cfg == HEAAC_CFG_HEV2 && hipMemcpy(d_ps, &ps, sizeof(ps), hipMemcpyHostToDevice) != hipSuccess) return -1;
@@ -614,7 +595,7 @@ static int dec_frame(HeaacCodecContext *avctx, void *data, int *data_size, Heaac
     HeaacDecoderPriv *p = (HeaacDecoderPriv *)avctx->priv_data;
     if (p->bitstream) return dec_frame_bitstream(avctx, p, data, data_size, avpkt);
     const uint8_t *buf = avpkt->data;
-    const int he = p->cfg == HEAAC_CFG_HEV1 || p->cfg == HEAAC_CFG_HEV1_MONO || p->cfg == HEAAC_CFG_HEV2;
+    const int he = cfg_is_he(p->cfg);
     size_t need = sizeof(HeaacFramePacket) + (size_t)p->ncore * 4096 + (he ? sizeof(HeaacSbrFrame) : 0) +
                   (p->cfg == HEAAC_CFG_HEV2 ? sizeof(HeaacPsFrame) : 0);
     if (!buf || (size_t)avpkt->size < need) return -1;

@@ -113,6 +113,7 @@ EXPORTED = [
     # heaac_dsp.h
     "heaac_device_create", "heaac_device_destroy", "heaac_device_workspace_bytes",
     "heaac_strerror", "heaac_imdct_half_batch", "heaac_lc_decode_batch", "heaac_lc_decode_streams",
+    "heaac_lc_decode_streams_ex", "heaac_he_decode_streams_ex", "heaac_spectral_tools_streams_ex",
     "heaac_he_decode_batch", "heaac_he_decode_batch_ex", "heaac_he_decode_streams", "heaac_qmf_analysis_batch", "heaac_qmf_synthesis_batch",
     "heaac_qmf_synthesis_ds_batch",
     "heaac_sbr_make_header", "heaac_build_info", "heaac_spectral_tools_batch", "heaac_spectral_tools_streams",
@@ -128,7 +129,7 @@ EXPORTED = [
     # heaac_parse.h
     "heaac_asc_parse", "heaac_ga_specific_config", "heaac_aac_parse_frame_ex", "heaac_pcm_interleave_batch", "heaac_aac_layout_default", "heaac_aac_layout_from_pce", "heaac_aac_layout_from_au", "heaac_asc_layout", "heaac_aac_parse_frame_layout", "heaac_aac_parse_frame_layout_ex", "heaac_spectral_tools_batch_ex", "heaac_codec_get_context_defaults", "heaac_adts_parse_header", "heaac_adts_probe", "heaac_adts_split",
     "heaac_heaac_parse_frame_ex", "heaac_pipeline_create", "heaac_pipeline_destroy", "heaac_pipeline_submit",
-    "heaac_pipeline_collect", "heaac_pipeline_timing",
+    "heaac_pipeline_collect", "heaac_pipeline_timing", "heaac_pipeline_create_streams", "heaac_pipeline_frames_per_tick",
     "heaac_layout_pipeline_create", "heaac_layout_pipeline_destroy", "heaac_layout_pipeline_submit",
     "heaac_layout_pipeline_collect", "heaac_layout_pipeline_channels",
     # heaac_debug.h
@@ -269,6 +270,13 @@ def _ptr(t):
     return C.c_void_p(t.data_ptr())
 
 
+def _hold_ptr(hold, n):
+    """The [S][T] hold mask of the *_streams_ex calls: a uint8 tensor of n = S * T elements."""
+    import torch
+    assert hold.dtype == torch.uint8 and hold.numel() == n, "hold"
+    return _ptr(hold)
+
+
 def _stream():
     import torch
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
@@ -348,11 +356,12 @@ class Device:
         return pcm, state_out
 
     def lc_decode_streams(self, channels, coeffs, ics, state_in, frames_per_stream, state_out=None, pcm=None,
-                          pcm_format=PCM_F32):
+                          pcm_format=PCM_F32, hold=None):
         """heaac_lc_decode_streams: S streams x T = frames_per_stream consecutive frames each.  The per-frame tensors
         are laid out as for lc_decode with n = S * T (frame t of stream s at s * T + t); state_in / state_out hold ONE
-        saved[] record of channels * 512 floats per stream (before frame 0 / after frame T - 1).  Returns
-        (pcm, state_out)."""
+        saved[] record of channels * 512 floats per stream (before frame 0 / after frame T - 1).  hold: None, or a
+        uint8 tensor of S * T elements, non-zero = frame held (heaac_lc_decode_streams_ex: skipped, zero PCM, the
+        stream's state passes over it).  Returns (pcm, state_out)."""
         import torch
         T = int(frames_per_stream)
         words = channels * 512
@@ -374,10 +383,17 @@ class Device:
         else:
             assert pcm.numel() == n * channels * 1024 and \
                 pcm.dtype == (torch.float32 if pcm_format == PCM_F32 else torch.int16), "pcm"
-        _check(lib().heaac_lc_decode_streams(self._h, channels, _ptr(coeffs), _ptr(ics), _ptr(state_in),
-                                             _ptr(state_out), _ptr(pcm), pcm_format, C.c_size_t(S), C.c_size_t(T),
-                                             _stream()),
-               "heaac_lc_decode_streams")
+        if hold is None:
+            _check(lib().heaac_lc_decode_streams(self._h, channels, _ptr(coeffs), _ptr(ics), _ptr(state_in),
+                                                 _ptr(state_out), _ptr(pcm), pcm_format, C.c_size_t(S), C.c_size_t(T),
+                                                 _stream()),
+                   "heaac_lc_decode_streams")
+        else:
+            d_hold = _hold_ptr(hold, n)
+            _check(lib().heaac_lc_decode_streams_ex(self._h, channels, _ptr(coeffs), _ptr(ics), _ptr(state_in),
+                                                    _ptr(state_out), _ptr(pcm), pcm_format, C.c_size_t(S), C.c_size_t(T),
+                                                    d_hold, _stream()),
+                   "heaac_lc_decode_streams_ex")
         return pcm, state_out
 
     # -- spectral tools before the IMDCT (M/S, intensity stereo, TNS), in place --
@@ -399,12 +415,13 @@ class Device:
         return coeffs
 
     def spectral_tools_streams(self, channels, coeffs, tools, frames_per_stream, rng=None, pred=None, rng_out=None,
-                               pred_out=None):
+                               pred_out=None, hold=None):
         """heaac_spectral_tools_streams: S streams x T = frames_per_stream consecutive frames each, in place on coeffs.
         coeffs / tools are laid out as for spectral_tools with n = S * T (frame t of stream s at s * T + t).  rng: int32
         [S] generator states, pred: float32 [S][channels][672][6] predictor states -- one record per stream, before
-        frame 0; the states after frame T - 1 go to rng_out / pred_out, or in place when those are None.  Returns
-        coeffs."""
+        frame 0; the states after frame T - 1 go to rng_out / pred_out, or in place when those are None.  hold: None, or a uint8
+        tensor of S * T elements, non-zero = frame held (heaac_spectral_tools_streams_ex: generator and predictors do
+        not move, the frame's coefficient row is unspecified afterwards).  Returns coeffs."""
         import torch
         T = int(frames_per_stream)
         assert T > 0, "frames_per_stream"
@@ -425,13 +442,17 @@ class Device:
             rng_out = rng
         if pred is not None and pred_out is None:
             pred_out = pred
-        _check(lib().heaac_spectral_tools_streams(self._h, channels, _ptr(coeffs), _ptr(tools),
-                                                  _ptr(rng) if rng is not None else None,
-                                                  _ptr(rng_out) if rng is not None else None,
-                                                  _ptr(pred) if pred is not None else None,
-                                                  _ptr(pred_out) if pred is not None else None,
-                                                  C.c_size_t(S), C.c_size_t(T), _stream()),
-               "heaac_spectral_tools_streams")
+        state = lambda: (_ptr(rng) if rng is not None else None, _ptr(rng_out) if rng is not None else None,
+                         _ptr(pred) if pred is not None else None, _ptr(pred_out) if pred is not None else None)
+        if hold is None:
+            _check(lib().heaac_spectral_tools_streams(self._h, channels, _ptr(coeffs), _ptr(tools), *state(),
+                                                      C.c_size_t(S), C.c_size_t(T), _stream()),
+                   "heaac_spectral_tools_streams")
+        else:
+            d_hold = _hold_ptr(hold, n)
+            _check(lib().heaac_spectral_tools_streams_ex(self._h, channels, _ptr(coeffs), _ptr(tools), *state(),
+                                                         C.c_size_t(S), C.c_size_t(T), d_hold, _stream()),
+                   "heaac_spectral_tools_streams_ex")
         return coeffs
 
     def spectral_tools_ex(self, channels, stages, coeffs, tools, rng=None, pred=None, cce=None, cce_coeffs=None):
@@ -540,10 +561,11 @@ class Device:
         return pcm, state_out
 
     def he_decode_streams(self, cfg, coeffs, ics, sbr, hdr, ps, state_in, frames_per_stream, state_out=None, pcm=None,
-                          pcm_format=PCM_F32, downsampled=False):
+                          pcm_format=PCM_F32, downsampled=False, hold=None):
         """heaac_he_decode_streams: S streams x T = frames_per_stream consecutive frames each.  The per-frame tensors
         are laid out as for he_decode with n = S * T (frame t of stream s at s * T + t); state_in / state_out hold ONE
-        record per stream (before frame 0 / after frame T - 1).  Returns (pcm, state_out)."""
+        record per stream (before frame 0 / after frame T - 1).  hold: None, or a uint8 tensor of S * T elements,
+        non-zero = frame held (heaac_he_decode_streams_ex).  Returns (pcm, state_out)."""
         import torch
         T = int(frames_per_stream)
         S = state_in.numel() // STATE_WORDS[cfg]
@@ -571,10 +593,17 @@ class Device:
             assert pcm.numel() == n * OUT_CH[cfg] * length and \
                 pcm.dtype == (torch.float32 if pcm_format == PCM_F32 else torch.int16), "pcm"
         n_hdr = hdr.numel() // SBR_HDR_DT.itemsize
-        _check(lib().heaac_he_decode_streams(self._h, cfg, 1 if downsampled else 0, _ptr(coeffs), _ptr(ics), _ptr(sbr),
-                                             _ptr(hdr), C.c_size_t(n_hdr), _ptr(ps), _ptr(state_in), _ptr(state_out),
-                                             _ptr(pcm), pcm_format, C.c_size_t(S), C.c_size_t(T), _stream()),
-               "heaac_he_decode_streams")
+        if hold is None:
+            _check(lib().heaac_he_decode_streams(self._h, cfg, 1 if downsampled else 0, _ptr(coeffs), _ptr(ics), _ptr(sbr),
+                                                 _ptr(hdr), C.c_size_t(n_hdr), _ptr(ps), _ptr(state_in), _ptr(state_out),
+                                                 _ptr(pcm), pcm_format, C.c_size_t(S), C.c_size_t(T), _stream()),
+                   "heaac_he_decode_streams")
+        else:
+            d_hold = _hold_ptr(hold, n)
+            _check(lib().heaac_he_decode_streams_ex(self._h, cfg, 1 if downsampled else 0, _ptr(coeffs), _ptr(ics), _ptr(sbr),
+                                                    _ptr(hdr), C.c_size_t(n_hdr), _ptr(ps), _ptr(state_in), _ptr(state_out),
+                                                    _ptr(pcm), pcm_format, C.c_size_t(S), C.c_size_t(T), d_hold, _stream()),
+                   "heaac_he_decode_streams_ex")
         return pcm, state_out
 
     def qmf_analysis(self, x, xhist, scale=32768.0):
@@ -679,21 +708,31 @@ def adts_split(buf):
 class Pipeline:
     """include/heaac_pipeline.h: access units in host memory -> int16 PCM in host memory, ticks overlapped."""
 
-    def __init__(self, aac_cfg, he_cfg, n_streams, threads=0):
+    def __init__(self, aac_cfg, he_cfg, n_streams, threads=0, frames_per_tick=1):
+        """frames_per_tick = T > 1: every tick carries T consecutive access units of each stream
+        (heaac_pipeline_create_streams), unit t of stream s at s * T + t."""
         self._h = C.c_void_p()
         self.n, self.ch, self.len = n_streams, OUT_CH[he_cfg], OUT_LEN[he_cfg]
+        self.T = int(frames_per_tick)
         if self.len == 2048 and aac_cfg.ext_sample_rate and aac_cfg.ext_sample_rate < 2 * aac_cfg.sample_rate:
             self.len = 1024                                # downsampled SBR: the output at the core rate
-        _check(lib().heaac_pipeline_create(C.byref(self._h), C.byref(aac_cfg), he_cfg, C.c_size_t(n_streams), threads),
-               "heaac_pipeline_create")
+        if self.T == 1:
+            _check(lib().heaac_pipeline_create(C.byref(self._h), C.byref(aac_cfg), he_cfg, C.c_size_t(n_streams), threads),
+                   "heaac_pipeline_create")
+        else:
+            _check(lib().heaac_pipeline_create_streams(C.byref(self._h), C.byref(aac_cfg), he_cfg, C.c_size_t(n_streams),
+                                                       C.c_size_t(max(self.T, 0)), threads),
+                   "heaac_pipeline_create_streams")
 
     def submit(self, aus, with_status=True):
-        """aus: n_streams access units (bytes).  Returns the parse status per stream (None without a status array)."""
-        assert len(aus) == self.n
+        """aus: n_streams * frames_per_tick access units (bytes; an empty one where a stream has run out).  Returns the
+        parse status per unit (None without a status array)."""
+        k = self.n * self.T
+        assert len(aus) == k
         keep = [C.create_string_buffer(bytes(a), len(a)) for a in aus]
-        ptrs = (C.c_char_p * self.n)(*[C.cast(k, C.c_char_p) for k in keep])
-        sizes = (C.c_int * self.n)(*[len(a) for a in aus])
-        status = np.zeros(self.n, np.int32) if with_status else None
+        ptrs = (C.c_char_p * k)(*[C.cast(q, C.c_char_p) for q in keep])
+        sizes = (C.c_int * k)(*[len(a) for a in aus])
+        status = np.zeros(k, np.int32) if with_status else None
         _check(lib().heaac_pipeline_submit(self._h, ptrs, sizes, status.ctypes.data_as(C.c_void_p) if with_status else None),
                "heaac_pipeline_submit")
         return status
@@ -702,10 +741,13 @@ class Pipeline:
         _check(lib().heaac_pipeline_submit(self._h, ptrs, sizes, None), "heaac_pipeline_submit")
 
     def collect(self):
-        """PCM of the oldest tick in flight: int16 [n][2048][channels] (a view of the pipeline's pinned buffer)."""
+        """PCM of the oldest tick in flight: int16 [n][len][channels], or [n][T][len][channels] with frames_per_tick =
+        T > 1 (a view of the pipeline's pinned buffer)."""
         p = C.POINTER(C.c_int16)()
         _check(lib().heaac_pipeline_collect(self._h, C.byref(p)), "heaac_pipeline_collect")
-        return np.ctypeslib.as_array(p, shape=(self.n, self.len, self.ch))
+        if self.T == 1:
+            return np.ctypeslib.as_array(p, shape=(self.n, self.len, self.ch))
+        return np.ctypeslib.as_array(p, shape=(self.n, self.T, self.len, self.ch))
 
     def timing(self):
         ms = (C.c_float * 4)()

@@ -240,6 +240,17 @@ extern "C" int heaac_lc_decode_streams(HeaacDevice *dev, int channels,
                                        void *d_pcm, int pcm_format,
                                        size_t n_streams, size_t frames_per_stream, void *stream)
 {
+    return heaac_lc_decode_streams_ex(dev, channels, d_coeffs, d_ics, d_state_in, d_state_out, d_pcm, pcm_format,
+                                      n_streams, frames_per_stream, NULL, stream);
+}
+
+extern "C" int heaac_lc_decode_streams_ex(HeaacDevice *dev, int channels,
+                                          const float *d_coeffs, const HeaacIcs *d_ics,
+                                          const float *d_state_in, float *d_state_out,
+                                          void *d_pcm, int pcm_format,
+                                          size_t n_streams, size_t frames_per_stream,
+                                          const uint8_t *d_hold, void *stream)
+{
     if (!dev || channels < 1 || channels > 2 || !pcm_format_ok(pcm_format) || frames_per_stream == 0)
         return HEAAC_ERR_ARG;
     if (n_streams == 0)
@@ -250,12 +261,12 @@ extern "C" int heaac_lc_decode_streams(HeaacDevice *dev, int channels,
     const size_t frame_bytes = (size_t)channels * 1024 * sizeof(float);
     if (n_streams > SIZE_MAX / frames_per_stream || n_streams * frames_per_stream > SIZE_MAX / frame_bytes)
         return HEAAC_ERR_ARG;
-    // one frame per stream: the per-frame arrays and the state are exactly the batch call's
-    if (frames_per_stream == 1)
+    // one frame per stream: the per-frame arrays and the state are exactly the batch call's (which knows no mask)
+    if (frames_per_stream == 1 && !d_hold)
         return heaac_launch_lc(dev->d_tab, dev->d_rev, channels, d_coeffs, d_ics, d_state_in, d_state_out,
                                d_pcm, pcm_format, n_streams, (hipStream_t)stream);
     return heaac_launch_lc_streams(dev->d_tab, dev->d_rev, channels, d_coeffs, d_ics, d_state_in, d_state_out,
-                                   d_pcm, pcm_format, n_streams, frames_per_stream, (hipStream_t)stream);
+                                   d_pcm, pcm_format, n_streams, frames_per_stream, d_hold, (hipStream_t)stream);
 }
 
 extern "C" int heaac_spectral_tools_batch(HeaacDevice *dev, int channels, float *d_coeffs,
@@ -293,6 +304,17 @@ extern "C" int heaac_spectral_tools_streams(HeaacDevice *dev, int channels, floa
                                             const HeaacPredictorState *d_pred_in, HeaacPredictorState *d_pred_out,
                                             size_t n_streams, size_t frames_per_stream, void *stream)
 {
+    return heaac_spectral_tools_streams_ex(dev, channels, d_coeffs, d_tools, d_rng_in, d_rng_out, d_pred_in, d_pred_out,
+                                           n_streams, frames_per_stream, NULL, stream);
+}
+
+extern "C" int heaac_spectral_tools_streams_ex(HeaacDevice *dev, int channels, float *d_coeffs,
+                                               const HeaacToolsFrame *d_tools,
+                                               const int32_t *d_rng_in, int32_t *d_rng_out,
+                                               const HeaacPredictorState *d_pred_in, HeaacPredictorState *d_pred_out,
+                                               size_t n_streams, size_t frames_per_stream,
+                                               const uint8_t *d_hold, void *stream)
+{
     if (!dev || channels < 1 || channels > 2 || frames_per_stream == 0 || (d_rng_in && !d_rng_out) ||
         (d_pred_in && !d_pred_out))
         return HEAAC_ERR_ARG;
@@ -309,15 +331,16 @@ extern "C" int heaac_spectral_tools_streams(HeaacDevice *dev, int channels, floa
         n > 0x7fffffffull * 256 / (3 * (size_t)channels))
         return HEAAC_ERR_ARG;
     // one frame per stream: the per-frame arrays and the state are exactly the batch call's
-    if (frames_per_stream == 1)
+    // (the batch kernels know no mask: with one, every case runs the chain kernel)
+    if (frames_per_stream == 1 && !d_hold)
         return heaac_launch_spectral_tools(channels, d_coeffs, d_tools, d_rng_in, d_rng_out, d_pred_in, d_pred_out,
                                            HEAAC_TOOLS_ALL, NULL, NULL, 0, n_streams, (hipStream_t)stream);
     // no state: every frame stands alone, one batch call over the S * T frames
-    if (!d_rng_in && !d_pred_in)
+    if (!d_rng_in && !d_pred_in && !d_hold)
         return heaac_launch_spectral_tools(channels, d_coeffs, d_tools, NULL, NULL, NULL, NULL, HEAAC_TOOLS_ALL,
                                            NULL, NULL, 0, n, (hipStream_t)stream);
     return heaac_launch_spectral_tools_streams(channels, d_coeffs, d_tools, d_rng_in, d_rng_out, d_pred_in,
-                                               d_pred_out, n_streams, frames_per_stream, (hipStream_t)stream);
+                                               d_pred_out, n_streams, frames_per_stream, d_hold, (hipStream_t)stream);
 }
 
 // The HE calls behind their argument checks: n_streams streams of T consecutive frames each.  Whole streams per
@@ -326,7 +349,7 @@ extern "C" int heaac_spectral_tools_streams(HeaacDevice *dev, int channels, floa
 static int he_walk(HeaacDevice *dev, int cfg, int flags, const float *d_coeffs, const HeaacIcs *d_ics,
                    const HeaacSbrFrame *d_sbr, const HeaacSbrHeader *d_hdr, size_t n_hdr, const HeaacPsFrame *d_ps,
                    const float *d_state_in, float *d_state_out, void *d_pcm, int pcm_format,
-                   size_t n_streams, size_t T, hipStream_t s)
+                   size_t n_streams, size_t T, const uint8_t *d_hold, hipStream_t s)
 {
     const HeaacCfgShape shape = heaac_cfg_shape(cfg);
     const size_t ncore = shape.ncore, words = shape.words;
@@ -362,7 +385,8 @@ static int he_walk(HeaacDevice *dev, int cfg, int flags, const float *d_coeffs, 
         float *ws_X = ws_W + dev->chunk * WS_W_FLOATS;
         unsigned char *xtop = dev->d_aux + HE_ZERO_BYTES + 2 * (size_t)k * dev->chunk;
         hipStream_t ls = lanes ? dev->lane[k] : s;
-        rc = T == 1
+        // (the batch kernels know no mask: with one, T = 1 runs the streams kernels too)
+        rc = T == 1 && !d_hold
             ? heaac_launch_he(dev->d_tab, dev->d_rev, cfg, d_coeffs + f0 * ncore * 1024, d_ics + f0 * ncore,
                               d_sbr + f0, d_hdr, hdrs, d_ps ? d_ps + f0 : NULL,
                               d_state_in + s0 * words, d_state_out + s0 * words,
@@ -372,7 +396,7 @@ static int he_walk(HeaacDevice *dev, int cfg, int flags, const float *d_coeffs, 
                                       d_sbr + f0, d_hdr, hdrs, d_ps ? d_ps + f0 : NULL,
                                       d_state_in + s0 * words, d_state_out + s0 * words,
                                       (char *)d_pcm + f0 * pcm_bytes, pcm_format, ws_W, ws_X, dev->d_queue + 16 * k,
-                                      xtop, (const float *)dev->d_aux, ns, T, flags, ls);
+                                      xtop, (const float *)dev->d_aux, ns, T, flags, d_hold ? d_hold + f0 : NULL, ls);
     }
     if (lanes) {
         // always rejoin, also after a failed launch (a capture must not be left forked)
@@ -401,7 +425,7 @@ extern "C" int heaac_he_decode_batch_ex(HeaacDevice *dev, int cfg, int flags,
         (cfg == HEAAC_CFG_HEV2 && !d_ps))
         return HEAAC_ERR_ARG;
     return he_walk(dev, cfg, flags, d_coeffs, d_ics, d_sbr, d_hdr, n_hdr, d_ps, d_state_in, d_state_out, d_pcm,
-                   pcm_format, n, 1, (hipStream_t)stream);
+                   pcm_format, n, 1, NULL, (hipStream_t)stream);
 }
 
 extern "C" int heaac_he_decode_batch(HeaacDevice *dev, int cfg,
@@ -426,8 +450,22 @@ extern "C" int heaac_he_decode_streams(HeaacDevice *dev, int cfg, int flags,
                                        void *d_pcm, int pcm_format,
                                        size_t n_streams, size_t frames_per_stream, void *stream)
 {
+    return heaac_he_decode_streams_ex(dev, cfg, flags, d_coeffs, d_ics, d_sbr, d_hdr, n_hdr, d_ps, d_state_in, d_state_out,
+                                      d_pcm, pcm_format, n_streams, frames_per_stream, NULL, stream);
+}
+
+extern "C" int heaac_he_decode_streams_ex(HeaacDevice *dev, int cfg, int flags,
+                                          const float *d_coeffs, const HeaacIcs *d_ics,
+                                          const HeaacSbrFrame *d_sbr,
+                                          const HeaacSbrHeader *d_hdr, size_t n_hdr,
+                                          const HeaacPsFrame *d_ps,
+                                          const float *d_state_in, float *d_state_out,
+                                          void *d_pcm, int pcm_format,
+                                          size_t n_streams, size_t frames_per_stream,
+                                          const uint8_t *d_hold, void *stream)
+{
     if (!dev || !he_cfg_ok(cfg) || !pcm_format_ok(pcm_format) || (flags & ~HEAAC_HE_DOWNSAMPLED) ||
-        frames_per_stream == 0 || frames_per_stream > dev->chunk)
+        frames_per_stream == 0 || frames_per_stream > heaac_device_max_frames_per_stream(dev))
         return HEAAC_ERR_ARG;
     if (n_streams == 0)
         return HEAAC_OK;
@@ -435,7 +473,7 @@ extern "C" int heaac_he_decode_streams(HeaacDevice *dev, int cfg, int flags,
         (cfg == HEAAC_CFG_HEV2 && !d_ps))
         return HEAAC_ERR_ARG;
     return he_walk(dev, cfg, flags, d_coeffs, d_ics, d_sbr, d_hdr, n_hdr, d_ps, d_state_in, d_state_out, d_pcm,
-                   pcm_format, n_streams, frames_per_stream, (hipStream_t)stream);
+                   pcm_format, n_streams, frames_per_stream, d_hold, (hipStream_t)stream);
 }
 
 extern "C" int heaac_qmf_analysis_batch(HeaacDevice *dev, const float *d_in,
@@ -515,6 +553,10 @@ extern "C" int heaac_debug_xbands(HeaacDevice *dev, unsigned char *host_out, siz
     return hipMemcpy(host_out, dev->d_aux + HE_ZERO_BYTES, 2 * n_frames, hipMemcpyDeviceToHost) == hipSuccess
                ? HEAAC_OK : HEAAC_ERR_HIP;
 }
+
+// internal (host_common.h): the most frames per stream the HE streams calls take on this device -- whole streams go
+// through one workspace set of `chunk` frames
+size_t heaac_device_max_frames_per_stream(const HeaacDevice *dev) { return dev ? dev->chunk : 0; }
 
 // internal: device table pointers for shim.hip
 extern "C" const float *heaac_device_tables(HeaacDevice *dev, const uint16_t **rev)

@@ -54,6 +54,11 @@ int heaac_failed_lists(hipStream_t s, const unsigned char *failed, size_t n, uns
 // old area is in flight then, the caller frees it) and *rows = first, doubled until it holds them, at most n.
 int heaac_park_grow(hipStream_t s, size_t needed, size_t have, size_t first, size_t n, size_t *rows);
 
+// ---- the device (capi.hip) ----
+// The most frames per stream heaac_he_decode_streams(_ex) takes on this device: a stream's frames go through one
+// workspace set.  The call's own argument check and heaac_pipeline_create_streams both ask here.
+size_t heaac_device_max_frames_per_stream(const HeaacDevice *dev);
+
 // ---- per-stream device state at create ----
 // ac->random_state of n streams (aacdec.c:558); reset_predict_state (aacdec.c:507-515) for `count` predictors
 int heaac_seed_generators(int32_t *d_rng, size_t n);                         // 1: done

@@ -35,6 +35,12 @@ __device__ __forceinline__ void wave_sync()
 // ---------------------------------------------------------------------------
 typedef float v2f __attribute__((ext_vector_type(2)));
 
+// The hold mask of the *_streams_ex calls ([S][T] bytes, non-zero = frame held) reaches a streams kernel as an optional
+// trailing argument: a parameter pack `Hold... hold` that is empty in the instantiations the plain calls launch -- their
+// signature and their code stay what they were -- and one `const uint8_t *` in the instantiations with a mask.
+__device__ __forceinline__ const uint8_t *hold_mask() { return nullptr; }
+__device__ __forceinline__ const uint8_t *hold_mask(const uint8_t *p) { return p; }
+
 // One channel of the X hand-over workspace between the HF / PS kernels and the synthesis kernels: [38 slots][64 bands]
 // [re, im] floats (slots 32..37: the hybrid filters' look-ahead).  A frame's record is two of them (left / mono, right).
 // (Re and im side by side: a lane's value leaves as ONE 8-byte store, a row of 48 bands is exactly three 128-byte lines.)

@@ -98,14 +98,19 @@ static_assert(CA_U <= 2 * 2 * C2_TSTRIDE, "u rows of channel 0 lie over the core
 
 // STRIDED (heaac_he_decode_streams): frame f of the launch reads its coefficients and ics at record f * rstride (frame
 // t of stream f, the pointers offset by t), its state at f and its W at unit f * ncore + ch of the launch.
-template <bool STRIDED>
+// Hold (heaac_he_decode_streams_ex; STRIDED only; k_common.h hold_mask): byte f * rstride != 0 skips frame f of the
+// launch -- no record read, no state or W written.  The two units of a pair may belong to different frames (ncore 1):
+// a held half takes the other half's unit through the transform (the result is dropped) and sits every per-unit step out.
+template <bool STRIDED, class... Hold>
 __global__ __launch_bounds__(CA_WAVES * WAVE)
 void k_core_ana(const float *__restrict__ g_tab, const uint16_t *__restrict__ g_rev,
                 const float *__restrict__ g_coeffs, const HeaacIcs *__restrict__ g_ics,
                 const float *g_state_in, float *g_state_out, int state_words,
                 int ncore, int off_saved0, int off_sbr0,
-                float *__restrict__ g_W, float scale, unsigned long long n_units, unsigned long long rstride)
+                float *__restrict__ g_W, float scale, unsigned long long n_units, unsigned long long rstride, Hold... hold)
 {
+    constexpr bool HOLD = sizeof...(Hold) != 0;
+    static_assert(STRIDED || !HOLD, "the batch form has no hold mask");
     // record index of unit u (= frame u / ncore, channel u % ncore)
     auto rec = [&](unsigned long long u) -> unsigned long long {
         if constexpr (STRIDED) return (u / ncore) * rstride * ncore + u % ncore;
@@ -152,7 +157,16 @@ void k_core_ana(const float *__restrict__ g_tab, const uint16_t *__restrict__ g_
         const unsigned long long u0 = 2 * pr;
         const bool have1 = u0 + 1 < n_units;                            // uniform
         const unsigned long long u1 = have1 ? u0 + 1 : u0;
-        const unsigned long long r0 = rec(u0), r1 = rec(u1);
+        unsigned long long r0 = rec(u0), r1 = rec(u1);
+        [[maybe_unused]] bool run0 = true, run1 = have1;                // unit c of the pair is worked on (uniform)
+        if constexpr (HOLD) {
+            const uint8_t *g_hold = hold_mask(hold...);
+            run0 = __builtin_amdgcn_readfirstlane((int)g_hold[(u0 / ncore) * rstride]) == 0;
+            run1 = have1 && __builtin_amdgcn_readfirstlane((int)g_hold[(u1 / ncore) * rstride]) == 0;
+            if (!run0 && !run1) continue;
+            if (!run0) r0 = r1;
+            if (!run1) r1 = r0;
+        }
         const HeaacIcs ics0 = g_ics[r0], ics1 = g_ics[r1];
         int lane = opaque(lane0);      // lane-derived addresses are recomputed per pair, not hoisted and spilled
         core2_stage_coeffs(reinterpret_cast<float *>(T0), g_coeffs + r0 * 1024, lane);
@@ -169,6 +183,9 @@ void k_core_ana(const float *__restrict__ g_tab, const uint16_t *__restrict__ g_
 #pragma unroll
         for (int c = 0; c < 2; c++) {
             if (c == 1 && !have1) break;
+            if constexpr (HOLD) {
+                if (!(c ? run1 : run0)) continue;
+            }
             const unsigned long long u = c ? u1 : u0;
             const unsigned long long f = u / ncore;
             const int ch = (int)(u - f * ncore);
@@ -197,6 +214,9 @@ void k_core_ana(const float *__restrict__ g_tab, const uint16_t *__restrict__ g_
 #pragma unroll
         for (int c = 0; c < 2; c++) {
             if (c == 1 && !have1) break;
+            if constexpr (HOLD) {
+                if (!(c ? run1 : run0)) continue;
+            }
             const unsigned long long u = c ? u1 : u0;
             const unsigned long long f = u / ncore;
             const int ch = (int)(u - f * ncore);
@@ -251,6 +271,9 @@ void k_core_ana(const float *__restrict__ g_tab, const uint16_t *__restrict__ g_
 #pragma unroll
         for (int c = 0; c < 2; c++) {
             if (c == 1 && !have1) break;
+            if constexpr (HOLD) {
+                if (!(c ? run1 : run0)) continue;
+            }
             const float *uu = c ? w.x0u1 : w.tu;
             float *Wo = g_W + (c ? u1 : u0) * 2048;
             // four rows per pass, sixteen bytes per lane: 8 stores of 1 KiB instead of 32 of 256 bytes (the LDS rows have
@@ -267,14 +290,16 @@ void k_core_ana(const float *__restrict__ g_tab, const uint16_t *__restrict__ g_
 }
 
 // STRIDED: frame f's SBR record is g_sbr[f * rstride] (see k_core_ana)
-template <bool STRIDED>
+// Hold: as k_core_ana -- the units of a held frame are skipped
+template <bool STRIDED, class... Hold>
 __global__ __launch_bounds__(HF_WAVES * WAVE)
 void k_hfadj(const float *__restrict__ g_tab,
              const HeaacSbrFrame *__restrict__ g_sbr, const HeaacSbrHeader *__restrict__ g_hdr, unsigned n_hdr,
              const float *g_W, const float *g_state_in, float *g_state_out, int state_words,
              int ncore, int off_sbr0, float *g_X, unsigned long long n_units, unsigned *g_queue,
-             unsigned char *__restrict__ g_xtop, unsigned long long rstride)
+             unsigned char *__restrict__ g_xtop, unsigned long long rstride, Hold... hold)
 {
+    static_assert(STRIDED || sizeof...(Hold) == 0, "the batch form has no hold mask");
     __shared__ float s_xlow[HF_WAVES][HF_XLOW_WORDS], s_aux[HF_WAVES][HF_AUX_WORDS], s_rec[HF_WAVES][HF_REC_WORDS];
     __shared__ float s_noise[1024];              // sbr_noise_table, staged once per workgroup
     wg_copy_f4(s_noise, g_tab + TB_NOISE, 1024);
@@ -291,6 +316,9 @@ void k_hfadj(const float *__restrict__ g_tab,
       for (int qi = 0; qi < 2 && ub + qi < n_units; qi++) {
         const unsigned long long u = ub + qi;
         const unsigned long long f = u / ncore;
+        if constexpr (sizeof...(Hold) != 0) {
+            if (__builtin_amdgcn_readfirstlane((int)hold_mask(hold...)[f * rstride])) continue;
+        }
         const int ch = (int)(u - f * ncore);
         const int off = off_sbr0 + ch * HEAAC_ST_SBR;
         const HeaacSbrFrame *sbr = STRIDED ? &g_sbr[f * rstride] : &g_sbr[f];
@@ -596,14 +624,18 @@ void k_synth(const float *__restrict__ g_tab, const float *g_X,
 // next frame -- or, after the last, the X rows and ring of the next ticket -- are on their way into registers.
 // X of frame (s, t) is unit t * n_streams + s of the workspace (the stages before run one launch per t); its PCM is
 // record s * T + t.
-template <int FMT>
+// Hold (k_common.h hold_mask): byte st * T + t != 0 -- the frame's X unit was never written (it may be fetched, it is
+// not used), its PCM is zero bytes and the ring stays in cur.h for the next frame (or goes to the state record after the
+// last).
+template <int FMT, class... Hold>
 __global__ __launch_bounds__(SYN_WAVES_F32 * WAVE)
 void k_synth_streams(const float *__restrict__ g_tab, const float *g_X,
                      const float *g_state_in, float *g_state_out, int state_words, int off_syn0,
                      int nout, void *__restrict__ g_pcm, float scale, float bias,
                      unsigned long long n_streams, unsigned T, unsigned *g_queue,
-                     const unsigned char *__restrict__ g_xtop, const float *__restrict__ g_zero)
+                     const unsigned char *__restrict__ g_xtop, const float *__restrict__ g_zero, Hold... hold)
 {
+    constexpr bool HOLD = sizeof...(Hold) != 0;
     constexpr int NW = SYN_WAVES_F32;
     __shared__ SynLdsT<NW> S;
     for (int i = threadIdx.x; i < 640; i += blockDim.x) S.win[i] = g_tab[TB_QMF_US + i];
@@ -639,11 +671,39 @@ void k_synth_streams(const float *__restrict__ g_tab, const float *g_X,
         const int ch = (int)(c - st * nout);
         for (unsigned t = 0; t < T; t++) {
             const bool last = t + 1 == T;
-            syn_rows<false>(S, w, cur, lane);
-            wave_sync();
+            [[maybe_unused]] bool held = false;                          // uniform
+            if constexpr (HOLD) {
+                held = __builtin_amdgcn_readfirstlane((int)hold_mask(hold...)[st * T + t]) != 0;
+                if (held && last) {
+                    // the chain ends on a held frame: the ring goes out from the registers, before the next chain's comes in
+                    float *v_out = g_state_out + st * state_words + off_syn0 + ch * HEAAC_ST_SYNTH;
+#pragma unroll
+                    for (int q = 0; q < 18; q++) syn_st(v_out + lane + 64 * q, cur.h[q]);
+                }
+            }
+            if (!HOLD || !held) {
+                syn_rows<false>(S, w, cur, lane);
+                wave_sync();
+            }
             if (!last) load_x(st, t + 1, ch, cur);
             else if (c1 < n_chains) load_chain(c1, cur);
             const unsigned long long r = st * T + t;
+            if constexpr (HOLD) {
+                if (held) {
+                    // (interleaved int16: 2-byte stores at stride nout, each chain of a stereo stream writes half of every
+                    // line, as the frame's own stores do; held frames are the exception, so it is left at that)
+                    if constexpr (FMT == HEAAC_PCM_F32_PLANAR) {
+                        float *o = reinterpret_cast<float *>(g_pcm) + (r * nout + ch) * 2048;
+#pragma nounroll
+                        for (int q = lane; q < 2048; q += WAVE) o[q] = 0.0f;
+                    } else {
+                        int16_t *o = reinterpret_cast<int16_t *>(g_pcm) + r * 2048 * nout;
+#pragma nounroll
+                        for (int q = lane; q < 2048; q += WAVE) o[q * nout + ch] = 0;
+                    }
+                    continue;
+                }
+            }
             if constexpr (FMT == HEAAC_PCM_F32_PLANAR) {
                 float *o = reinterpret_cast<float *>(g_pcm) + (r * nout + ch) * 2048;
                 syn_poly<1>(S, w, scale, bias, lane, [&](int i, int n, float v) { syn_st(o + 64 * i + n, v); });
@@ -872,13 +932,16 @@ void k_synth_ds(const float *__restrict__ g_tab, const float *g_X,
 // k_synth_ds in the streams form: one wave per (stream, output channel), its T frames in t order.  The ring (the
 // first 576 words of the channel's synthesis state) is loaded once, moves from v rows 0..8 to rows 32..40 between
 // frames, and is stored once; the rest of the record passes through.  X and PCM as k_synth_streams.
-template <int FMT>
+// Hold (k_common.h hold_mask): a held frame stores zero bytes and leaves the v rows alone; `fresh` says whether the
+// ring is in rows 0..8 (a frame has run since it was loaded or moved) or still in rows 32..40.
+template <int FMT, class... Hold>
 __global__ __launch_bounds__(DS_WAVES * WAVE)
 void k_synth_ds_streams(const float *__restrict__ g_tab, const float *g_X,
                         const float *g_state_in, float *g_state_out, int state_words, int off_syn0,
                         int nout, void *__restrict__ g_pcm, float scale, float bias,
-                        unsigned long long n_streams, unsigned T)
+                        unsigned long long n_streams, unsigned T, Hold... hold)
 {
+    constexpr bool HOLD = sizeof...(Hold) != 0;
     __shared__ SynDsLds S;
     syn_ds_lds_init(S, g_tab);
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / WAVE), lane = threadIdx.x % WAVE;
@@ -893,8 +956,27 @@ void k_synth_ds_streams(const float *__restrict__ g_tab, const float *g_X,
         if (v_out != v_in)
             for (int q = 576 + lane; q < HEAAC_ST_SYNTH; q += WAVE) v_out[q] = v_in[q];
         for (int q = lane; q < 576; q += WAVE) vb[(32 + (q >> 6)) * DS_STRIDE + (q & 63)] = v_in[q];
+        [[maybe_unused]] bool fresh = false;
         for (unsigned t = 0; t < T; t++) {
-            if (t) {
+            bool move = t;
+            if constexpr (HOLD) {
+                if (__builtin_amdgcn_readfirstlane((int)hold_mask(hold...)[st * T + t])) {
+                    const unsigned long long r = st * T + t;
+                    if constexpr (FMT == HEAAC_PCM_F32_PLANAR) {
+                        float *o = reinterpret_cast<float *>(g_pcm) + (r * nout + ch) * 1024;
+#pragma nounroll
+                        for (int q = lane; q < 1024; q += WAVE) o[q] = 0.0f;
+                    } else {
+                        int16_t *o = reinterpret_cast<int16_t *>(g_pcm) + r * 1024 * nout + ch;
+#pragma nounroll
+                        for (int q = lane; q < 1024; q += WAVE) o[q * nout] = 0;
+                    }
+                    continue;
+                }
+                move = fresh;
+                fresh = true;
+            }
+            if (move) {
                 // the frame before left its new ring in rows 0..8 (its last reads of rows 32..40 are behind the
                 // wave_sync that ends synth_ds_channel); lane = column
                 float h[9];
@@ -915,7 +997,13 @@ void k_synth_ds_streams(const float *__restrict__ g_tab, const float *g_X,
                                                [&](int i, int nn, float v) { o[(32 * i + nn) * nout] = (int16_t)pcm_int16<FMT>(v); });
             }
         }
-        for (int q = lane; q < 576; q += WAVE) v_out[q] = vb[(q >> 6) * DS_STRIDE + (q & 63)];
+        if constexpr (HOLD) {
+            // (every frame held: the ring is still in rows 32..40)
+            const int row0 = fresh ? 0 : 32;
+            for (int q = lane; q < 576; q += WAVE) v_out[q] = vb[(row0 + (q >> 6)) * DS_STRIDE + (q & 63)];
+        } else {
+            for (int q = lane; q < 576; q += WAVE) v_out[q] = vb[(q >> 6) * DS_STRIDE + (q & 63)];
+        }
         wave_sync();
     }
 }
@@ -982,9 +1070,9 @@ extern "C" int heaac_launch_he(const float *d_tab, const uint16_t *d_rev, int cf
         // frames with another PS layout (it skips the rest)
         const int off_ps = off_syn0 + 2 * HEAAC_ST_SYNTH;
         int rc = heaac_launch_hfps(d_tab, d_sbr, d_hdr, n_hdr, d_ps, d_ws_W, d_state_in, d_state_out, words,
-                                   off_sbr0, off_ps, d_ws_X, n, d_queue, d_xtop, 1, s);
+                                   off_sbr0, off_ps, d_ws_X, n, d_queue, d_xtop, 1, nullptr, s);
         if (rc != HEAAC_OK) return rc;
-        rc = heaac_launch_ps(d_tab, d_ps, d_sbr, d_hdr, n_hdr, d_state_in, d_state_out, words, off_ps, d_ws_X, n, 2, 1, s);
+        rc = heaac_launch_ps(d_tab, d_ps, d_sbr, d_hdr, n_hdr, d_state_in, d_state_out, words, off_ps, d_ws_X, n, 2, 1, nullptr, s);
         if (rc != HEAAC_OK) return rc;
     } else {
         hipLaunchKernelGGL(k_hfadj<false>, dim3(he_grid((units + 1) / 2, HF_WAVES)), dim3(HF_WAVES * WAVE), 0, s,
@@ -992,7 +1080,7 @@ extern "C" int heaac_launch_he(const float *d_tab, const uint16_t *d_rev, int cf
                            d_ws_X, units, d_queue + 1, cfg == HEAAC_CFG_HEV2 ? nullptr : d_xtop, 1ull);
         if (cfg == HEAAC_CFG_HEV2) {
             int rc = heaac_launch_ps(d_tab, d_ps, d_sbr, d_hdr, n_hdr, d_state_in, d_state_out, words,
-                                     off_syn0 + 2 * HEAAC_ST_SYNTH, d_ws_X, n, 3, 1, s);
+                                     off_syn0 + 2 * HEAAC_ST_SYNTH, d_ws_X, n, 3, 1, nullptr, s);
             if (rc != HEAAC_OK) return rc;
         }
     }
@@ -1029,6 +1117,15 @@ extern "C" int heaac_launch_he(const float *d_tab, const uint16_t *d_rev, int cf
     return hipGetLastError() == hipSuccess ? HEAAC_OK : HEAAC_ERR_HIP;
 }
 
+// A streams kernel on stream `s` (a variable of the caller): the plain instantiation, or with a hold mask the one that
+// takes it as its trailing argument (k_common.h hold_mask)
+#define HE_LAUNCH_STREAMS(PLAIN, HOLD, mask, grid, block, ...)                                        \
+    do {                                                                                          \
+        const uint8_t *he_mask_ = (mask);                                                         \
+        if (he_mask_) hipLaunchKernelGGL(HOLD, grid, block, 0, s, __VA_ARGS__, he_mask_);         \
+        else hipLaunchKernelGGL(PLAIN, grid, block, 0, s, __VA_ARGS__);                           \
+    } while (0)
+
 // The streams form (heaac_he_decode_streams) over one chunk of whole streams: n_streams x T frames, frame (s, t) at
 // record s * T + t of the per-frame arrays, the state one record per stream.  The core + analysis and HF (+ PS) stages
 // run one launch per t, in t order, over the n_streams frames of position t (the record stride is T; frame t reads the
@@ -1042,7 +1139,7 @@ extern "C" int heaac_launch_he_streams(const float *d_tab, const uint16_t *d_rev
                                        void *d_pcm, int pcm_format,
                                        float *d_ws_W, float *d_ws_X, unsigned *d_queue,
                                        unsigned char *d_xtop, const float *d_zero,
-                                       size_t n_streams, size_t T, int flags, hipStream_t s)
+                                       size_t n_streams, size_t T, int flags, const uint8_t *d_hold, hipStream_t s)
 {
     const int ncore = cfg == HEAAC_CFG_HEV1 ? 2 : 1;
     const int nout  = cfg == HEAAC_CFG_HEV1_MONO ? 1 : 2;
@@ -1060,28 +1157,37 @@ extern "C" int heaac_launch_he_streams(const float *d_tab, const uint16_t *d_rev
     const bool simd = pcm_format == HEAAC_PCM_S16_INTERLEAVED_SSE2;
     const float sf_scale = simd ? -1.0f / 1024.0f : HEAAC_SF_SCALE;
     if (hipMemsetAsync(d_xtop, 64, 2 * n_streams * T, s) != hipSuccess) return HEAAC_ERR_HIP;
+    // With a hold mask the first frame of a stream that runs may be any t, or none: the state is carried over in front
+    // of the launches and every stage reads and writes d_state_out.
+    if (d_hold && d_state_in != d_state_out) {
+        if (hipMemcpyAsync(d_state_out, d_state_in, n_streams * (size_t)words * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess)
+            return HEAAC_ERR_HIP;
+        d_state_in = d_state_out;
+    }
     for (size_t t = 0; t < T; t++) {
         const float *st_in = t ? d_state_out : d_state_in;
         float *W = d_ws_W + t * units * 2048;
         float *X = d_ws_X + t * n_streams * 2 * HE_X_CHANNEL;
         unsigned char *xtop = d_xtop + 2 * t * n_streams;
-        hipLaunchKernelGGL(k_core_ana<true>, dim3(he_grid((units + 1) / 2, CA_WAVES)), dim3(CA_WAVES * WAVE), 0, s,
-                           d_tab, d_rev, d_coeffs + t * ncore * 1024, d_ics + t * ncore, st_in, d_state_out, words, ncore,
-                           off_saved0, off_sbr0, W, 1 / (-1024 * sf_scale), units, (unsigned long long)T);
+        HE_LAUNCH_STREAMS((k_core_ana<true>), (k_core_ana<true, const uint8_t *>), d_hold ? d_hold + t : nullptr,
+                          dim3(he_grid((units + 1) / 2, CA_WAVES)), dim3(CA_WAVES * WAVE),
+                          d_tab, d_rev, d_coeffs + t * ncore * 1024, d_ics + t * ncore, st_in, d_state_out, words, ncore,
+                          off_saved0, off_sbr0, W, 1 / (-1024 * sf_scale), units, (unsigned long long)T);
         // queue heads (k_hfps: [0], k_hfadj: [1]; k_synth_streams: [2], which no launch before it draws from)
         if (hipMemsetAsync(d_queue, 0, 64, s) != hipSuccess) return HEAAC_ERR_HIP;
         if (cfg == HEAAC_CFG_HEV2) {
             const int off_ps = off_syn0 + 2 * HEAAC_ST_SYNTH;
             int rc = heaac_launch_hfps(d_tab, d_sbr + t, d_hdr, n_hdr, d_ps + t, W, st_in, d_state_out, words,
-                                       off_sbr0, off_ps, X, n_streams, d_queue, xtop, T, s);
+                                       off_sbr0, off_ps, X, n_streams, d_queue, xtop, T, d_hold ? d_hold + t : nullptr, s);
             if (rc != HEAAC_OK) return rc;
             rc = heaac_launch_ps(d_tab, d_ps + t, d_sbr + t, d_hdr, n_hdr, st_in, d_state_out, words, off_ps, X,
-                                 n_streams, 2, T, s);
+                                 n_streams, 2, T, d_hold ? d_hold + t : nullptr, s);
             if (rc != HEAAC_OK) return rc;
         } else {
-            hipLaunchKernelGGL(k_hfadj<true>, dim3(he_grid((units + 1) / 2, HF_WAVES)), dim3(HF_WAVES * WAVE), 0, s,
-                               d_tab, d_sbr + t, d_hdr, n_hdr, W, st_in, d_state_out, words, ncore, off_sbr0,
-                               X, units, d_queue + 1, xtop, (unsigned long long)T);
+            HE_LAUNCH_STREAMS((k_hfadj<true>), (k_hfadj<true, const uint8_t *>), d_hold ? d_hold + t : nullptr,
+                              dim3(he_grid((units + 1) / 2, HF_WAVES)), dim3(HF_WAVES * WAVE),
+                              d_tab, d_sbr + t, d_hdr, n_hdr, W, st_in, d_state_out, words, ncore, off_sbr0,
+                              X, units, d_queue + 1, xtop, (unsigned long long)T);
         }
     }
     const float scale = -1024 * sf_scale, bias = simd ? 0.0f : HEAAC_ADD_BIAS;
@@ -1090,29 +1196,24 @@ extern "C" int heaac_launch_he_streams(const float *d_tab, const uint16_t *d_rev
     const unsigned Tu = (unsigned)T;
     if (flags & HEAAC_HE_DOWNSAMPLED) {
         const dim3 gd(he_grid(chains, DS_WAVES)), bd(DS_WAVES * WAVE);
-        if (pcm_format == HEAAC_PCM_F32_PLANAR)
-            hipLaunchKernelGGL((k_synth_ds_streams<HEAAC_PCM_F32_PLANAR>), gd, bd, 0, s, d_tab, d_ws_X, d_state_in,
-                               d_state_out, words, off_syn0, nout, d_pcm, scale, bias, ns, Tu);
-        else if (simd)
-            hipLaunchKernelGGL((k_synth_ds_streams<HEAAC_PCM_S16_INTERLEAVED_SSE2>), gd, bd, 0, s, d_tab, d_ws_X, d_state_in,
-                               d_state_out, words, off_syn0, nout, d_pcm, scale, bias, ns, Tu);
-        else
-            hipLaunchKernelGGL((k_synth_ds_streams<HEAAC_PCM_S16_INTERLEAVED>), gd, bd, 0, s, d_tab, d_ws_X, d_state_in,
-                               d_state_out, words, off_syn0, nout, d_pcm, scale, bias, ns, Tu);
+#define SYN_DS(FMT) \
+        HE_LAUNCH_STREAMS((k_synth_ds_streams<FMT>), (k_synth_ds_streams<FMT, const uint8_t *>), d_hold, gd, bd, d_tab, d_ws_X, \
+                          d_state_in, d_state_out, words, off_syn0, nout, d_pcm, scale, bias, ns, Tu)
+        if (pcm_format == HEAAC_PCM_F32_PLANAR) SYN_DS(HEAAC_PCM_F32_PLANAR);
+        else if (simd) SYN_DS(HEAAC_PCM_S16_INTERLEAVED_SSE2);
+        else SYN_DS(HEAAC_PCM_S16_INTERLEAVED);
+#undef SYN_DS
         return hipGetLastError() == hipSuccess ? HEAAC_OK : HEAAC_ERR_HIP;
     }
     const dim3 g(he_grid(chains, SYN_WAVES_F32)), b(SYN_WAVES_F32 * WAVE);
-    if (pcm_format == HEAAC_PCM_F32_PLANAR)
-        hipLaunchKernelGGL((k_synth_streams<HEAAC_PCM_F32_PLANAR>), g, b, 0, s, d_tab, d_ws_X, d_state_in, d_state_out,
-                           words, off_syn0, nout, d_pcm, scale, bias, ns, Tu, d_queue + 2, d_xtop, d_zero);
-    else if (pcm_format == HEAAC_PCM_S16_INTERLEAVED)
-        hipLaunchKernelGGL((k_synth_streams<HEAAC_PCM_S16_INTERLEAVED>), g, b, 0, s, d_tab, d_ws_X, d_state_in, d_state_out,
-                           words, off_syn0, nout, d_pcm, scale, bias, ns, Tu, d_queue + 2, d_xtop, d_zero);
-    else if (simd)
-        hipLaunchKernelGGL((k_synth_streams<HEAAC_PCM_S16_INTERLEAVED_SSE2>), g, b, 0, s, d_tab, d_ws_X, d_state_in, d_state_out,
-                           words, off_syn0, nout, d_pcm, scale, bias, ns, Tu, d_queue + 2, d_xtop, d_zero);
-    else
-        return HEAAC_ERR_ARG;
+#define SYN(FMT) \
+    HE_LAUNCH_STREAMS((k_synth_streams<FMT>), (k_synth_streams<FMT, const uint8_t *>), d_hold, g, b, d_tab, d_ws_X, d_state_in, \
+                      d_state_out, words, off_syn0, nout, d_pcm, scale, bias, ns, Tu, d_queue + 2, d_xtop, d_zero)
+    if (pcm_format == HEAAC_PCM_F32_PLANAR) SYN(HEAAC_PCM_F32_PLANAR);
+    else if (pcm_format == HEAAC_PCM_S16_INTERLEAVED) SYN(HEAAC_PCM_S16_INTERLEAVED);
+    else if (simd) SYN(HEAAC_PCM_S16_INTERLEAVED_SSE2);
+    else return HEAAC_ERR_ARG;
+#undef SYN
     return hipGetLastError() == hipSuccess ? HEAAC_OK : HEAAC_ERR_HIP;
 }
 

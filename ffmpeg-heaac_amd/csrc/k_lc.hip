@@ -134,13 +134,37 @@ constexpr int lcs_waves()
 #endif
 }
 
+// the PCM row of a held unit: zero bytes (c: the unit's half; an interleaved int16 pair is one row, written with c = 1)
 template <int CH, int FMT>
+__device__ __forceinline__ void lcs_zero_row(void *g_pcm, unsigned long long u, unsigned long long u0, int c, int lane)
+{
+    if (FMT == HEAAC_PCM_F32_PLANAR) {
+        float *o = reinterpret_cast<float *>(g_pcm) + u * 1024;
+#pragma nounroll
+        for (int q = lane; q < 1024; q += WAVE) o[q] = 0.0f;
+    } else if (CH == 1) {
+        uint32_t *o = reinterpret_cast<uint32_t *>(reinterpret_cast<int16_t *>(g_pcm) + u * 1024);
+#pragma nounroll
+        for (int q = lane; q < 512; q += WAVE) o[q] = 0u;
+    } else if (c == 1) {
+        uint32_t *o = reinterpret_cast<uint32_t *>(g_pcm) + (u0 / 2) * 1024;
+#pragma nounroll
+        for (int q = lane; q < 1024; q += WAVE) o[q] = 0u;
+    }
+}
+
+// Hold (heaac_lc_decode_streams_ex; k_common.h hold_mask): byte s * T + t != 0 skips frame t of stream s -- its records
+// are not read, its PCM row is zero bytes and the unit's sv[] carry stays as it is.  CH 2: the whole wave skips.  CH 1:
+// the two halves may differ; a held half takes the other half's unit through the transform (the result is dropped) and
+// sits the windowing out.
+template <int CH, int FMT, class... Hold>
 __global__ __launch_bounds__((lcs_waves<CH, FMT>() * WAVE))
 void k_lc_decode_streams(const float *__restrict__ g_tab, const uint16_t *__restrict__ g_rev,
                          const float *__restrict__ g_coeffs, const HeaacIcs *__restrict__ g_ics,
                          const float *g_state_in, float *g_state_out,
-                         void *__restrict__ g_pcm, unsigned long long S, unsigned long long T)
+                         void *__restrict__ g_pcm, unsigned long long S, unsigned long long T, Hold... hold)
 {
+    constexpr bool HOLD = sizeof...(Hold) != 0;
     constexpr int NW = lcs_waves<CH, FMT>();
     __shared__ Core2Lds L;
     __shared__ Lc2Wave W[NW];
@@ -168,9 +192,22 @@ void k_lc_decode_streams(const float *__restrict__ g_tab, const uint16_t *__rest
         }
         for (unsigned long long t = 0; t < T; t++) {
             const unsigned long long u0 = base0 + CH * t, u1 = base1 + CH * t;
-            const HeaacIcs ics0 = g_ics[u0], ics1 = g_ics[u1];
-            core2_stage_coeffs(reinterpret_cast<float *>(w.T[0]), g_coeffs + u0 * 1024, lane);
-            core2_stage_coeffs(reinterpret_cast<float *>(w.T[1]), g_coeffs + u1 * 1024, lane);
+            // v0, v1: the unit each half takes through the transform (with a mask: a held half repeats the other's)
+            unsigned long long v0 = u0, v1 = u1;
+            [[maybe_unused]] bool held0 = false, held1 = false;                 // uniform
+            if constexpr (HOLD) {
+                const uint8_t *g_hold = hold_mask(hold...);
+                held0 = __builtin_amdgcn_readfirstlane((int)g_hold[CH == 2 ? pr * T + t : u0]) != 0;
+                held1 = CH == 2 ? held0 : __builtin_amdgcn_readfirstlane((int)g_hold[u1]) != 0;
+                if (held0) lcs_zero_row<CH, FMT>(g_pcm, u0, u0, 0, lane);
+                if (held1 && have1) lcs_zero_row<CH, FMT>(g_pcm, u1, u0, 1, lane);
+                if (held0 && held1) continue;
+                if (held0) v0 = u1;
+                if (held1) v1 = u0;
+            }
+            const HeaacIcs ics0 = g_ics[v0], ics1 = g_ics[v1];
+            core2_stage_coeffs(reinterpret_cast<float *>(w.T[0]), g_coeffs + v0 * 1024, lane);
+            core2_stage_coeffs(reinterpret_cast<float *>(w.T[1]), g_coeffs + v1 * 1024, lane);
             wave_sync();
             {
                 const int half = lane >> 5, hl = lane & 31;
@@ -180,6 +217,9 @@ void k_lc_decode_streams(const float *__restrict__ g_tab, const uint16_t *__rest
 #pragma unroll
             for (int c = 0; c < 2; c++) {
                 if (c == 1 && !have1) break;
+                if constexpr (HOLD) {
+                    if (c ? held1 : held0) continue;
+                }
                 lc2_window<CH, FMT>(LT, c ? ics1 : ics0, reinterpret_cast<const float *>(w.T[c]), OverlapRegs{ sv[c] },
                                     lane, c, c ? u1 : u0, u0, g_pcm, w);
             }
@@ -342,15 +382,21 @@ extern "C" int heaac_launch_lc_streams(const float *d_tab, const uint16_t *d_rev
                                        const float *d_coeffs, const HeaacIcs *d_ics,
                                        const float *d_state_in, float *d_state_out,
                                        void *d_pcm, int pcm_format, size_t n_streams, size_t frames_per_stream,
-                                       hipStream_t s)
+                                       const uint8_t *d_hold, hipStream_t s)
 {
     if (n_streams == 0) return HEAAC_OK;
     const unsigned long long S = n_streams, T = frames_per_stream;
     const unsigned long long chains = channels == 2 ? S : (S + 1) / 2;
 #define LAUNCH(CH, FMT) \
-    hipLaunchKernelGGL((k_lc_decode_streams<CH, FMT>), dim3(grid_for(chains, lcs_waves<CH, FMT>(), 1)), \
-                       dim3(lcs_waves<CH, FMT>() * WAVE), 0, s, d_tab, d_rev, d_coeffs, d_ics, \
-                       d_state_in, d_state_out, d_pcm, S, T)
+    do { \
+        const dim3 g(grid_for(chains, lcs_waves<CH, FMT>(), 1)), b(lcs_waves<CH, FMT>() * WAVE); \
+        if (d_hold) \
+            hipLaunchKernelGGL((k_lc_decode_streams<CH, FMT, const uint8_t *>), g, b, 0, s, d_tab, d_rev, d_coeffs, d_ics, \
+                               d_state_in, d_state_out, d_pcm, S, T, d_hold); \
+        else \
+            hipLaunchKernelGGL((k_lc_decode_streams<CH, FMT>), g, b, 0, s, d_tab, d_rev, d_coeffs, d_ics, \
+                               d_state_in, d_state_out, d_pcm, S, T); \
+    } while (0)
     if (channels == 1 && pcm_format == HEAAC_PCM_F32_PLANAR) LAUNCH(1, HEAAC_PCM_F32_PLANAR);
     else if (channels == 1 && pcm_format == HEAAC_PCM_S16_INTERLEAVED) LAUNCH(1, HEAAC_PCM_S16_INTERLEAVED);
     else if (channels == 2 && pcm_format == HEAAC_PCM_F32_PLANAR) LAUNCH(2, HEAAC_PCM_F32_PLANAR);

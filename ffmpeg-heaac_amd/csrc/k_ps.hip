@@ -19,13 +19,16 @@
 #include "k_psf.h"
 
 // STRIDED (heaac_he_decode_streams): frame f's SBR and PS records are at f * rstride; X and state at f.
-template <bool GENERAL, int WAVES, bool STRIDED = false>
+// Hold (heaac_he_decode_streams_ex; STRIDED only; k_common.h hold_mask): byte f * rstride != 0 -- frame f is nobody's,
+// its records are not read.
+template <bool GENERAL, int WAVES, bool STRIDED = false, class... Hold>
 __global__ __launch_bounds__(WAVES * WAVE)
 void k_ps(const float *__restrict__ g_tab, const HeaacPsFrame *__restrict__ g_ps,
           const HeaacSbrFrame *__restrict__ g_sbr, const HeaacSbrHeader *__restrict__ g_hdr, unsigned n_hdr,
           const float *g_state_in, float *g_state_out, int state_words, int off_ps,
-          float *g_X, unsigned long long n, unsigned long long rstride)
+          float *g_X, unsigned long long n, unsigned long long rstride, Hold... hold)
 {
+    static_assert(STRIDED || sizeof...(Hold) == 0, "the batch form has no hold mask");
     using WT = PsWaveT<GENERAL>;
     __shared__ HeaacPsFrame s_p[WAVES];
     __shared__ float s_inb[WAVES][WT::NLOW][44][2];
@@ -51,7 +54,11 @@ void k_ps(const float *__restrict__ g_tab, const HeaacPsFrame *__restrict__ g_ps
     const unsigned long long nw = (unsigned long long)gridDim.x * WAVES;
     for (unsigned long long base = wid; base < n; base += nw * WAVE) {
         const unsigned long long fl = base + (unsigned long long)lane * nw;
-        const bool mine = fl < n && ps_frame_is_general(&g_ps[STRIDED ? fl * rstride : fl]) == GENERAL;
+        bool mine;
+        if constexpr (sizeof...(Hold) != 0)
+            mine = fl < n && !hold_mask(hold...)[fl * rstride] && ps_frame_is_general(&g_ps[fl * rstride]) == GENERAL;
+        else
+            mine = fl < n && ps_frame_is_general(&g_ps[STRIDED ? fl * rstride : fl]) == GENERAL;
         unsigned long long todo = __ballot(mine);
         while (todo) {
             const int j = __builtin_amdgcn_readfirstlane(__builtin_ctzll(todo));
@@ -80,14 +87,17 @@ void k_ps(const float *__restrict__ g_tab, const HeaacPsFrame *__restrict__ g_ps
 #define HFPS_C_WORDS (HF_REC_WORDS > 20 * 33 ? HF_REC_WORDS : 20 * 33)
 
 // STRIDED (heaac_he_decode_streams): frame f's SBR and PS records are at f * rstride; W, X, xtop and state at f.
-template <bool STRIDED>
+// Hold (heaac_he_decode_streams_ex; STRIDED only; k_common.h hold_mask): byte f * rstride != 0 -- frame f is passed over
+// like one that is another kernel's; its records are not read (the look-ahead may touch them into L2: no value is used).
+template <bool STRIDED, class... Hold>
 __global__ __launch_bounds__(HFPS_WAVES * WAVE)
 void k_hfps(const float *__restrict__ g_tab, const HeaacSbrFrame *__restrict__ g_sbr,
             const HeaacSbrHeader *__restrict__ g_hdr, unsigned n_hdr, const HeaacPsFrame *__restrict__ g_ps,
             const float *g_W, const float *g_state_in, float *g_state_out, int state_words,
             int off_sbr, int off_ps, float *g_X, unsigned long long n_frames, unsigned *g_queue,
-            unsigned char *__restrict__ g_xtop, int skip_fast, unsigned long long rstride)
+            unsigned char *__restrict__ g_xtop, int skip_fast, unsigned long long rstride, Hold... hold)
 {
+    static_assert(STRIDED || sizeof...(Hold) == 0, "the batch form has no hold mask");
     using WT = PsWaveT<false>;
     static_assert(WT::SCR <= HF_XLOW_WORDS, "|s|^2 / subL / subR lie over X_low");
     constexpr int B_WORDS = WT::NSUB * SUB_STRIDE > HF_AUX_WORDS ? WT::NSUB * SUB_STRIDE : HF_AUX_WORDS;
@@ -125,6 +135,12 @@ void k_hfps(const float *__restrict__ g_tab, const HeaacSbrFrame *__restrict__ g
         const unsigned long long f = feed.cur, f1 = feed.nxt;
         feed.request(lane);
         const unsigned long long rf = STRIDED ? f * rstride : f, rf1 = STRIDED ? f1 * rstride : f1;
+        if constexpr (sizeof...(Hold) != 0) {
+            if (__builtin_amdgcn_readfirstlane((int)hold_mask(hold...)[rf])) {
+                feed.advance();
+                continue;
+            }
+        }
         // slot of the PS loop at which the next frame's SBR and PS records (1.2 KB) are touched into L2
         constexpr int TOUCH_RECORDS_SLOT = 20;
         auto prefetch_next = [&](int n) {
@@ -311,7 +327,7 @@ void k_hfps12(const float *__restrict__ g_tab, const HeaacSbrFrame *__restrict__
 extern "C" int heaac_launch_ps(const float *d_tab, const HeaacPsFrame *d_ps, const HeaacSbrFrame *d_sbr,
                                const HeaacSbrHeader *d_hdr, unsigned n_hdr, const float *d_state_in, float *d_state_out,
                                int state_words, int off_ps, float *d_ws_X, size_t n, int variants, size_t rstride,
-                               hipStream_t s)
+                               const uint8_t *d_hold, hipStream_t s)
 {
     if (!n) return HEAAC_OK;
     const unsigned long long rs = rstride;
@@ -325,7 +341,11 @@ extern "C" int heaac_launch_ps(const float *d_tab, const HeaacPsFrame *d_ps, con
         return HEAAC_ERR_ARG;                       // (the unfused A/B path has no streams form)
     g = (n + PS_WAVES_GEN - 1) / PS_WAVES_GEN;
     if (g > 256) g = 256;
-    if ((variants & 2) && rs == 1)
+    if ((variants & 2) && d_hold)
+        hipLaunchKernelGGL((k_ps<true, PS_WAVES_GEN, true, const uint8_t *>), dim3((unsigned)g), dim3(PS_WAVES_GEN * WAVE), 0, s,
+                           d_tab, d_ps, d_sbr, d_hdr, n_hdr, d_state_in, d_state_out, state_words, off_ps, d_ws_X,
+                           (unsigned long long)n, rs, d_hold);
+    else if ((variants & 2) && rs == 1)
         hipLaunchKernelGGL((k_ps<true, PS_WAVES_GEN>), dim3((unsigned)g), dim3(PS_WAVES_GEN * WAVE), 0, s, d_tab,
                            d_ps, d_sbr, d_hdr, n_hdr, d_state_in, d_state_out, state_words, off_ps, d_ws_X,
                            (unsigned long long)n, rs);
@@ -341,12 +361,19 @@ extern "C" int heaac_launch_hfps(const float *d_tab, const HeaacSbrFrame *d_sbr,
                                  unsigned n_hdr, const HeaacPsFrame *d_ps, const float *d_ws_W,
                                  const float *d_state_in, float *d_state_out, int state_words,
                                  int off_sbr, int off_ps, float *d_ws_X, size_t n, unsigned *d_queue,
-                                 unsigned char *d_xtop, size_t rstride, hipStream_t s)
+                                 unsigned char *d_xtop, size_t rstride, const uint8_t *d_hold, hipStream_t s)
 {
     if (!n) return HEAAC_OK;
     int skip_fast = 0;
     unsigned long long g = (n + HFPS_WAVES - 1) / HFPS_WAVES;
     if (g > 256) g = 256;
+    if (d_hold) {
+        // (with a mask also at one frame per stream: the batch kernel has no hold test)
+        hipLaunchKernelGGL((k_hfps<true, const uint8_t *>), dim3((unsigned)g), dim3(HFPS_WAVES * WAVE), 0, s, d_tab, d_sbr, d_hdr,
+                           n_hdr, d_ps, d_ws_W, d_state_in, d_state_out, state_words, off_sbr, off_ps, d_ws_X,
+                           (unsigned long long)n, d_queue, d_xtop, 0, (unsigned long long)rstride, d_hold);
+        return hipGetLastError() == hipSuccess ? HEAAC_OK : HEAAC_ERR_HIP;
+    }
     if (rstride != 1) {
         hipLaunchKernelGGL(k_hfps<true>, dim3((unsigned)g), dim3(HFPS_WAVES * WAVE), 0, s, d_tab, d_sbr, d_hdr, n_hdr, d_ps,
                            d_ws_W, d_state_in, d_state_out, state_words, off_sbr, off_ps, d_ws_X,

@@ -324,12 +324,16 @@ __device__ __forceinline__ int wave_max(int v)
 // there sit it out).  One frame per wave leaves 58 to 63 lanes idle for the whole recursion, which was most of what the
 // spectral tools cost (profiles/r04_experiments.md E8).
 #define TNS_FILTERS 3              // n_filt is two bits for a long window (0 .. 3), one for a short one
-template <int CH>
+// Hold (heaac_spectral_tools_streams_ex; k_common.h hold_mask): the lanes of a frame whose byte is set sit the pass out.
+template <int CH, class... Hold>
 __global__ __launch_bounds__(256)
-void k_tns(float *g_coeffs, const HeaacToolsFrame *__restrict__ g_tools, unsigned long long n)
+void k_tns(float *g_coeffs, const HeaacToolsFrame *__restrict__ g_tools, unsigned long long n, Hold... hold)
 {
     const unsigned long long u = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
-    const bool live = u < n * CH * TNS_FILTERS;
+    bool live = u < n * CH * TNS_FILTERS;
+    if constexpr (sizeof...(Hold) != 0) {
+        if (live && hold_mask(hold...)[u / (CH * TNS_FILTERS)]) live = false;
+    }
     const unsigned long long f = live ? u / (CH * TNS_FILTERS) : 0;
     const int r = live ? (int)(u - f * (CH * TNS_FILTERS)) : 0;
     const int ch = r / TNS_FILTERS, filt = r - ch * TNS_FILTERS;
@@ -548,12 +552,14 @@ constexpr int tss_waves()
 template <int CH, bool PRED> struct PredCarry { HeaacPredictorState ps[CH][PRED_ROWS]; };
 template <int CH> struct PredCarry<CH, false> {};
 
-template <int CH, bool PRED>
+// Hold (heaac_spectral_tools_streams_ex; k_common.h hold_mask): byte s * T + t != 0 skips frame t of stream s, a
+// wave-uniform test; the frame's record and coefficients are not touched, rs and pc stay in their registers.
+template <int CH, bool PRED, class... Hold>
 __global__ __launch_bounds__((tss_waves<CH, PRED>() * WAVE))
 void k_spectral_tools_streams(float *g_coeffs, const HeaacToolsFrame *__restrict__ g_tools,
                               const int *g_rng_in, int *g_rng_out,
                               const HeaacPredictorState *g_pred_in, HeaacPredictorState *g_pred_out,
-                              unsigned long long S, unsigned long long T)
+                              unsigned long long S, unsigned long long T, Hold... hold)
 {
     constexpr int NW = tss_waves<CH, PRED>();
     __shared__ ToolsWave W[NW];
@@ -585,6 +591,9 @@ void k_spectral_tools_streams(float *g_coeffs, const HeaacToolsFrame *__restrict
         }
         for (unsigned long long t = 0; t < T; t++) {
             const unsigned long long f = s * T + t;
+            if constexpr (sizeof...(Hold) != 0) {
+                if (__builtin_amdgcn_readfirstlane((int)hold_mask(hold...)[f])) continue;
+            }
             float *gc = g_coeffs + f * CH * 1024;
             {
                 const float4 *c4 = reinterpret_cast<const float4 *>(gc);
@@ -671,12 +680,14 @@ extern "C" int heaac_launch_spectral_tools(int channels, float *d_coeffs, const 
     return hipGetLastError() == hipSuccess ? HEAAC_OK : HEAAC_ERR_HIP;
 }
 
-// S streams x T frames (T > 1, some state given: the caller routes the other cases to heaac_launch_spectral_tools).
+// S streams x T frames (the plain call comes here with T > 1 and some state given and routes its other cases to
+// heaac_launch_spectral_tools; with a hold mask every case comes here).
 // The chain kernel runs the PRE half one wave per stream; TNS follows as k_tns over the S * T frames.
 extern "C" int heaac_launch_spectral_tools_streams(int channels, float *d_coeffs, const HeaacToolsFrame *d_tools,
                                                    const int *d_rng_in, int *d_rng_out,
                                                    const HeaacPredictorState *d_pred_in, HeaacPredictorState *d_pred_out,
-                                                   size_t n_streams, size_t frames_per_stream, hipStream_t s)
+                                                   size_t n_streams, size_t frames_per_stream,
+                                                   const uint8_t *d_hold, hipStream_t s)
 {
     if (n_streams == 0) return HEAAC_OK;
     if (channels != 1 && channels != 2) return HEAAC_ERR_ARG;
@@ -687,14 +698,25 @@ extern "C" int heaac_launch_spectral_tools_streams(int channels, float *d_coeffs
     do {                                                                                                             \
         unsigned long long g = (S + tss_waves<CH, PRED>() - 1) / tss_waves<CH, PRED>();                            \
         if (g > 256) g = 256;                                                                                        \
-        hipLaunchKernelGGL((k_spectral_tools_streams<CH, PRED>), dim3((unsigned)g), dim3(tss_waves<CH, PRED>() * WAVE), \
-                           0, s, d_coeffs, d_tools, d_rng_in, d_rng_out, d_pred_in, d_pred_out, S, T);             \
+        if (d_hold)                                                                                                  \
+            hipLaunchKernelGGL((k_spectral_tools_streams<CH, PRED, const uint8_t *>), dim3((unsigned)g),            \
+                               dim3(tss_waves<CH, PRED>() * WAVE), 0, s, d_coeffs, d_tools, d_rng_in, d_rng_out,    \
+                               d_pred_in, d_pred_out, S, T, d_hold);                                                 \
+        else                                                                                                         \
+            hipLaunchKernelGGL((k_spectral_tools_streams<CH, PRED>), dim3((unsigned)g),                             \
+                               dim3(tss_waves<CH, PRED>() * WAVE), 0, s, d_coeffs, d_tools, d_rng_in, d_rng_out,    \
+                               d_pred_in, d_pred_out, S, T);                                                         \
     } while (0)
     const bool pred = d_pred_in != nullptr;
     if (channels == 2) { if (pred) LAUNCH(2, true); else LAUNCH(2, false); }
     else               { if (pred) LAUNCH(1, true); else LAUNCH(1, false); }
 #undef LAUNCH
-    if (channels == 2) hipLaunchKernelGGL(k_tns<2>, dim3((unsigned)blocks), dim3(256), 0, s, d_coeffs, d_tools, n);
-    else               hipLaunchKernelGGL(k_tns<1>, dim3((unsigned)blocks), dim3(256), 0, s, d_coeffs, d_tools, n);
+    if (d_hold) {
+        if (channels == 2) hipLaunchKernelGGL((k_tns<2, const uint8_t *>), dim3((unsigned)blocks), dim3(256), 0, s, d_coeffs, d_tools, n, d_hold);
+        else               hipLaunchKernelGGL((k_tns<1, const uint8_t *>), dim3((unsigned)blocks), dim3(256), 0, s, d_coeffs, d_tools, n, d_hold);
+    } else {
+        if (channels == 2) hipLaunchKernelGGL(k_tns<2>, dim3((unsigned)blocks), dim3(256), 0, s, d_coeffs, d_tools, n);
+        else               hipLaunchKernelGGL(k_tns<1>, dim3((unsigned)blocks), dim3(256), 0, s, d_coeffs, d_tools, n);
+    }
     return hipGetLastError() == hipSuccess ? HEAAC_OK : HEAAC_ERR_HIP;
 }

@@ -1,5 +1,6 @@
 // kernels.h -- internal launch functions (one per .hip translation unit).
 // Not part of the public ABI; include/heaac_dsp.h is.
+// d_hold: the [S][T] hold mask of the *_streams_ex calls (NULL: none, the kernels of the plain calls run).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -16,7 +17,7 @@ int heaac_launch_lc_streams(const float *d_tab, const uint16_t *d_rev, int chann
                             const float *d_coeffs, const HeaacIcs *d_ics,
                             const float *d_state_in, float *d_state_out,
                             void *d_pcm, int pcm_format, size_t n_streams, size_t frames_per_stream,
-                            hipStream_t s);
+                            const uint8_t *d_hold, hipStream_t s);
 
 int heaac_launch_imdct_half(const float *d_tab, const uint16_t *d_rev, int which,
                             float *d_out, const float *d_in, size_t n, hipStream_t s);
@@ -47,17 +48,19 @@ int heaac_launch_he_streams(const float *d_tab, const uint16_t *d_rev, int cfg,
                             void *d_pcm, int pcm_format,
                             float *d_ws_W, float *d_ws_X, unsigned *d_queue,
                             unsigned char *d_xtop, const float *d_zero,
-                            size_t n_streams, size_t frames_per_stream, int flags, hipStream_t s);
+                            size_t n_streams, size_t frames_per_stream, int flags, const uint8_t *d_hold,
+                            hipStream_t s);
 
 int heaac_launch_ps(const float *d_tab, const HeaacPsFrame *d_ps, const HeaacSbrFrame *d_sbr,
                     const HeaacSbrHeader *d_hdr, unsigned n_hdr, const float *d_state_in, float *d_state_out,
-                    int state_words, int off_ps, float *d_ws_X, size_t n, int variants, size_t rstride, hipStream_t s);
+                    int state_words, int off_ps, float *d_ws_X, size_t n, int variants, size_t rstride,
+                    const uint8_t *d_hold, hipStream_t s);
 
 int heaac_launch_hfps(const float *d_tab, const HeaacSbrFrame *d_sbr, const HeaacSbrHeader *d_hdr,
                       unsigned n_hdr, const HeaacPsFrame *d_ps, const float *d_ws_W,
                       const float *d_state_in, float *d_state_out, int state_words,
                       int off_sbr, int off_ps, float *d_ws_X, size_t n, unsigned *d_queue, unsigned char *d_xtop,
-                      size_t rstride, hipStream_t s);
+                      size_t rstride, const uint8_t *d_hold, hipStream_t s);
 
 int heaac_launch_qmf_analysis(const float *d_tab, const float *d_in, const float *d_xh_in,
                               float *d_xh_out, float *d_W, float scale, size_t n, hipStream_t s);
@@ -81,7 +84,8 @@ int heaac_launch_spectral_tools(int channels, float *d_coeffs, const HeaacToolsF
 int heaac_launch_spectral_tools_streams(int channels, float *d_coeffs, const HeaacToolsFrame *d_tools,
                                         const int *d_rng_in, int *d_rng_out,
                                         const HeaacPredictorState *d_pred_in, HeaacPredictorState *d_pred_out,
-                                        size_t n_streams, size_t frames_per_stream, hipStream_t s);
+                                        size_t n_streams, size_t frames_per_stream, const uint8_t *d_hold,
+                                        hipStream_t s);
 int heaac_launch_fft_calc(const float *d_tab, int nbits, float *d_z, size_t n, hipStream_t s);
 int heaac_launch_imdct_mirror(float *d_out, int n, size_t count, hipStream_t s);
 }

@@ -4,6 +4,8 @@
 //   host parse   the worker pool of host_common.h, one slice of the streams per thread
 //   H2D          stream `in`:  parsed records of the tick's buffer set, pinned -> device
 //   GPU          stream `run`: heaac_spectral_tools_batch + heaac_he_decode_batch, DSP state in place
+//                (frames_per_tick = T > 1: heaac_spectral_tools_streams_ex + heaac_he_decode_streams_ex over the T units
+//                of each stream, a unit that did not parse held by the calls' masks instead of parked around them)
 //   D2H          stream `out`: int16 PCM of the tick's buffer set, device -> pinned
 // PL_DEPTH buffer sets rotate (set = tick % PL_DEPTH): a tick spends parse + H2D + GPU + D2H in flight (about 24 ms for
 // 32 k streams) while the slowest stage takes 7 ms, so four ticks must overlap to keep every stage busy.
@@ -31,12 +33,18 @@ struct Set {
     unsigned char *failed;          // [n] the stream's access unit of this tick did not parse (core element): 1, or 2 where
                                     // the spectral tools still have to move its noise generator / predictors
     unsigned *h_list, *d_list;      // [2 n] (stream, parking row) pairs of the failed streams, pinned / device
+    // frames_per_tick > 1 instead of failed / the lists: the hold masks of the streams calls, pinned / device.
+    // [0, n T): hold_dsp, the unit did not parse; [n T, 2 n T): hold_tools, it did not and the tools do not run either
+    // (failed == 1 of the one-unit tick; failed == 2 is hold_dsp alone)
+    uint8_t *h_hold, *d_hold;
+    int any_held;                   // some byte of hold_dsp is set (hold_tools is a subset): the masks are uploaded and passed
 };
 
 struct HeaacPipeline {
     HeaacAacConfig aac;
     int he_cfg, ncore, nout, he, out_len;
     size_t n, words;
+    size_t T, nf;                   // access units per stream and tick; n * T, the frames of a tick
     HeaacDevice *dev;
     hipStream_t in, run, out;
     Set set[PL_DEPTH];
@@ -103,7 +111,42 @@ __attribute__((noinline)) static void parse_slice(HeaacPipeline *p, int w)
     }
 }
 
-static void pl_slice(void *ctx, int w, int) { parse_slice((HeaacPipeline *)ctx, w); }
+// The slice of a tick that carries T > 1 units per stream: each stream's units in order on the stream's parser state,
+// the records of unit t of stream i at i T + t.  Per unit the decision is parse_slice's; it goes into the two hold
+// masks, and since the streams calls never read a held frame's records nothing is rewritten to be "safe to decode"
+// (a unit whose tools still run keeps the parser's tools record and coefficients, as there).
+static void parse_slice_streams(HeaacPipeline *p, int w)
+{
+    const size_t lo = p->n * (size_t)w / (size_t)p->threads, hi = p->n * (size_t)(w + 1) / (size_t)p->threads;
+    Set *s = p->job_set;
+    for (size_t i = lo; i < hi; i++) {
+        HeaacSbrStream *sst_i = (HeaacSbrStream *)((char *)p->sst + i * heaac_sbr_stream_bytes());
+        for (size_t t = 0; t < p->T; t++) {
+            const size_t f = i * p->T + t;
+            HeaacAacFrameInfo fi;
+            memset(&fi, 0, sizeof(fi));
+            const int r = p->he
+                ? heaac_heaac_parse_frame_ex(&p->aac, &p->ast[i], sst_i, p->tab, p->job_au[f], p->job_size[f],
+                                             p->ncore, s->h_coeffs + f * (size_t)p->ncore * 1024, s->h_ics + f * p->ncore,
+                                             &s->h_tools[f], &s->h_sbr[f], s->h_ps ? &s->h_ps[f] : NULL, &fi)
+                : heaac_aac_parse_frame_ex(&p->aac, &p->ast[i], p->job_au[f], p->job_size[f], p->ncore,
+                                           s->h_coeffs + f * (size_t)p->ncore * 1024, s->h_ics + f * p->ncore,
+                                           &s->h_tools[f], NULL, &fi);
+            if (p->job_status) p->job_status[f] = r;
+            const int core_failed = r < 0 && fi.channels == 0;
+            const int run_tools = core_failed && (fi.refused & HEAAC_REFUSED_RUN_TOOLS);
+            s->h_hold[f] = (uint8_t)core_failed;
+            s->h_hold[p->nf + f] = (uint8_t)(core_failed && !run_tools);
+        }
+    }
+}
+
+static void pl_slice(void *ctx, int w, int)
+{
+    HeaacPipeline *p = (HeaacPipeline *)ctx;
+    if (p->T > 1) parse_slice_streams(p, w);
+    else parse_slice(p, w);
+}
 
 extern "C" void heaac_pipeline_destroy(HeaacPipeline *p)
 {
@@ -114,8 +157,8 @@ extern "C" void heaac_pipeline_destroy(HeaacPipeline *p)
     if (p->out) (void)hipStreamSynchronize(p->out);
     for (int k = 0; k < PL_DEPTH; k++) {
         Set *s = &p->set[k];
-        void *h[] = { s->h_coeffs, s->h_ics, s->h_tools, s->h_sbr, s->h_ps, s->h_pcm, s->h_list };
-        void *d[] = { s->d_coeffs, s->d_ics, s->d_tools, s->d_sbr, s->d_ps, s->d_pcm, s->d_list };
+        void *h[] = { s->h_coeffs, s->h_ics, s->h_tools, s->h_sbr, s->h_ps, s->h_pcm, s->h_list, s->h_hold };
+        void *d[] = { s->d_coeffs, s->d_ics, s->d_tools, s->d_sbr, s->d_ps, s->d_pcm, s->d_list, s->d_hold };
         for (void *x : h) if (x) (void)hipHostFree(x);
         for (void *x : d) if (x) (void)hipFree(x);
         hipEvent_t ev[] = { s->in_start, s->in_done, s->run_done, s->out_done };
@@ -140,10 +183,20 @@ extern "C" void heaac_pipeline_destroy(HeaacPipeline *p)
 
 extern "C" int heaac_pipeline_create(HeaacPipeline **out, const HeaacAacConfig *aac, int he_cfg, size_t n, int threads)
 {
+    return heaac_pipeline_create_streams(out, aac, he_cfg, n, 1, threads);
+}
+
+extern "C" size_t heaac_pipeline_frames_per_tick(const HeaacPipeline *p) { return p ? p->T : 0; }
+
+extern "C" int heaac_pipeline_create_streams(HeaacPipeline **out, const HeaacAacConfig *aac, int he_cfg, size_t n_streams,
+                                             size_t frames_per_tick, int threads)
+{
     if (!out) return HEAAC_ERR_ARG;
     *out = NULL;
+    const size_t n = n_streams, T = frames_per_tick;
     const bool lc = he_cfg == HEAAC_CFG_LC_MONO || he_cfg == HEAAC_CFG_LC_STEREO;
-    if (!aac || !n || (!lc && he_cfg != HEAAC_CFG_HEV2 && he_cfg != HEAAC_CFG_HEV1 && he_cfg != HEAAC_CFG_HEV1_MONO) ||
+    if (!aac || !n || !T || n > SIZE_MAX / T ||
+        (!lc && he_cfg != HEAAC_CFG_HEV2 && he_cfg != HEAAC_CFG_HEV1 && he_cfg != HEAAC_CFG_HEV1_MONO) ||
         aac->sampling_index < 0 || aac->sampling_index > 12)
         return HEAAC_ERR_ARG;
     HeaacPipeline *p = (HeaacPipeline *)calloc(1, sizeof(*p));
@@ -158,36 +211,44 @@ extern "C" int heaac_pipeline_create(HeaacPipeline **out, const HeaacAacConfig *
     p->out_len = lc || mode ? 1024 : 2048;
     const HeaacCfgShape shape = heaac_cfg_shape(he_cfg);
     p->ncore = shape.ncore; p->nout = shape.nout; p->words = shape.words;
-    p->n = n;
-    int rc = heaac_device_create(&p->dev, n);
+    p->n = n; p->T = T; p->nf = n * T;
+    int rc = heaac_device_create(&p->dev, p->nf);
     if (rc != HEAAC_OK) { free(p); return rc; }
+    // a T the HE streams call refuses on this device
+    if (p->he && T > heaac_device_max_frames_per_stream(p->dev)) {
+        heaac_device_destroy(p->dev);
+        free(p);
+        return HEAAC_ERR_ARG;
+    }
+    const size_t nf = p->nf;
     bool ok = hipStreamCreateWithFlags(&p->in, hipStreamNonBlocking) == hipSuccess &&
               hipStreamCreateWithFlags(&p->run, hipStreamNonBlocking) == hipSuccess &&
               hipStreamCreateWithFlags(&p->out, hipStreamNonBlocking) == hipSuccess;
     const int with_ps = he_cfg == HEAAC_CFG_HEV2;
     for (int k = 0; k < PL_DEPTH && ok; k++) {
         Set *s = &p->set[k];
-        const size_t nc = n * (size_t)p->ncore;
+        const size_t nc = nf * (size_t)p->ncore;
         ok = pinned((void **)&s->h_coeffs, nc * 4096) && pinned((void **)&s->h_ics, nc * sizeof(HeaacIcs)) &&
-             pinned((void **)&s->h_tools, n * sizeof(HeaacToolsFrame)) &&
-             (!p->he || pinned((void **)&s->h_sbr, n * sizeof(HeaacSbrFrame))) &&
-             (!with_ps || pinned((void **)&s->h_ps, n * sizeof(HeaacPsFrame))) &&
-             pinned((void **)&s->h_pcm, n * (size_t)p->nout * p->out_len * 2) &&
+             pinned((void **)&s->h_tools, nf * sizeof(HeaacToolsFrame)) &&
+             (!p->he || pinned((void **)&s->h_sbr, nf * sizeof(HeaacSbrFrame))) &&
+             (!with_ps || pinned((void **)&s->h_ps, nf * sizeof(HeaacPsFrame))) &&
+             pinned((void **)&s->h_pcm, nf * (size_t)p->nout * p->out_len * 2) &&
              devmem((void **)&s->d_coeffs, nc * 4096) && devmem((void **)&s->d_ics, nc * sizeof(HeaacIcs)) &&
-             devmem((void **)&s->d_tools, n * sizeof(HeaacToolsFrame)) &&
-             (!p->he || devmem((void **)&s->d_sbr, n * sizeof(HeaacSbrFrame))) &&
-             (!with_ps || devmem((void **)&s->d_ps, n * sizeof(HeaacPsFrame))) &&
-             devmem((void **)&s->d_pcm, n * (size_t)p->nout * p->out_len * 2) &&
-             (s->failed = (unsigned char *)calloc(n, 1)) != NULL &&
-             pinned((void **)&s->h_list, 4 * n * sizeof(unsigned)) && devmem((void **)&s->d_list, 4 * n * sizeof(unsigned)) &&
+             devmem((void **)&s->d_tools, nf * sizeof(HeaacToolsFrame)) &&
+             (!p->he || devmem((void **)&s->d_sbr, nf * sizeof(HeaacSbrFrame))) &&
+             (!with_ps || devmem((void **)&s->d_ps, nf * sizeof(HeaacPsFrame))) &&
+             devmem((void **)&s->d_pcm, nf * (size_t)p->nout * p->out_len * 2) &&
+             (T > 1 ? pinned((void **)&s->h_hold, 2 * nf) && devmem((void **)&s->d_hold, 2 * nf)
+                    : (s->failed = (unsigned char *)calloc(n, 1)) != NULL &&
+                      pinned((void **)&s->h_list, 4 * n * sizeof(unsigned)) && devmem((void **)&s->d_list, 4 * n * sizeof(unsigned))) &&
              hipEventCreate(&s->in_start) == hipSuccess && hipEventCreate(&s->in_done) == hipSuccess &&
              hipEventCreate(&s->run_done) == hipSuccess && hipEventCreate(&s->out_done) == hipSuccess;
         if (ok) {
             memset(s->h_coeffs, 0, nc * 4096); memset(s->h_ics, 0, nc * sizeof(HeaacIcs));
-            memset(s->h_tools, 0, n * sizeof(HeaacToolsFrame));
-            if (p->he) memset(s->h_sbr, 0, n * sizeof(HeaacSbrFrame));
-            if (with_ps) memset(s->h_ps, 0, n * sizeof(HeaacPsFrame));
-            ok = hipMemset(s->d_tools, 0, n * sizeof(HeaacToolsFrame)) == hipSuccess;
+            memset(s->h_tools, 0, nf * sizeof(HeaacToolsFrame));
+            if (p->he) memset(s->h_sbr, 0, nf * sizeof(HeaacSbrFrame));
+            if (with_ps) memset(s->h_ps, 0, nf * sizeof(HeaacPsFrame));
+            ok = hipMemset(s->d_tools, 0, nf * sizeof(HeaacToolsFrame)) == hipSuccess;
         }
     }
     ok = ok && devmem((void **)&p->d_state, n * p->words * 4) && devmem((void **)&p->d_rng, n * 4) &&
@@ -246,42 +307,11 @@ static void pl_park(HeaacPipeline *p, const Set *s, unsigned n_all, unsigned n_f
     if (p->d_pred) heaac_rows(p->run, full, n_full, 256, p->d_pred, p->d_park_pred, pl_pred_row_bytes(p) / 4, mode);
 }
 
-extern "C" int heaac_pipeline_submit(HeaacPipeline *p, const uint8_t *const *au, const int *size, int *status)
+// The GPU stage of a one-unit tick: the batch calls, the failed streams' state rows parked around them
+static int pl_run_batch(HeaacPipeline *p, Set *s)
 {
-    if (!p || !au || !size) return HEAAC_ERR_ARG;
-    if (p->submitted - p->collected >= PL_DEPTH) return HEAAC_ERR_ARG;
-    Set *s = &p->set[p->submitted % PL_DEPTH];
-    // the pinned inputs of this set are free once the H2D of the tick that used it last has finished
-    if (s->used) HIP_OK(hipEventSynchronize(s->in_done));
-    const double t0 = now_ms();
-    p->job_au = au; p->job_size = size; p->job_status = status; p->job_set = s;
-    heaac_pool_run(p->pool, 0);
-    s->parse_ms = (float)(now_ms() - t0);
-
-    const size_t n = p->n, nc = n * (size_t)p->ncore;
-    // new SBR headers of this tick (the table's storage never moves)
-    if (heaac_sbr_table_count(p->tab) > PL_MAX_HDRS) return HEAAC_ERR_ARG;
-    // H2D
-    if (s->used) HIP_OK(hipStreamWaitEvent(p->in, s->run_done, 0));
-    HIP_OK(hipEventRecord(s->in_start, p->in));
-    int rc = heaac_upload_headers(p->tab, &p->hdr_uploaded, p->d_hdr, NULL, p->in);
-    if (rc != HEAAC_OK) return rc;
-    HIP_OK(hipMemcpyAsync(s->d_coeffs, s->h_coeffs, nc * 4096, hipMemcpyHostToDevice, p->in));
-    HIP_OK(hipMemcpyAsync(s->d_ics, s->h_ics, nc * sizeof(HeaacIcs), hipMemcpyHostToDevice, p->in));
-    if (p->ncore == 1) {
-        // a mono stream uses channel 0 of the tools record only: the second channel's 3.5 KB stay on the host
-        // (the device copies were zeroed once and the kernel never reads them for one channel)
-        HIP_OK(hipMemcpy2DAsync(s->d_tools, sizeof(HeaacToolsFrame), s->h_tools, sizeof(HeaacToolsFrame),
-                                offsetof(HeaacToolsFrame, ch) + sizeof(HeaacToolsChannel), n, hipMemcpyHostToDevice, p->in));
-    } else {
-        HIP_OK(hipMemcpyAsync(s->d_tools, s->h_tools, n * sizeof(HeaacToolsFrame), hipMemcpyHostToDevice, p->in));
-    }
-    if (p->he) HIP_OK(hipMemcpyAsync(s->d_sbr, s->h_sbr, n * sizeof(HeaacSbrFrame), hipMemcpyHostToDevice, p->in));
-    if (s->d_ps) HIP_OK(hipMemcpyAsync(s->d_ps, s->h_ps, n * sizeof(HeaacPsFrame), hipMemcpyHostToDevice, p->in));
-    HIP_OK(hipEventRecord(s->in_done, p->in));
-    // GPU
-    HIP_OK(hipStreamWaitEvent(p->run, s->in_done, 0));
-    if (s->used) HIP_OK(hipStreamWaitEvent(p->run, s->out_done, 0));
+    const size_t n = p->n;
+    int rc;
     // streams whose unit failed: park their state rows (state, noise generator, predictors) before the launches ...
     unsigned n_all = 0, n_full = 0;
     rc = heaac_failed_lists(p->run, s->failed, n, s->h_list, s->d_list, &n_all, &n_full);
@@ -319,10 +349,72 @@ extern "C" int heaac_pipeline_submit(HeaacPipeline *p, const uint8_t *const *au,
         heaac_rows(p->run, s->d_list, n_all, 256, s->d_pcm, NULL, pcm_row / 2, 2);
         HIP_OK(hipGetLastError());
     }
+    return HEAAC_OK;
+}
+
+// The GPU stage of a tick of T > 1 units per stream: the streams calls, a unit that did not parse held by their masks
+// (no parking area, no row launches)
+static int pl_run_streams(HeaacPipeline *p, Set *s)
+{
+    const size_t n = p->n;
+    // a tick without a failed unit -- the usual one -- runs the plain streams kernels (NULL: no mask)
+    const uint8_t *hold_dsp = s->any_held ? s->d_hold : NULL, *hold_tools = s->any_held ? s->d_hold + p->nf : NULL;
+    int rc = heaac_spectral_tools_streams_ex(p->dev, p->ncore, s->d_coeffs, s->d_tools, p->d_rng, p->d_rng, p->d_pred,
+                                             p->d_pred, n, p->T, hold_tools, (void *)p->run);
+    if (rc == HEAAC_OK)
+        rc = p->he ? heaac_he_decode_streams_ex(p->dev, p->he_cfg, p->downsampled ? HEAAC_HE_DOWNSAMPLED : 0, s->d_coeffs,
+                                                s->d_ics, s->d_sbr, p->d_hdr, PL_MAX_HDRS, s->d_ps, p->d_state, p->d_state,
+                                                s->d_pcm, HEAAC_PCM_S16_INTERLEAVED, n, p->T, hold_dsp, (void *)p->run)
+                   : heaac_lc_decode_streams_ex(p->dev, p->ncore, s->d_coeffs, s->d_ics, p->d_state, p->d_state, s->d_pcm,
+                                                HEAAC_PCM_S16_INTERLEAVED, n, p->T, hold_dsp, (void *)p->run);
+    return rc;
+}
+
+extern "C" int heaac_pipeline_submit(HeaacPipeline *p, const uint8_t *const *au, const int *size, int *status)
+{
+    if (!p || !au || !size) return HEAAC_ERR_ARG;
+    if (p->submitted - p->collected >= PL_DEPTH) return HEAAC_ERR_ARG;
+    Set *s = &p->set[p->submitted % PL_DEPTH];
+    // the pinned inputs of this set are free once the H2D of the tick that used it last has finished
+    if (s->used) HIP_OK(hipEventSynchronize(s->in_done));
+    const double t0 = now_ms();
+    p->job_au = au; p->job_size = size; p->job_status = status; p->job_set = s;
+    heaac_pool_run(p->pool, 0);
+    s->parse_ms = (float)(now_ms() - t0);
+
+    // (nf: the frames of a tick, one per stream or T)
+    const size_t nf = p->nf, nc = nf * (size_t)p->ncore;
+    // new SBR headers of this tick (the table's storage never moves)
+    if (heaac_sbr_table_count(p->tab) > PL_MAX_HDRS) return HEAAC_ERR_ARG;
+    // H2D
+    if (s->used) HIP_OK(hipStreamWaitEvent(p->in, s->run_done, 0));
+    HIP_OK(hipEventRecord(s->in_start, p->in));
+    int rc = heaac_upload_headers(p->tab, &p->hdr_uploaded, p->d_hdr, NULL, p->in);
+    if (rc != HEAAC_OK) return rc;
+    HIP_OK(hipMemcpyAsync(s->d_coeffs, s->h_coeffs, nc * 4096, hipMemcpyHostToDevice, p->in));
+    HIP_OK(hipMemcpyAsync(s->d_ics, s->h_ics, nc * sizeof(HeaacIcs), hipMemcpyHostToDevice, p->in));
+    if (p->ncore == 1) {
+        // a mono stream uses channel 0 of the tools record only: the second channel's 3.5 KB stay on the host
+        // (the device copies were zeroed once and the kernel never reads them for one channel)
+        HIP_OK(hipMemcpy2DAsync(s->d_tools, sizeof(HeaacToolsFrame), s->h_tools, sizeof(HeaacToolsFrame),
+                                offsetof(HeaacToolsFrame, ch) + sizeof(HeaacToolsChannel), nf, hipMemcpyHostToDevice, p->in));
+    } else {
+        HIP_OK(hipMemcpyAsync(s->d_tools, s->h_tools, nf * sizeof(HeaacToolsFrame), hipMemcpyHostToDevice, p->in));
+    }
+    if (p->he) HIP_OK(hipMemcpyAsync(s->d_sbr, s->h_sbr, nf * sizeof(HeaacSbrFrame), hipMemcpyHostToDevice, p->in));
+    if (s->d_ps) HIP_OK(hipMemcpyAsync(s->d_ps, s->h_ps, nf * sizeof(HeaacPsFrame), hipMemcpyHostToDevice, p->in));
+    s->any_held = s->h_hold && memchr(s->h_hold, 1, nf) != NULL;
+    if (s->any_held) HIP_OK(hipMemcpyAsync(s->d_hold, s->h_hold, 2 * nf, hipMemcpyHostToDevice, p->in));
+    HIP_OK(hipEventRecord(s->in_done, p->in));
+    // GPU
+    HIP_OK(hipStreamWaitEvent(p->run, s->in_done, 0));
+    if (s->used) HIP_OK(hipStreamWaitEvent(p->run, s->out_done, 0));
+    rc = p->T > 1 ? pl_run_streams(p, s) : pl_run_batch(p, s);
+    if (rc != HEAAC_OK) return rc;
     HIP_OK(hipEventRecord(s->run_done, p->run));
     // D2H
     HIP_OK(hipStreamWaitEvent(p->out, s->run_done, 0));
-    HIP_OK(hipMemcpyAsync(s->h_pcm, s->d_pcm, n * (size_t)p->nout * p->out_len * 2, hipMemcpyDeviceToHost, p->out));
+    HIP_OK(hipMemcpyAsync(s->h_pcm, s->d_pcm, nf * (size_t)p->nout * p->out_len * 2, hipMemcpyDeviceToHost, p->out));
     HIP_OK(hipEventRecord(s->out_done, p->out));
     s->used = 1;
     p->submitted++;

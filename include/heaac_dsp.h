@@ -294,6 +294,30 @@ int heaac_lc_decode_streams(HeaacDevice *dev, int channels,
                             void *d_pcm, int pcm_format,
                             size_t n_streams, size_t frames_per_stream, void *stream);
 
+/* The streams form with a per-frame HOLD mask: d_hold is [S][T] bytes on the device, frame t of stream s at s * T + t,
+ * non-zero = held.  This is how a caller hands a chain with damaged units to the streams calls (a unit that does not
+ * parse gives silence and leaves its stream where it was).  The same contract in the three *_streams_ex
+ * calls:
+ *   - d_hold == NULL is the plain call, bit for bit (the plain functions are this call).
+ *   - A held frame is skipped.  Its per-frame records (coefficients, ICS, SBR, PS, tools) are not read and may hold
+ *     anything, also what a failed parse half wrote.
+ *   - The stream's state passes over a held frame unchanged: frame t + 1 sees what frame t - 1 left.  With every frame
+ *     of a stream held its state_out equals its state_in, also where the two buffers differ.
+ *   - Decode calls: the PCM row of a held frame is all zero bytes in every PCM format.  HEAAC_CFG_HEV1 / channels = 2
+ *     hold both channels of the frame.
+ *   - Tools call: the generator word and the predictors do not move over a held frame; the held frame's coefficient
+ *     row is unspecified afterwards and nothing downstream may use it.
+ *   - Frames that are not held: PCM, coefficients and final state are bit-identical to the chain of batch calls over
+ *     the stream's non-held frames, in order.
+ *   - Honoured for every T (T = 1 included) and in the stateless tools case.
+ *   - Everything else as the plain call: no allocation, no synchronisation, capturable, the same argument checks. */
+int heaac_lc_decode_streams_ex(HeaacDevice *dev, int channels,
+                               const float *d_coeffs, const HeaacIcs *d_ics,
+                               const float *d_state_in, float *d_state_out,
+                               void *d_pcm, int pcm_format,
+                               size_t n_streams, size_t frames_per_stream,
+                               const uint8_t *d_hold, void *stream);
+
 /* AFTER_IMDCT independent channel coupling: apply_independent_coupling()
  * (aacdec.c:1849-1862) the way spectral_to_sample() applies it to an SCE / CPE once the element's own
  * IMDCT is done (:1929-1930, apply_channel_coupling :1870-1898), AAC-LC (no SBR: len = 1024):
@@ -382,6 +406,18 @@ int heaac_he_decode_streams(HeaacDevice *dev, int cfg, int flags,
                             const float *d_state_in, float *d_state_out,
                             void *d_pcm, int pcm_format,
                             size_t n_streams, size_t frames_per_stream, void *stream);
+
+/* heaac_he_decode_streams with a hold mask (see heaac_lc_decode_streams_ex).  With a mask and d_state_in != d_state_out
+ * the state is copied over once (an asynchronous device-to-device copy on `stream`) in front of the launches. */
+int heaac_he_decode_streams_ex(HeaacDevice *dev, int cfg, int flags,
+                               const float *d_coeffs, const HeaacIcs *d_ics,
+                               const HeaacSbrFrame *d_sbr,
+                               const HeaacSbrHeader *d_hdr, size_t n_hdr,
+                               const HeaacPsFrame *d_ps,
+                               const float *d_state_in, float *d_state_out,
+                               void *d_pcm, int pcm_format,
+                               size_t n_streams, size_t frames_per_stream,
+                               const uint8_t *d_hold, void *stream);
 
 /* Record validation.  The batched entry points take records from ANY parser (the library's own, heaac_parse.h,
  * only writes records that pass), so the per-frame records are where malformed data would arrive; the rules are the reference parser's own rejections
@@ -557,6 +593,14 @@ int heaac_spectral_tools_streams(HeaacDevice *dev, int channels, float *d_coeffs
                                  const int32_t *d_rng_in, int32_t *d_rng_out,
                                  const HeaacPredictorState *d_pred_in, HeaacPredictorState *d_pred_out,
                                  size_t n_streams, size_t frames_per_stream, void *stream);
+
+/* heaac_spectral_tools_streams with a hold mask (see heaac_lc_decode_streams_ex). */
+int heaac_spectral_tools_streams_ex(HeaacDevice *dev, int channels, float *d_coeffs,
+                                    const HeaacToolsFrame *d_tools,
+                                    const int32_t *d_rng_in, int32_t *d_rng_out,
+                                    const HeaacPredictorState *d_pred_in, HeaacPredictorState *d_pred_out,
+                                    size_t n_streams, size_t frames_per_stream,
+                                    const uint8_t *d_hold, void *stream);
 
 /* ------------------------------------------------------------------------
  * Dependent channel coupling: a coupling_channel_element whose spectrum is added into its target

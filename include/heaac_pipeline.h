@@ -52,6 +52,27 @@ void heaac_pipeline_destroy(HeaacPipeline *p);
  * HEAAC_PIPELINE_DEPTH ticks may be in flight: one more submit before a collect returns HEAAC_ERR_ARG. */
 int heaac_pipeline_submit(HeaacPipeline *p, const uint8_t *const *au, const int *size, int *status);
 
+/* The streams form: as heaac_pipeline_create, and every tick carries frames_per_tick = T consecutive access units of
+ * each stream.  A caller with whole files (heaac_adts_split hands out every access unit of a file at once) pays the
+ * fixed cost of a tick -- one dispatch of the parser pool, the copies, the launches, one download -- once per T frames
+ * of each stream, and the GPU stage runs heaac_spectral_tools_streams_ex + heaac_he_decode_streams_ex (AAC-LC:
+ * heaac_lc_decode_streams_ex), the stream's state on chip across the T frames.
+ *   submit:  au[n_streams * T] / size[...] / status[...], unit t of stream s at s * T + t.
+ *   collect: [n_streams][T][len][channels] int16.
+ * Depth, event order and heaac_pipeline_timing are those of the one-unit tick.  Every unit is treated as the one-unit
+ * tick treats it: one that does not parse gives silence for its frame and leaves the stream as heaac_pipeline_submit
+ * describes -- here through the hold masks of the streams calls instead of parking the state around the batch calls
+ * (the two must agree, and tests/test_pipeline_streams_gpu.py compares them).
+ * A stream that has run out of units passes size = 0 for the rest of its tick: the parser answers size <= 0 with
+ * HEAAC_PARSE_ERR_ARG before it looks at the buffer, which is a unit that does not parse -- status
+ * HEAAC_PARSE_ERR_ARG, silence, the stream untouched -- with T = 1 and with T > 1 alike.
+ * frames_per_tick = 1 is heaac_pipeline_create (the batch calls).  HEAAC_ERR_ARG for frames_per_tick = 0, for one that
+ * heaac_he_decode_streams refuses on a device created for n_streams * T frames, and for what heaac_pipeline_create
+ * refuses; HEAAC_ERR_NODEVICE without a usable device. */
+int heaac_pipeline_create_streams(HeaacPipeline **out, const HeaacAacConfig *aac, int he_cfg,
+                                  size_t n_streams, size_t frames_per_tick, int threads);
+size_t heaac_pipeline_frames_per_tick(const HeaacPipeline *p);     /* T of the create call (1: heaac_pipeline_create) */
+
 /* Waits for the OLDEST tick in flight and hands out its PCM: [n_streams][2048 (LC, downsampled SBR: 1024)][channels] int16 in pinned memory
  * owned by the pipeline, valid until HEAAC_PIPELINE_DEPTH more ticks have been submitted. */
 int heaac_pipeline_collect(HeaacPipeline *p, const int16_t **pcm);

@@ -133,9 +133,9 @@ EXPORTED = [
     "heaac_layout_pipeline_create", "heaac_layout_pipeline_destroy", "heaac_layout_pipeline_submit",
     "heaac_layout_pipeline_collect", "heaac_layout_pipeline_channels",
     # heaac_debug.h
-    "heaac_debug_workspace", "heaac_debug_xbands",
+    "heaac_debug_workspace", "heaac_debug_xbands", "heaac_debug_aac_parse_core",
     "heaac_multi_shard", "heaac_multi_create", "heaac_multi_destroy", "heaac_multi_devices", "heaac_multi_device",
-    "heaac_multi_stream", "heaac_multi_he_decode", "heaac_aac_parse_frame", "heaac_aac_parse_batch",
+    "heaac_multi_stream", "heaac_multi_he_decode", "heaac_aac_parse_frame", "heaac_aac_parse_batch", "heaac_aac_parse_device",
     "heaac_aac_tables_fingerprint",
     "heaac_sbr_table_create", "heaac_sbr_table_destroy", "heaac_sbr_table_count", "heaac_sbr_table_data",
     "heaac_sbr_stream_init", "heaac_sbr_stream_bytes", "heaac_sbr_parse_payload", "heaac_sbr_no_payload",
@@ -178,11 +178,12 @@ KERNEL_SOURCE_EXTRA = ("kernels.h", "tables.h", "validate.h")
 def kernel_source_files():
     """The device sources of the kernels bench.py's workloads launch, relative to the repository root: csrc/k_*.hip,
     csrc/k_*.h, kernels.h, tables.h, validate.h and the record header include/heaac_dsp.h -- without k_tools.hip (the
-    spectral tools: no bench workload runs them; tools/tools_rate.py measures them by themselves)."""
+    spectral tools: no bench workload runs them; tools/tools_rate.py measures them by themselves) and k_parse.hip (the
+    device parser: tools/parse_rate.py --device)."""
     import glob
     d = os.path.join(_HERE, "csrc")
     files = sorted(f for f in glob.glob(os.path.join(d, "k_*.hip")) + glob.glob(os.path.join(d, "k_*.h"))
-                   if os.path.basename(f) != "k_tools.hip")
+                   if os.path.basename(f) not in ("k_tools.hip", "k_parse.hip"))
     files += [os.path.join(d, f) for f in KERNEL_SOURCE_EXTRA]
     files.append(os.path.join(os.path.dirname(_HERE), "include", "heaac_dsp.h"))
     return [os.path.relpath(f, os.path.dirname(_HERE)) for f in files]
@@ -395,6 +396,56 @@ class Device:
                                                     d_hold, _stream()),
                    "heaac_lc_decode_streams_ex")
         return pcm, state_out
+
+    # -- compressed access units -> the records of spectral_tools / lc_decode, on the device --
+    def aac_parse(self, cfg, streams, au_bytes, au_offset, coeff_channels=2, coeffs=None, ics=None, tools=None,
+                  info=None, status=None):
+        """heaac_aac_parse_device: n independent streams, one access unit each; unit i is
+        au_bytes[au_offset[i] : au_offset[i + 1]].  streams: uint8 tensor of n AAC_STREAM_DT records (updated in place
+        for the units that come back OK), au_bytes: uint8 tensor, au_offset: n + 1 offsets, either a host array (checked
+        here against len(au_bytes) and uploaded) or an int32 device tensor the caller vouches for.  Returns the dict
+        aac_parse_batch returns, as device tensors (coeffs float32 [n][coeff_channels][1024]; ics, tools, info as
+        uint8 records), plus status int32 [n]: PARSE_OK or PARSE_DEFERRED (parse that unit on the host)."""
+        import torch
+        if isinstance(au_offset, torch.Tensor):
+            assert au_offset.dtype == torch.int32 and au_offset.numel() >= 1, "au_offset"
+            d_off = au_offset
+        else:
+            off = np.ascontiguousarray(au_offset, dtype=np.int64).reshape(-1)
+            assert off.size >= 1 and off[0] >= 0 and (np.diff(off) >= 0).all() and off[-1] <= au_bytes.numel() and \
+                off[-1] < 2 ** 31, "au_offset"
+            d_off = torch.from_numpy(off.astype(np.int32)).to(au_bytes.device)
+        n = d_off.numel() - 1
+        cc = int(coeff_channels)
+        # a wrong-length tensor would be a silent device out-of-bounds access: check them all here
+        assert cc in (1, 2), "coeff_channels"
+        assert au_bytes.dtype == torch.uint8, "au_bytes"
+        assert streams.dtype == torch.uint8 and streams.numel() == n * AAC_STREAM_DT.itemsize, "streams"
+        dv = au_bytes.device
+        if coeffs is None:
+            coeffs = torch.empty((n, cc, 1024), dtype=torch.float32, device=dv)
+        else:
+            assert coeffs.dtype == torch.float32 and coeffs.numel() == n * cc * 1024, "coeffs"
+        if ics is None:
+            ics = torch.empty(n * cc * ICS_DT.itemsize, dtype=torch.uint8, device=dv)
+        else:
+            assert ics.dtype == torch.uint8 and ics.numel() == n * cc * ICS_DT.itemsize, "ics"
+        if tools is None:
+            tools = torch.empty(n * TOOLS_FRAME_DT.itemsize, dtype=torch.uint8, device=dv)
+        else:
+            assert tools.dtype == torch.uint8 and tools.numel() == n * TOOLS_FRAME_DT.itemsize, "tools"
+        if info is None:
+            info = torch.empty(n * AAC_INFO_DT.itemsize, dtype=torch.uint8, device=dv)
+        else:
+            assert info.dtype == torch.uint8 and info.numel() == n * AAC_INFO_DT.itemsize, "info"
+        if status is None:
+            status = torch.empty(n, dtype=torch.int32, device=dv)
+        else:
+            assert status.dtype == torch.int32 and status.numel() == n, "status"
+        _check(lib().heaac_aac_parse_device(self._h, C.byref(cfg), _ptr(streams), _ptr(au_bytes), _ptr(d_off),
+                                            C.c_size_t(n), cc, _ptr(coeffs), _ptr(ics), _ptr(tools), _ptr(info),
+                                            _ptr(status), _stream()), "heaac_aac_parse_device")
+        return dict(coeffs=coeffs, ics=ics, tools=tools, info=info, status=status)
 
     # -- spectral tools before the IMDCT (M/S, intensity stereo, TNS), in place --
     def spectral_tools(self, channels, coeffs, tools, rng=None, pred=None):
@@ -896,6 +947,41 @@ def aac_parse_batch(cfg, streams, aus, threads=0):
                                          out["tools"].ctypes.data_as(C.c_void_p), out["info"].ctypes.data_as(C.c_void_p),
                                          out["status"].ctypes.data_as(C.c_void_p), C.c_int(threads))
     out["failed"] = failed
+    return out
+
+
+PARSE_OK, PARSE_DEFERRED = 0, 1
+PARSE_WHY_PULSE, PARSE_WHY_ELEMENT, PARSE_WHY_REFUSED = 1, 2, 4
+
+
+def pack_units(aus):
+    """A list of access units (bytes) -> (uint8 array of all of them back to back, int64 offsets [n + 1])."""
+    off = np.zeros(len(aus) + 1, np.int64)
+    np.cumsum([len(a) for a in aus], out=off[1:])
+    return np.frombuffer(b"".join(bytes(a) for a in aus), np.uint8).copy(), off
+
+
+def aac_parse_core(cfg, streams, aus, coeff_channels=2, out=None):
+    """heaac_debug_aac_parse_core (include/heaac_debug.h): the walk of heaac_aac_parse_device on the host, over a
+    list of access units, one per stream.  `streams`: AAC_STREAM_DT array, updated in place for the units that come
+    back PARSE_OK.  Returns the dict of aac_parse_batch (coeffs [n][coeff_channels][1024], ics [n][coeff_channels])
+    plus why [n]: 0, or the PARSE_WHY_* reason a unit was deferred for.  `out`: a dict of pre-filled arrays to write into."""
+    n = len(aus)
+    buf, off = pack_units(aus)
+    off = off.astype(np.uint32)
+    if out is None:
+        out = dict(coeffs=np.zeros((n, coeff_channels, 1024), np.float32), ics=np.zeros((n, coeff_channels), ICS_DT),
+                   tools=np.zeros(n, TOOLS_FRAME_DT), info=np.zeros(n, AAC_INFO_DT))
+    out["status"] = np.zeros(n, np.int32)
+    out["why"] = np.zeros(n, np.int32)
+    assert streams.dtype == AAC_STREAM_DT and streams.shape == (n,)
+    keep = np.concatenate([buf, np.zeros(1, np.uint8)])          # (a pointer even when every unit is empty)
+    rc = lib().heaac_debug_aac_parse_core(C.byref(cfg), streams.ctypes.data_as(C.c_void_p), keep.ctypes.data_as(C.c_void_p),
+                                          off.ctypes.data_as(C.c_void_p), C.c_size_t(n), C.c_int(coeff_channels),
+                                          out["coeffs"].ctypes.data_as(C.c_void_p), out["ics"].ctypes.data_as(C.c_void_p),
+                                          out["tools"].ctypes.data_as(C.c_void_p), out["info"].ctypes.data_as(C.c_void_p),
+                                          out["status"].ctypes.data_as(C.c_void_p), out["why"].ctypes.data_as(C.c_void_p))
+    _check(rc, "heaac_debug_aac_parse_core")
     return out
 
 

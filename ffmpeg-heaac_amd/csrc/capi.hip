@@ -9,6 +9,8 @@
 #include <string.h>
 #include "heaac_dsp.h"
 #include "heaac_debug.h"
+#include "heaac_parse.h"
+#include "parse_core.h"
 #include "tables.h"
 #include "kernels.h"
 #include "host_common.h"
@@ -19,6 +21,7 @@ struct HeaacDevice {
     int device;
     float *d_tab;
     uint16_t *d_rev;
+    HeaacParseTables *d_ptab;   // parse_core.h: what heaac_aac_parse_device reads (code trees, dequantisation and band tables)
     void *d_work;
     unsigned *d_queue;      // frame-queue heads of the kernels that draw frames dynamically (one set per lane)
     // X hand-over side data: a page of zeros, then per workspace set one byte per frame and channel = the number of QMF
@@ -166,8 +169,12 @@ extern "C" int heaac_device_create(HeaacDevice **out, size_t max_frames)
         hipMalloc((void **)&d->d_rev, sizeof(t->rev)) != hipSuccess ||
         hipMalloc((void **)&d->d_queue, 64 * HE_MAX_LANES) != hipSuccess ||
         hipMalloc((void **)&d->d_aux, HE_ZERO_BYTES + 2 * (size_t)(d->sets > 0 ? d->sets : 1) * (d->chunk ? d->chunk : 1)) != hipSuccess ||
+        hipMalloc((void **)&d->d_ptab, sizeof(HeaacParseTables)) != hipSuccess ||
         (d->work_bytes && hipMalloc(&d->d_work, d->work_bytes) != hipSuccess))
         rc = HEAAC_ERR_NOMEM;
+    const HeaacParseTables *pt = heaac_parse_tables();
+    if (rc == HEAAC_OK && (!pt || hipMemcpy(d->d_ptab, pt, sizeof(*pt), hipMemcpyHostToDevice) != hipSuccess))
+        rc = HEAAC_ERR_HIP;
     if (rc == HEAAC_OK &&
         (hipMemset(d->d_aux, 0, HE_ZERO_BYTES) != hipSuccess ||
          hipMemcpy(d->d_tab, t->f, sizeof(t->f), hipMemcpyHostToDevice) != hipSuccess ||
@@ -195,6 +202,7 @@ extern "C" void heaac_device_destroy(HeaacDevice *d)
     if (!d) return;
     if (d->d_tab) (void)hipFree(d->d_tab);
     if (d->d_rev) (void)hipFree(d->d_rev);
+    if (d->d_ptab) (void)hipFree(d->d_ptab);
     if (d->d_work) (void)hipFree(d->d_work);
     if (d->d_queue) (void)hipFree(d->d_queue);
     if (d->d_aux) (void)hipFree(d->d_aux);
@@ -267,6 +275,23 @@ extern "C" int heaac_lc_decode_streams_ex(HeaacDevice *dev, int channels,
                                d_pcm, pcm_format, n_streams, (hipStream_t)stream);
     return heaac_launch_lc_streams(dev->d_tab, dev->d_rev, channels, d_coeffs, d_ics, d_state_in, d_state_out,
                                    d_pcm, pcm_format, n_streams, frames_per_stream, d_hold, (hipStream_t)stream);
+}
+
+extern "C" int heaac_aac_parse_device(HeaacDevice *dev, const HeaacAacConfig *cfg, HeaacAacStream *d_st,
+                                      const uint8_t *d_au, const uint32_t *d_au_offset, size_t n, int coeff_channels,
+                                      float *d_coeffs, HeaacIcs *d_ics, HeaacToolsFrame *d_tools,
+                                      HeaacAacFrameInfo *d_info, int32_t *d_status, void *stream)
+{
+    if (!dev || !heaac_parse_args_ok(cfg, coeff_channels))
+        return HEAAC_ERR_ARG;
+    if (n == 0)
+        return HEAAC_OK;
+    // the walk stores a quad codeword's four lines as one 16-byte word
+    if (!d_st || !d_au || !d_au_offset || !d_coeffs || !d_ics || !d_tools || !d_info || !d_status ||
+        ((uintptr_t)d_coeffs & 15) || ((uintptr_t)d_tools & 3) || ((uintptr_t)d_au_offset & 3) || ((uintptr_t)d_info & 3) || ((uintptr_t)d_status & 3))
+        return HEAAC_ERR_ARG;
+    return heaac_launch_aac_parse(dev->d_ptab, cfg, d_st, d_au, d_au_offset, n, coeff_channels, d_coeffs, d_ics, d_tools,
+                                  d_info, d_status, (hipStream_t)stream);
 }
 
 extern "C" int heaac_spectral_tools_batch(HeaacDevice *dev, int channels, float *d_coeffs,

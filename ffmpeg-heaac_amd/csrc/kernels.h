@@ -88,4 +88,15 @@ int heaac_launch_spectral_tools_streams(int channels, float *d_coeffs, const Hea
                                         hipStream_t s);
 int heaac_launch_fft_calc(const float *d_tab, int nbits, float *d_z, size_t n, hipStream_t s);
 int heaac_launch_imdct_mirror(float *d_out, int n, size_t count, hipStream_t s);
+
+/* k_parse.hip: heaac_aac_parse_device (include/heaac_parse.h); d_tab = the device copy of heaac_parse_tables() */
+struct HeaacParseTables;
+struct HeaacAacConfig;
+struct HeaacAacStream;
+struct HeaacAacFrameInfo;
+int heaac_parse_args_ok(const struct HeaacAacConfig *cfg, int coeff_channels);
+int heaac_launch_aac_parse(const struct HeaacParseTables *d_tab, const struct HeaacAacConfig *cfg, struct HeaacAacStream *d_st,
+                           const uint8_t *d_au, const uint32_t *d_au_offset, size_t n, int coeff_channels,
+                           float *d_coeffs, HeaacIcs *d_ics, HeaacToolsFrame *d_tools, struct HeaacAacFrameInfo *d_info,
+                           int32_t *d_status, hipStream_t s);
 }

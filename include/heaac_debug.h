@@ -6,6 +6,7 @@
 
 #include <stddef.h>
 #include "heaac_dsp.h"
+#include "heaac_parse.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -27,6 +28,16 @@ int heaac_debug_workspace(HeaacDevice *dev, float **d_W, float **d_X, size_t *ch
  * channel ch.  heaac_he_decode_streams works in chunks of floor(chunk / T) whole streams, so its records are in frame
  * order only where T divides the chunk.  bench.py reports the shares, since the headline leans on them. */
 int heaac_debug_xbands(HeaacDevice *dev, unsigned char *host_out, size_t n_frames);
+
+/* The access-unit walk of heaac_aac_parse_device (csrc/parse_core.h) instantiated for the host: the same arguments
+ * with host pointers, a plain loop over the n units, no device.  This is where the walk is compared with
+ * heaac_aac_parse_frame_ex unit by unit, fuzzed and run under sanitizers, and where a kernel fault is debugged.
+ * `why` (may be NULL) receives per unit 0 for HEAAC_PARSE_OK, or why the unit was deferred: 1 pulse data, 2 a CCE /
+ * PCE / LFE or a second SCE / CPE, 4 a check of the host parser it does not pass. */
+int heaac_debug_aac_parse_core(const HeaacAacConfig *cfg, HeaacAacStream *st, const uint8_t *au,
+                               const uint32_t *au_offset, size_t n, int coeff_channels, float *coeffs,
+                               HeaacIcs *ics, HeaacToolsFrame *tools, HeaacAacFrameInfo *info, int32_t *status,
+                               int32_t *why);
 
 #ifdef __cplusplus
 }

@@ -328,6 +328,35 @@ int heaac_aac_parse_batch(const HeaacAacConfig *cfg, HeaacAacStream *st,
                           float *coeffs, HeaacIcs *ics, HeaacToolsFrame *tools,
                           HeaacAacFrameInfo *info, int *status, int threads);
 
+/* ---- the same records from compressed units already in device memory (csrc/k_parse.hip, csrc/parse_core.h) ----
+ * n independent streams, one access unit each: unit i is d_au[d_au_offset[i] .. d_au_offset[i + 1]).  The outputs are
+ * laid out as heaac_aac_parse_batch lays them out with coeff_channels (1 or 2, as heaac_aac_parse_frame_ex) as the
+ * channel stride: d_coeffs [n][coeff_channels][1024], d_ics [n][coeff_channels], d_tools [n], d_info [n], d_status [n].
+ * Every pointer but cfg is device memory; d_coeffs must be 16-byte aligned; d_au must not be NULL when n > 0, even if
+ * every unit is empty (pass any valid device pointer).  Per unit, d_status[i] is
+ *   HEAAC_PARSE_OK        d_st[i], the decoded channels' coefficient rows and HeaacIcs, the whole HeaacToolsFrame and
+ *                         the whole HeaacAacFrameInfo are byte for byte what heaac_aac_parse_frame_ex(cfg, &st, au, size,
+ *                         coeff_channels, ..., cce = NULL, &info) leaves on the host from the same st
+ *   HEAAC_PARSE_DEFERRED  not parsed here: d_st[i] is exactly as it was, the unit's output rows are unspecified; parse
+ *                         the unit with heaac_aac_parse_frame_ex on the host from that state and upload its records.
+ * Deferred are: every unit the host parser would not return HEAAC_PARSE_OK for (the device never decides a refusal:
+ * the HEAAC_REFUSED_* rules stay in aac_parse.c); every unit with pulse data (the reference re-quantises such a line
+ * through cbrtf on an arbitrary float, whose last bit is the host libm's); every unit with a coupling channel, program
+ * config or LFE element, or a second SCE / CPE.  Everything else comes back OK: AAC-LC and AAC-Main (prediction side
+ * info, TNS up to order 20), SCE and CPE with M/S, intensity and noise bands, eight-short grouping, all eleven spectral
+ * books with escapes, data stream and fill elements skipped with the SBR payload located, an ADTS header in front.
+ * Returns HEAAC_OK (0; n = 0 included), or HEAAC_ERR_ARG (heaac_dsp.h) before anything is launched for NULL pointers
+ * with n > 0, coeff_channels outside 1 .. 2, cfg->sampling_index outside 0 .. 12 or an object type other than AAC-LC /
+ * AAC-Main.  As the other batch calls: no allocation, no synchronisation, capturable into a graph (two kernels,
+ * in line), no use of the context's workspace. */
+#define HEAAC_PARSE_DEFERRED 1      /* not parsed here: hand this unit to heaac_aac_parse_frame_ex on the host */
+int heaac_aac_parse_device(HeaacDevice *dev, const HeaacAacConfig *cfg /* host */,
+                           HeaacAacStream *d_st,                 /* [n] in / out */
+                           const uint8_t *d_au, const uint32_t *d_au_offset /* [n + 1] */,
+                           size_t n, int coeff_channels,
+                           float *d_coeffs, HeaacIcs *d_ics, HeaacToolsFrame *d_tools,
+                           HeaacAacFrameInfo *d_info, int32_t *d_status, void *stream);
+
 /* SHA-256-free integrity hook for tests: FNV-1a of the generated ISO tables (codes, lengths, band offsets). */
 uint64_t heaac_aac_tables_fingerprint(void);
 

@@ -1,5 +1,17 @@
-"""Host parser throughput: whole HE-AAC access units (core element + SBR payload with PS) per second through
-heaac_heaac_parse_batch, on 1 thread and on all cores.  Usage: python tools/parse_rate.py [n] """
+"""Parser throughput.
+
+  python tools/parse_rate.py [n]
+      host parser: whole HE-AAC access units (core element + SBR payload with PS) per second through
+      heaac_heaac_parse_batch, on 1 thread and on all cores.
+
+  python tools/parse_rate.py --device [--units 32768] [--rounds 12] [--corpus FILE.npz] [--out FILE.jsonl]
+      heaac_aac_parse_device against the host parser on the same box, A/B alternating in one process: about 1 024
+      distinct in-scope stereo AAC-LC units from the bit writer (FILE.npz is read if it exists, written otherwise),
+      tiled to --units.  Timed per round: the device call (device time from events; the H2D of the bytes is timed apart),
+      and heaac_aac_parse_batch on 16 threads plus the H2D of its records from pinned memory (host clock around work
+      that ends in a synchronise).  One JSON line per form: ms per call over the rounds (median, min, max), bytes over
+      the link per unit, and for the device form a nominal store rate: the record sizes (an upper bound of what the kernels write; the
+      counter is rocprofv3 --pmc WRITE_SIZE, in a run of its own) over the call time."""
 import importlib, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -8,6 +20,118 @@ pkg = importlib.import_module("ffmpeg-heaac_amd")
 import sbr_bitwriter as SW
 import test_parse as TP
 import test_sbr_parse as TS
+
+def device_mode(argv):
+    import argparse, ctypes as C, json
+    import torch
+    import parse_device_common as PC
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--device", action="store_true")
+    ap.add_argument("--units", type=int, default=32768)
+    ap.add_argument("--distinct", type=int, default=1024)
+    ap.add_argument("--rounds", type=int, default=12)
+    ap.add_argument("--threads", type=int, default=16)
+    ap.add_argument("--corpus", default="")
+    ap.add_argument("--out", default="")
+    a = ap.parse_args(argv)
+    if a.corpus and os.path.exists(a.corpus):
+        z = np.load(a.corpus)
+        units = [bytes(z["bytes"][z["off"][i]:z["off"][i + 1]]) for i in range(len(z["off"]) - 1)]
+    else:
+        units = PC.in_scope_steps(np.random.default_rng(2024), 3, 2, True, a.distinct, 1, adts=0.0, sbr=0.0)[0]
+        if a.corpus:
+            b, o = pkg.pack_units(units)
+            np.savez(a.corpus, bytes=b, off=o)
+    n = a.units
+    aus = [units[i % len(units)] for i in range(n)]
+    mean_size = float(np.mean([len(u) for u in aus]))
+    cfg = TP._cfg(pkg, 2, 3, 2)
+    assert torch.cuda.is_available(), "parse_rate --device needs a GPU"
+    dev = pkg.Device()
+    buf, off = pkg.pack_units(aus)
+    h_buf = torch.from_numpy(buf).pin_memory()
+    h_off = torch.from_numpy(off.astype(np.int32)).pin_memory()
+    d_buf = torch.empty_like(h_buf, device="cuda"); d_off = torch.empty_like(h_off, device="cuda")
+    d_st = torch.zeros(n * pkg.AAC_STREAM_DT.itemsize, dtype=torch.uint8, device="cuda")
+    d_out = dict(coeffs=torch.empty((n, 2, 1024), dtype=torch.float32, device="cuda"),
+                 ics=torch.empty(n * 8, dtype=torch.uint8, device="cuda"),
+                 tools=torch.empty(n * pkg.TOOLS_FRAME_DT.itemsize, dtype=torch.uint8, device="cuda"),
+                 info=torch.empty(n * pkg.AAC_INFO_DT.itemsize, dtype=torch.uint8, device="cuda"),
+                 status=torch.empty(n, dtype=torch.int32, device="cuda"))
+    # host form: pinned records, the marshalled unit pointers of heaac_aac_parse_batch
+    h_out = dict(coeffs=torch.empty((n, 2, 1024), dtype=torch.float32).pin_memory(),
+                 ics=torch.empty(n * 8, dtype=torch.uint8).pin_memory(),
+                 tools=torch.empty(n * pkg.TOOLS_FRAME_DT.itemsize, dtype=torch.uint8).pin_memory(),
+                 info=torch.empty(n * pkg.AAC_INFO_DT.itemsize, dtype=torch.uint8).pin_memory(),
+                 status=torch.empty(n, dtype=torch.int32).pin_memory())
+    u_out = {k: torch.empty_like(v, device="cuda") for k, v in h_out.items()}
+    keep = [C.create_string_buffer(u, len(u)) for u in units]
+    ptrs = (C.c_char_p * n)(*[C.cast(keep[i % len(units)], C.c_char_p) for i in range(n)])
+    sizes = (C.c_int * n)(*[len(u) for u in aus])
+    h_st = np.zeros(n, pkg.AAC_STREAM_DT)
+    L = pkg.lib()
+    vp = lambda t: C.c_void_p(t.data_ptr())
+
+    def host_round():
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        failed = L.heaac_aac_parse_batch(C.byref(cfg), h_st.ctypes.data_as(C.c_void_p), ptrs, sizes, C.c_size_t(n),
+                                         vp(h_out["coeffs"]), vp(h_out["ics"]), vp(h_out["tools"]), vp(h_out["info"]),
+                                         vp(h_out["status"]), C.c_int(a.threads))
+        t1 = time.perf_counter()
+        for k in h_out:
+            u_out[k].copy_(h_out[k], non_blocking=True)
+        torch.cuda.synchronize()
+        t2 = time.perf_counter()
+        assert failed == 0
+        return (t1 - t0) * 1e3, (t2 - t1) * 1e3
+
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+
+    def device_round():
+        torch.cuda.synchronize()
+        ev[0].record()
+        d_buf.copy_(h_buf, non_blocking=True); d_off.copy_(h_off, non_blocking=True)
+        ev[1].record()
+        dev.aac_parse(cfg, d_st, d_buf, d_off, coeff_channels=2, **d_out)
+        ev[2].record()
+        torch.cuda.synchronize()
+        return ev[1].elapsed_time(ev[2]), ev[0].elapsed_time(ev[1])
+
+    for _ in range(3):                                         # warm-up of both forms at the timed shape
+        device_round(); host_round()
+    assert not d_out["status"].cpu().numpy().any(), "the corpus is in scope: nothing may be deferred"
+    same = all(np.array_equal(d_out[k].cpu().numpy().reshape(-1).view(np.uint8), u_out[k].cpu().numpy().reshape(-1).view(np.uint8))
+               for k in ("coeffs", "ics", "tools", "info"))
+    dev_ms, dev_h2d, host_ms, host_h2d = [], [], [], []
+    for _ in range(a.rounds):
+        x, y = device_round(); dev_ms.append(x); dev_h2d.append(y)
+        x, y = host_round(); host_ms.append(x); host_h2d.append(y)
+    rec = 2 * 4096 + 8 + pkg.TOOLS_FRAME_DT.itemsize + pkg.AAC_INFO_DT.itemsize + 4
+    # an upper bound from the record sizes, not a counter: the zero fill, then every record as if the walk wrote all of it
+    # (it writes the coefficient rows whole, of the tools record only the fields the unit uses)
+    stored = rec + pkg.TOOLS_FRAME_DT.itemsize + pkg.AAC_STREAM_DT.itemsize
+    sp = lambda v: dict(median=round(float(np.median(v)), 3), min=round(float(min(v)), 3), max=round(float(max(v)), 3))
+    lines = [
+        dict(form="heaac_aac_parse_device", units=n, distinct=len(units), mean_unit_bytes=round(mean_size, 1), rounds=a.rounds,
+             call_ms=sp(dev_ms), h2d_bytes_ms=sp(dev_h2d), link_bytes_per_unit=round(mean_size + 4, 1),
+             nominal_stored_bytes_per_unit=stored, nominal_store_GBps=round(stored * n / (np.median(dev_ms) * 1e-3) / 1e9, 1),
+             units_per_s=round(n / (np.median(dev_ms) * 1e-3)), records_equal_host=bool(same)),
+        dict(form="heaac_aac_parse_batch + H2D", units=n, threads=a.threads, rounds=a.rounds,
+             parse_ms=sp(host_ms), h2d_records_ms=sp(host_h2d), total_ms=sp([x + y for x, y in zip(host_ms, host_h2d)]),
+             link_bytes_per_unit=rec, units_per_s=round(n / ((np.median(host_ms) + np.median(host_h2d)) * 1e-3))),
+    ]
+    for l in lines:
+        print(json.dumps(l))
+    if a.out:
+        with open(a.out, "a") as f:
+            for l in lines:
+                f.write(json.dumps(l) + "\n")
+
+
+if "--device" in sys.argv:
+    device_mode(sys.argv[1:])
+    sys.exit(0)
 
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 512
 rng = np.random.default_rng(1)

@@ -12,7 +12,6 @@
 // to each other through a workspace, one chunk of frames at a time (capi.hip).
 //
 // Reference line numbers are libavcodec/aacsbr.c and aacps.c.
-#include <stdlib.h>
 #include <type_traits>
 #include "k_core.h"
 #include "k_core2.h"
@@ -1019,18 +1018,6 @@ static int he_grid(unsigned long long units, int per_block)
     return (int)g;
 }
 
-// The product fuses the HF stage with baseline PS (k_hfps).  A -DHEAAC_TUNING build keeps the stages in
-// separate kernels when HEAAC_HE_UNFUSED=1 is set (A/B measurements only).
-static bool he_fused()
-{
-#ifdef HEAAC_TUNING
-    static const bool fused = []() { const char *e = getenv("HEAAC_HE_UNFUSED"); return !(e && e[0] == '1'); }();
-    return fused;
-#else
-    return true;
-#endif
-}
-
 extern "C" int heaac_launch_he(const float *d_tab, const uint16_t *d_rev, int cfg,
                                const float *d_coeffs, const HeaacIcs *d_ics,
                                const HeaacSbrFrame *d_sbr, const HeaacSbrHeader *d_hdr, unsigned n_hdr,
@@ -1065,24 +1052,19 @@ extern "C" int heaac_launch_he(const float *d_tab, const uint16_t *d_rev, int cf
     hipLaunchKernelGGL(k_core_ana<false>, dim3(he_grid((units + 1) / 2, CA_WAVES)), dim3(CA_WAVES * WAVE), 0, s,
                        d_tab, d_rev, d_coeffs, d_ics, d_state_in, d_state_out, words, ncore,
                        off_saved0, off_sbr0, d_ws_W, 1 / (-1024 * sf_scale), units, 1ull);
-    if (cfg == HEAAC_CFG_HEV2 && he_fused()) {
+    if (cfg == HEAAC_CFG_HEV2) {
         // HF adjustment + baseline PS in one kernel; the general PS kernel finishes the
         // frames with another PS layout (it skips the rest)
         const int off_ps = off_syn0 + 2 * HEAAC_ST_SYNTH;
         int rc = heaac_launch_hfps(d_tab, d_sbr, d_hdr, n_hdr, d_ps, d_ws_W, d_state_in, d_state_out, words,
                                    off_sbr0, off_ps, d_ws_X, n, d_queue, d_xtop, 1, nullptr, s);
         if (rc != HEAAC_OK) return rc;
-        rc = heaac_launch_ps(d_tab, d_ps, d_sbr, d_hdr, n_hdr, d_state_in, d_state_out, words, off_ps, d_ws_X, n, 2, 1, nullptr, s);
+        rc = heaac_launch_ps(d_tab, d_ps, d_sbr, d_hdr, n_hdr, d_state_in, d_state_out, words, off_ps, d_ws_X, n, 1, nullptr, s);
         if (rc != HEAAC_OK) return rc;
     } else {
         hipLaunchKernelGGL(k_hfadj<false>, dim3(he_grid((units + 1) / 2, HF_WAVES)), dim3(HF_WAVES * WAVE), 0, s,
                            d_tab, d_sbr, d_hdr, n_hdr, d_ws_W, d_state_in, d_state_out, words, ncore, off_sbr0,
-                           d_ws_X, units, d_queue + 1, cfg == HEAAC_CFG_HEV2 ? nullptr : d_xtop, 1ull);
-        if (cfg == HEAAC_CFG_HEV2) {
-            int rc = heaac_launch_ps(d_tab, d_ps, d_sbr, d_hdr, n_hdr, d_state_in, d_state_out, words,
-                                     off_syn0 + 2 * HEAAC_ST_SYNTH, d_ws_X, n, 3, 1, nullptr, s);
-            if (rc != HEAAC_OK) return rc;
-        }
+                           d_ws_X, units, d_queue + 1, d_xtop, 1ull);
     }
     const float scale = -1024 * sf_scale, bias = simd ? 0.0f : HEAAC_ADD_BIAS;
     if (flags & HEAAC_HE_DOWNSAMPLED) {
@@ -1181,7 +1163,7 @@ extern "C" int heaac_launch_he_streams(const float *d_tab, const uint16_t *d_rev
                                        off_sbr0, off_ps, X, n_streams, d_queue, xtop, T, d_hold ? d_hold + t : nullptr, s);
             if (rc != HEAAC_OK) return rc;
             rc = heaac_launch_ps(d_tab, d_ps + t, d_sbr + t, d_hdr, n_hdr, st_in, d_state_out, words, off_ps, X,
-                                 n_streams, 2, T, d_hold ? d_hold + t : nullptr, s);
+                                 n_streams, T, d_hold ? d_hold + t : nullptr, s);
             if (rc != HEAAC_OK) return rc;
         } else {
             HE_LAUNCH_STREAMS((k_hfadj<true>), (k_hfadj<true, const uint8_t *>), d_hold ? d_hold + t : nullptr,

@@ -760,3 +760,10 @@ __device__ __forceinline__ void hf_channel(const HfWave &w, const float *g_noise
     HSTAMP(10);
 }
 
+// The frames k_hfps passes over when its skip_fast argument is set (k_ps.hip: it never is).  Wave-uniform.
+__device__ __forceinline__ bool hf_frame_is_fast(const HeaacSbrFrame *g_fr, const HeaacSbrHeader *g_hdr, unsigned n_hdr)
+{
+    const unsigned hi = g_fr->hdr;
+    const HeaacSbrHeader &h = g_hdr[hi < n_hdr ? hi : n_hdr - 1];
+    return g_fr->start && h.bs_interpol_freq && !g_fr->bs_coupling;
+}

@@ -53,7 +53,7 @@ int heaac_launch_he_streams(const float *d_tab, const uint16_t *d_rev, int cfg,
 
 int heaac_launch_ps(const float *d_tab, const HeaacPsFrame *d_ps, const HeaacSbrFrame *d_sbr,
                     const HeaacSbrHeader *d_hdr, unsigned n_hdr, const float *d_state_in, float *d_state_out,
-                    int state_words, int off_ps, float *d_ws_X, size_t n, int variants, size_t rstride,
+                    int state_words, int off_ps, float *d_ws_X, size_t n, size_t rstride,
                     const uint8_t *d_hold, hipStream_t s);
 
 int heaac_launch_hfps(const float *d_tab, const HeaacSbrFrame *d_sbr, const HeaacSbrHeader *d_hdr,

@@ -1,6 +1,6 @@
 """Where a kernel spills: scratch_load / scratch_store of one kernel of a device assembly listing, by source file and
 20-line block (compile with  hipcc ... -gline-tables-only --cuda-device-only -S file.hip -o file.s).
-usage: python3 tools/spill_sites.py file.s <kernel name prefix, mangled, e.g. _Z8k_hfps12>"""
+usage: python3 tools/spill_sites.py file.s <kernel name prefix, mangled, e.g. _Z6k_hfps>"""
 import collections, re, sys
 lines = open(sys.argv[1]).read().split('\n')
 start = [i for i, l in enumerate(lines) if l.startswith(sys.argv[2]) and ':' in l][0]

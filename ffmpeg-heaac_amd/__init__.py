@@ -834,6 +834,12 @@ class LayoutPipeline:
                "heaac_layout_pipeline_submit")
         return status
 
+    def submit_raw(self, ptrs, sizes, status=None):
+        """ptrs, sizes: ctypes arrays of n_streams built once by the caller; status: an int32 array of n_streams to
+        fill, or None."""
+        _check(lib().heaac_layout_pipeline_submit(self._h, ptrs, sizes, status.ctypes.data_as(C.c_void_p) if status is not None else None),
+               "heaac_layout_pipeline_submit")
+
     def collect(self):
         p = C.POINTER(C.c_int16)()
         _check(lib().heaac_layout_pipeline_collect(self._h, C.byref(p)), "heaac_layout_pipeline_collect")

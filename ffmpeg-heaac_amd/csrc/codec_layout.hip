@@ -1,4 +1,7 @@
-// codec_layout.hip -- aac_decode_frame for multi-element layouts behind the AVCodec surface (shim.hip):
+// codec_layout.hip -- aac_decode_frame for multi-element layouts behind the AVCodec surface (shim.hip), one stream
+// with batches of one.  The rules of the walk -- an element's shape, whether a unit stands, how an element's SBR
+// record is read, the order of the spectral tools -- are layout_common.hip's, shared with pipeline_layout.hip; this
+// file validates the records, settles implicit signalling in the first unit and runs the steps synchronously:
 // the element loop is heaac_aac_parse_frame_layout (aac_parse.c), spectral_to_sample (aacdec.c:1903-1933) is one
 // decode call per element on that element's own state record, float_to_int16_interleave over output_data[]
 // (:2096-2097) is heaac_pcm_interleave_batch over the elements' float planes in layout order.
@@ -9,28 +12,22 @@
 //     ff_sbr_apply, with a start = 0 record ("pure upsampling") where it has no payload; a payload behind an LFE, or
 //     with another fill / data stream element between it and its element, is read for its header and switches the
 //     element's SBR off (aacsbr.c:996-1000);
-//   * an access unit that leaves an element of the layout out is refused: the reference transforms whatever that
-//     element's buffers still hold from an earlier frame, which no record of this path carries;
-//   * coupling channel elements: those the program config element names
-//     (che_configure allocates no others).  They are individual channel streams of their own -- tools, and an
-//     IMDCT when they couple AFTER_IMDCT -- processed before their targets (spectral_to_sample walks the element
-//     types downwards, :1907); dependent coupling sits around a target's TNS, independent coupling behind its
-//     IMDCT (:1911-1930), coupling elements in ascending tag order (apply_channel_coupling :1876).  One that an
-//     earlier access unit carried and this one leaves out is refused for the same reason as an output element.
+//   * an access unit that leaves out an element of the layout, or a coupling element an earlier one carried, is refused;
+//   * coupling channel elements: those the program config element names (che_configure allocates no others).  They
+//     are individual channel streams of their own -- tools, and an IMDCT when they couple AFTER_IMDCT -- processed
+//     before their targets; dependent coupling sits around a target's TNS, independent coupling behind its IMDCT
+//     (:1911-1930), coupling elements in ascending tag order (apply_channel_coupling :1876).
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
 #include <string.h>
 #include "codec_layout.h"
-#include "host_common.h"
+#include "layout_common.h"
 
 #define LAY_MAX_HDRS 64
 #define CCE_STATE_WORDS HEAAC_STATE_WORDS_HEV1_MONO
 #define LAY_STATE_WORDS HEAAC_STATE_WORDS_MAX
 
-struct LayElem {
-    int cfg_lc, cfg_he, channels;
-    int out_channels, first_out;  // planes the element gives and where they stand among the stream's; 2 for an SCE
-                                  // that carries Parametric Stereo (che_configure, aacdec.c:203-206)
+struct LayElem : HeaacLayElem {   // out = 2 for an SCE that carries Parametric Stereo (che_configure, aacdec.c:203-206)
     HeaacPsFrame *d_ps;           // ... and its record
     HeaacAacStream ast;
     HeaacSbrStream sst;
@@ -61,11 +58,12 @@ struct LayCoupled {
     HeaacPredictorState *d_pred;  // [MAX_CCE][672]
     float *d_ret;                 // [MAX_CCE][2048] the coupling channels' own output
     HeaacCoupling *d_gain;        // [2]
-    int seen[HEAAC_MAX_CCE];      // an earlier access unit carried this coupling element
+    unsigned char seen[HEAAC_MAX_CCE];   // an earlier access unit carried this coupling element
 };
 
 struct HeaacLayoutDec {
     HeaacDevice *dev;
+    HeaacMem *mem;                // every block below
     HeaacAacConfig m4ac;
     HeaacAacLayout layout;
     int out_channels;             // avctx->channels: the layout's, plus one per SCE with Parametric Stereo
@@ -86,63 +84,28 @@ struct HeaacLayoutDec {
     LayCoupled *cpl;              // layouts whose program config element names coupling elements
 };
 
-static void coupled_free(LayCoupled *c)
+static bool coupled_alloc(HeaacLayoutDec *d)
 {
-    if (!c) return;
-    if (c->d_cce) (void)hipFree(c->d_cce);
-    if (c->d_coeffs) (void)hipFree(c->d_coeffs);
-    if (c->d_ics) (void)hipFree(c->d_ics);
-    if (c->d_tools) (void)hipFree(c->d_tools);
-    if (c->d_state) (void)hipFree(c->d_state);
-    if (c->d_pred) (void)hipFree(c->d_pred);
-    if (c->d_ret) (void)hipFree(c->d_ret);
-    if (c->d_gain) (void)hipFree(c->d_gain);
-    if (c->d_sbr) (void)hipFree(c->d_sbr);
-    free(c);
-}
-
-static LayCoupled *coupled_alloc(void)
-{
-    LayCoupled *c = (LayCoupled *)calloc(1, sizeof(*c));
-    if (!c) return NULL;
-    bool ok =
-        hipMalloc((void **)&c->d_cce, sizeof(c->h_cce)) == hipSuccess &&
-        hipMalloc((void **)&c->d_coeffs, sizeof(c->h_coeffs)) == hipSuccess &&
-        hipMalloc((void **)&c->d_ics, sizeof(c->h_ics)) == hipSuccess &&
-        hipMalloc((void **)&c->d_tools, sizeof(c->h_tools)) == hipSuccess &&
-        hipMalloc((void **)&c->d_state, HEAAC_MAX_CCE * CCE_STATE_WORDS * 4) == hipSuccess &&
-        hipMalloc((void **)&c->d_pred, HEAAC_MAX_CCE * HEAAC_MAX_PREDICTORS * sizeof(HeaacPredictorState)) == hipSuccess &&
-        hipMalloc((void **)&c->d_ret, HEAAC_MAX_CCE * 2048 * 4) == hipSuccess &&
-        hipMalloc((void **)&c->d_gain, 2 * sizeof(HeaacCoupling)) == hipSuccess &&
-        hipMalloc((void **)&c->d_sbr, HEAAC_MAX_CCE * sizeof(HeaacSbrFrame)) == hipSuccess &&
-        hipMemset(c->d_state, 0, HEAAC_MAX_CCE * CCE_STATE_WORDS * 4) == hipSuccess &&
-        heaac_reset_predictors(c->d_pred, HEAAC_MAX_CCE * HEAAC_MAX_PREDICTORS);
+    LayCoupled *c = NULL;
+    HeaacMem **m = &d->mem;
+    if (!heaac_host(m, &c, sizeof(*c))) return false;
+    d->cpl = c;
     heaac_sbr_stream_init(c->sst, HEAAC_MAX_CCE);
-    if (!ok) { coupled_free(c); return NULL; }
-    return c;
+    return heaac_dev(m, &c->d_cce, sizeof(c->h_cce)) && heaac_dev(m, &c->d_coeffs, sizeof(c->h_coeffs)) &&
+           heaac_dev(m, &c->d_ics, sizeof(c->h_ics)) && heaac_dev(m, &c->d_tools, sizeof(c->h_tools)) &&
+           heaac_dev(m, &c->d_state, HEAAC_MAX_CCE * CCE_STATE_WORDS * 4) &&
+           heaac_dev(m, &c->d_pred, HEAAC_MAX_CCE * HEAAC_MAX_PREDICTORS * sizeof(HeaacPredictorState)) &&
+           heaac_dev(m, &c->d_ret, HEAAC_MAX_CCE * 2048 * 4) && heaac_dev(m, &c->d_gain, 2 * sizeof(HeaacCoupling)) &&
+           heaac_dev(m, &c->d_sbr, HEAAC_MAX_CCE * sizeof(HeaacSbrFrame)) &&
+           hipMemset(c->d_state, 0, HEAAC_MAX_CCE * CCE_STATE_WORDS * 4) == hipSuccess &&
+           heaac_reset_predictors(c->d_pred, HEAAC_MAX_CCE * HEAAC_MAX_PREDICTORS);
 }
 
 void heaac_layout_dec_destroy(HeaacLayoutDec *d)
 {
     if (!d) return;
-    for (int i = 0; i < d->n; i++) {
-        LayElem &e = d->e[i];
-        if (e.d_coeffs) (void)hipFree(e.d_coeffs);
-        if (e.d_ics) (void)hipFree(e.d_ics);
-        if (e.d_tools) (void)hipFree(e.d_tools);
-        if (e.d_state) (void)hipFree(e.d_state);
-        if (e.d_pred) (void)hipFree(e.d_pred);
-        if (e.d_sbr) (void)hipFree(e.d_sbr);
-        if (e.d_f32) (void)hipFree(e.d_f32);
-        if (e.d_ps) (void)hipFree(e.d_ps);
-    }
-    if (d->d_hdr) (void)hipFree(d->d_hdr);
-    if (d->d_rng) (void)hipFree(d->d_rng);
-    if (d->d_pcm) (void)hipFree(d->d_pcm);
-    coupled_free(d->cpl);
+    heaac_mem_release(&d->mem);
     heaac_sbr_table_destroy(d->tab);
-    free(d->h_coeffs);
-    free(d->h_tools);
     free(d);
 }
 
@@ -154,58 +117,76 @@ HeaacLayoutDec *heaac_layout_dec_create(HeaacDevice *dev, const HeaacAacConfig *
         layout->channels < 1 || layout->channels > HEAAC_MAX_PCM_PLANES)
         return NULL;
     // Explicitly signalled SBR with the Parametric Stereo question left open (ps = -1: only a program-config layout
-    // leaves it open, mpeg4audio.c:137-139) is ps = 1 to decode_audio_specific_config (aacdec.c:476-477), and
-    // che_configure then gives EVERY single channel element of the layout a second output channel (:203-206):
-    // ff_sbr_apply runs ff_ps_apply on it once PS data has arrived and copies the left channel until then
-    // (aacsbr.c:1751-1758).  An LFE stays one channel (its type is not TYPE_SCE).
+    // leaves it open, mpeg4audio.c:137-139) is ps = 1 to decode_audio_specific_config (aacdec.c:476-477) -- shim.hip
+    // has made it so -- and che_configure then gives EVERY single channel element of the layout a second output
+    // channel: ff_sbr_apply runs ff_ps_apply on it once PS data has arrived and copies the left channel until then
+    // (aacsbr.c:1751-1758).
     // (A one-channel layout that signals SBR implicitly gets there in its first access unit: heaac_layout_dec_frame.)
-    const int ps_sce = m4ac->sbr == 1 && m4ac->ps == 1;
-    int outs = 0;
-    for (int i = 0; i < layout->n_elements; i++)
-        outs += ps_sce && layout->elem[i].type == HEAAC_ELEM_SCE ? 2 : layout->elem[i].channels;
-    if (outs > HEAAC_MAX_PCM_PLANES) return NULL;
-    const int most_outs = outs < 2 ? 2 : outs;
+    HeaacLayShape sh;
+    if (!heaac_lay_shape(layout, m4ac->sbr == 1, m4ac->ps == 1, &sh)) return NULL;
+    const int most_outs = sh.planes < 2 ? 2 : sh.planes;
     HeaacLayoutDec *d = (HeaacLayoutDec *)calloc(1, sizeof(*d));
     if (!d) return NULL;
+    HeaacMem **m = &d->mem;
     d->dev = dev;
     d->m4ac = *m4ac;
     d->layout = *layout;
     d->n = layout->n_elements;
-    d->out_channels = outs;
+    d->out_channels = sh.planes;
     d->tab = heaac_sbr_table_create(LAY_MAX_HDRS);
-    d->h_coeffs = (float *)calloc((size_t)d->n * 2048, sizeof(float));
-    d->h_tools = (HeaacToolsFrame *)calloc(d->n, sizeof(HeaacToolsFrame));
-    bool ok = d->tab && d->h_coeffs && d->h_tools;
+    bool ok = d->tab && heaac_host(m, &d->h_coeffs, (size_t)d->n * 2048 * sizeof(float)) &&
+              heaac_host(m, &d->h_tools, d->n * sizeof(HeaacToolsFrame));
     for (int i = 0; ok && i < d->n; i++) {
         LayElem &e = d->e[i];
-        e.channels = layout->elem[i].channels;
-        e.cfg_lc = e.channels == 2 ? HEAAC_CFG_LC_STEREO : HEAAC_CFG_LC_MONO;
-        e.cfg_he = e.channels == 2 ? HEAAC_CFG_HEV1 : HEAAC_CFG_HEV1_MONO;
-        e.out_channels = e.channels;
-        if (ps_sce && layout->elem[i].type == HEAAC_ELEM_SCE) { e.cfg_he = HEAAC_CFG_HEV2; e.out_channels = 2; }
-        e.first_out = i ? d->e[i - 1].first_out + d->e[i - 1].out_channels : 0;
+        (HeaacLayElem &)e = sh.e[i];
         heaac_sbr_stream_init(&e.sst, 1);
-        ok = hipMalloc((void **)&e.d_coeffs, 2 * 1024 * 4) == hipSuccess &&
-             hipMalloc((void **)&e.d_ics, 2 * sizeof(HeaacIcs)) == hipSuccess &&
-             hipMalloc((void **)&e.d_tools, sizeof(HeaacToolsFrame)) == hipSuccess &&
-             hipMalloc((void **)&e.d_state, LAY_STATE_WORDS * 4) == hipSuccess &&
-             hipMalloc((void **)&e.d_ps, sizeof(HeaacPsFrame)) == hipSuccess &&
-             hipMalloc((void **)&e.d_pred, 2 * HEAAC_MAX_PREDICTORS * sizeof(HeaacPredictorState)) == hipSuccess &&
-             hipMalloc((void **)&e.d_sbr, sizeof(HeaacSbrFrame)) == hipSuccess &&
-             hipMalloc((void **)&e.d_f32, 2 * 2048 * 4) == hipSuccess &&
+        ok = heaac_dev(m, &e.d_coeffs, 2 * 1024 * 4) && heaac_dev(m, &e.d_ics, 2 * sizeof(HeaacIcs)) &&
+             heaac_dev(m, &e.d_tools, sizeof(HeaacToolsFrame)) && heaac_dev(m, &e.d_state, LAY_STATE_WORDS * 4) &&
+             heaac_dev(m, &e.d_ps, sizeof(HeaacPsFrame)) &&
+             heaac_dev(m, &e.d_pred, 2 * HEAAC_MAX_PREDICTORS * sizeof(HeaacPredictorState)) &&
+             heaac_dev(m, &e.d_sbr, sizeof(HeaacSbrFrame)) && heaac_dev(m, &e.d_f32, 2 * 2048 * 4) &&
              hipMemset(e.d_state, 0, LAY_STATE_WORDS * 4) == hipSuccess &&
              heaac_reset_predictors(e.d_pred, 2 * HEAAC_MAX_PREDICTORS);
     }
-    for (int id = 0; ok && id < 16; id++)
-        if (layout->slot_of[HEAAC_ELEM_CCE][id] && !d->cpl) ok = (d->cpl = coupled_alloc()) != NULL;
+    if (ok && sh.cce_slots) ok = coupled_alloc(d);
     for (int i = 0; i < LAY_MAX_HDRS; i++) d->hdr[i].kx = 32;          // kx' = 32, m = 0 (aacsbr.c:130)
-    ok = ok && hipMalloc((void **)&d->d_hdr, sizeof(d->hdr)) == hipSuccess &&
-         hipMalloc((void **)&d->d_rng, 4) == hipSuccess &&
-         hipMalloc((void **)&d->d_pcm, (size_t)most_outs * 2048 * 2) == hipSuccess &&
+    ok = ok && heaac_dev(m, &d->d_hdr, sizeof(d->hdr)) && heaac_dev(m, &d->d_rng, 4) &&
+         heaac_dev(m, &d->d_pcm, (size_t)most_outs * 2048 * 2) &&
          hipMemcpy(d->d_hdr, d->hdr, sizeof(d->hdr), hipMemcpyHostToDevice) == hipSuccess &&
          heaac_seed_generators(d->d_rng, 1);
     if (!ok) { heaac_layout_dec_destroy(d); return NULL; }
     return d;
+}
+
+// The spectral tools, step by step of the schedule.  upload: the element's spectrum and tools record go up in front of
+// its step (a refused unit's, which has no upload pass of its own).
+static int lay_run_tools(HeaacLayoutDec *d, const HeaacLayStep *steps, int n_steps, bool upload)
+{
+    LayCoupled *c = d->cpl;
+    const int main_profile = d->m4ac.object_type == HEAAC_AOT_AAC_MAIN;
+    for (int s = 0; s < n_steps; s++) {
+        const int k = steps[s].index;
+        if (steps[s].cce) {
+            HeaacPredictorState *pr = main_profile ? c->d_pred + k * HEAAC_MAX_PREDICTORS : NULL;
+            if (heaac_spectral_tools_batch_ex(d->dev, 1, HEAAC_TOOLS_ALL, c->d_coeffs + k * 1024, c->d_tools + k,
+                                              d->d_rng, d->d_rng, pr, pr, NULL, NULL, 0, 1, NULL) != HEAAC_OK)
+                return -1;
+            continue;
+        }
+        LayElem &e = d->e[k];
+        if (upload &&
+            (hipMemcpy(e.d_coeffs, d->h_coeffs + (size_t)k * 2048, (size_t)e.channels * 4096, hipMemcpyHostToDevice) != hipSuccess ||
+             hipMemcpy(e.d_tools, &d->h_tools[k], sizeof(HeaacToolsFrame), hipMemcpyHostToDevice) != hipSuccess))
+            return -1;
+        HeaacPredictorState *pr = main_profile ? e.d_pred : NULL;
+        const int rc = steps[s].stages == HEAAC_TOOLS_POST
+            ? heaac_spectral_tools_batch_ex(d->dev, e.channels, HEAAC_TOOLS_POST, e.d_coeffs, e.d_tools, NULL, NULL, NULL, NULL,
+                                            c->d_cce + (size_t)k * HEAAC_MAX_CCE, c->d_coeffs, HEAAC_MAX_CCE, 1, NULL)
+            : heaac_spectral_tools_batch_ex(d->dev, e.channels, steps[s].stages, e.d_coeffs, e.d_tools, d->d_rng, d->d_rng,
+                                            pr, pr, NULL, NULL, 0, 1, NULL);
+        if (rc != HEAAC_OK) return -1;
+    }
+    return 0;
 }
 
 int heaac_layout_dec_frame(HeaacLayoutDec *d, const uint8_t *buf, int size, void *data, int *data_size,
@@ -213,6 +194,8 @@ int heaac_layout_dec_frame(HeaacLayoutDec *d, const uint8_t *buf, int size, void
 {
     if (!d || !buf || size < 2 || !data || !data_size) return -1;
     HeaacAacFrameInfo fi;
+    HeaacLayStep steps[HEAAC_LAY_MAX_STEPS];
+    unsigned char pos[HEAAC_MAX_ELEMENTS];
     // the parser works on copies of the window histories until the whole unit has parsed
     HeaacAacStream st[HEAAC_MAX_ELEMENTS];
     for (int i = 0; i < d->n; i++) st[i] = d->e[i].ast;
@@ -227,55 +210,41 @@ int heaac_layout_dec_frame(HeaacLayoutDec *d, const uint8_t *buf, int size, void
         if (fi.refused & HEAAC_REFUSED_AS_REFERENCE)
             for (int i = 0; i < d->n; i++) d->e[i].ast = st[i];
         if (fi.refused & HEAAC_REFUSED_RUN_TOOLS) {
-            const int main_profile = d->m4ac.object_type == HEAAC_AOT_AAC_MAIN;
-            for (int seq = 0; seq < d->n; seq++)
-                for (int i = 0; i < d->n; i++) {
-                    if (!d->h_elem[i].present || d->h_elem[i].seq != seq) continue;
-                    LayElem &e = d->e[i];
-                    HeaacPredictorState *pr = main_profile ? e.d_pred : NULL;
-                    if (hipMemcpy(e.d_coeffs, d->h_coeffs + (size_t)i * 2048, (size_t)e.channels * 4096, hipMemcpyHostToDevice) != hipSuccess ||
-                        hipMemcpy(e.d_tools, &d->h_tools[i], sizeof(HeaacToolsFrame), hipMemcpyHostToDevice) != hipSuccess ||
-                        heaac_spectral_tools_batch_ex(d->dev, e.channels, HEAAC_TOOLS_ALL, e.d_coeffs, e.d_tools, d->d_rng, d->d_rng,
-                                                      pr, pr, NULL, NULL, 0, 1, NULL) != HEAAC_OK)
-                        return -1;
-                }
+            // the schedule of a unit without coupling elements over the elements the parser got through
+            for (int i = 0; i < d->n; i++) pos[i] = d->h_elem[i].present ? d->h_elem[i].seq : 0xff;
+            if (lay_run_tools(d, steps, heaac_lay_tools_schedule(NULL, 0, pos, d->n, steps), true)) return -1;
             (void)hipDeviceSynchronize();
         }
         return -1;
     }
-    for (int i = 0; i < d->n; i++)
-        if (!d->h_elem[i].present) return -1;
+    const int K = c ? HEAAC_MAX_CCE : 0;
+    if (!heaac_lay_unit_stands(d->h_elem, d->n, c ? c->h_cce[0] : NULL, c ? c->seen : NULL, K)) return -1;
     // the coupling elements of this access unit: slot k of the layout's list, the same in every output slot's row
-    int cce_here[HEAAC_MAX_CCE] = { 0 }, n_cce = 0;
-    for (int k = 0; c && k < HEAAC_MAX_CCE; k++) {
-        cce_here[k] = c->h_cce[0][k].present;
-        n_cce += cce_here[k];
-        if (c->seen[k] && !cce_here[k]) return -1;
+    int n_cce = 0;
+    HeaacLayCcePlace place[HEAAC_MAX_CCE] = {};
+    for (int k = 0; k < K; k++) {
+        const HeaacCceFrame &r = c->h_cce[0][k];
+        place[k] = { r.present, r.outputs_before, r.seq };
+        n_cce += r.present;
+        if (r.present) c->seen[k] = 1;
     }
     for (int i = 0; i < d->n; i++) d->e[i].ast = st[i];
-    for (int k = 0; k < HEAAC_MAX_CCE; k++)
-        if (cce_here[k]) c->seen[k] = 1;
-    // "Dependent coupling is not supported together with LTP" (apply_dependent_coupling :1822-1826 returns): an LTP
-    // profile stream (an ADTS header can say so) keeps its coupling elements but nothing couples in the spectrum
-    if (n_cce && d->m4ac.object_type == 4)
-        for (int i = 0; i < d->n; i++)
-            for (int k = 0; k < HEAAC_MAX_CCE; k++)
-                if (c->h_cce[i][k].coupling_point != HEAAC_CC_AFTER_IMDCT) c->h_cce[i][k].n_links = 0;
+    for (int i = 0; n_cce && i < d->n; i++) heaac_lay_ltp_rule(&d->m4ac, c->h_cce[i], K);
     if (!d->locked) {
         // implicit SBR counts only when the first access unit carries it (aacdec.c:1666-1675)
         if (d->m4ac.sbr == -1) {
             d->m4ac.sbr = 0;
             for (int i = 0; i < d->n; i++)
                 if (d->h_elem[i].sbr_payload_bit >= 0) d->m4ac.sbr = 1;
-            for (int k = 0; c && k < HEAAC_MAX_CCE; k++)
-                if (cce_here[k] && c->h_elem[k].sbr_payload_bit >= 0) d->m4ac.sbr = 1;
+            for (int k = 0; k < K; k++)
+                if (place[k].present && c->h_elem[k].sbr_payload_bit >= 0) d->m4ac.sbr = 1;
             // ... and in a stream of ONE channel the first payload turns Parametric Stereo on with it: the output is
             // configured again, now with two channels (decode_extension_payload, aacdec.c:1670-1673)
             if (d->m4ac.sbr == 1 && d->m4ac.ps == -1 && d->out_channels == 1 && d->n == 1 &&
                 d->layout.elem[0].type == HEAAC_ELEM_SCE) {
                 d->m4ac.ps = 1;
                 d->e[0].cfg_he = HEAAC_CFG_HEV2;
-                d->e[0].out_channels = d->out_channels = 2;
+                d->e[0].out = d->out_channels = 2;
             }
         }
         d->locked = 1;
@@ -284,8 +253,7 @@ int heaac_layout_dec_frame(HeaacLayoutDec *d, const uint8_t *buf, int size, void
     const int mode = he ? heaac_sbr_output_mode(&d->m4ac) : 0;        // 1: the output at the core rate (shim.hip)
     if (mode < 0) return -1;
     const int len = he && !mode ? 2048 : 1024;
-    const int main_profile = d->m4ac.object_type == HEAAC_AOT_AAC_MAIN;
-    // uploads, then the spectral tools of the elements in bitstream order (one noise generator)
+    // uploads, then the spectral tools in the schedule's order (one noise generator)
     for (int i = 0; i < d->n; i++) {
         LayElem &e = d->e[i];
         if (hipMemcpy(e.d_coeffs, d->h_coeffs + (size_t)i * 2048, (size_t)e.channels * 4096, hipMemcpyHostToDevice) != hipSuccess ||
@@ -301,44 +269,14 @@ int heaac_layout_dec_frame(HeaacLayoutDec *d, const uint8_t *buf, int size, void
         return -1;
     // header records the SBR readers have added to the table since the last upload
     auto sync_headers = [&]() -> int { return heaac_upload_headers(d->tab, &d->hdr_uploaded, d->d_hdr, d->hdr, NULL); };
-    // A coupling element's tools as a whole at its place in the stream (nothing couples INTO it); an output element's
-    // first half there, its second half -- coupling, TNS, coupling -- once every coupling element is through.
-    auto cce_tools = [&](int outputs_before) -> int {
-        for (int seq = 0; seq < n_cce; seq++)
-            for (int k = 0; k < HEAAC_MAX_CCE; k++) {
-                const HeaacCceFrame &r = c->h_cce[0][k];
-                if (!r.present || r.seq != seq || r.outputs_before != outputs_before) continue;
-                HeaacPredictorState *pr = main_profile ? c->d_pred + k * HEAAC_MAX_PREDICTORS : NULL;
-                if (heaac_spectral_tools_batch_ex(d->dev, 1, HEAAC_TOOLS_ALL, c->d_coeffs + k * 1024, c->d_tools + k,
-                                                  d->d_rng, d->d_rng, pr, pr, NULL, NULL, 0, 1, NULL) != HEAAC_OK)
-                    return -1;
-            }
-        return 0;
-    };
-    for (int seq = 0; seq < d->n; seq++) {
-        if (n_cce && cce_tools(seq)) return -1;
-        for (int i = 0; i < d->n; i++) {
-            if (d->h_elem[i].seq != seq) continue;
-            LayElem &e = d->e[i];
-            HeaacPredictorState *pr = main_profile ? e.d_pred : NULL;
-            if (heaac_spectral_tools_batch_ex(d->dev, e.channels, n_cce ? HEAAC_TOOLS_PRE : HEAAC_TOOLS_ALL, e.d_coeffs, e.d_tools,
-                                              d->d_rng, d->d_rng, pr, pr, NULL, NULL, 0, 1, NULL) != HEAAC_OK)
-                return -1;
-        }
-    }
+    for (int i = 0; i < d->n; i++) pos[i] = d->h_elem[i].seq;
+    if (lay_run_tools(d, steps, heaac_lay_tools_schedule(place, K, pos, d->n, steps), false)) return -1;
     if (n_cce) {
-        if (cce_tools(d->n)) return -1;
-        for (int i = 0; i < d->n; i++) {
-            LayElem &e = d->e[i];
-            if (heaac_spectral_tools_batch_ex(d->dev, e.channels, HEAAC_TOOLS_POST, e.d_coeffs, e.d_tools, NULL, NULL, NULL, NULL,
-                                              c->d_cce + (size_t)i * HEAAC_MAX_CCE, c->d_coeffs, HEAAC_MAX_CCE, 1, NULL) != HEAAC_OK)
-                return -1;
-        }
         // the coupling channels that couple behind the IMDCT: their own IMDCT -- and SBR, as a mono element's
         // (:1920-1927) -- first (type 2 before types 1 and 0).  A payload behind a coupling element that couples in
         // the spectrum is read all the same (decode_extension_payload does not look at the coupling point).
         for (int k = 0; k < HEAAC_MAX_CCE; k++) {
-            if (!cce_here[k]) continue;
+            if (!place[k].present) continue;
             const bool after = c->h_cce[0][k].coupling_point == HEAAC_CC_AFTER_IMDCT;
             float *st_k = c->d_state + (size_t)k * CCE_STATE_WORDS;
             if (!he) {
@@ -349,11 +287,9 @@ int heaac_layout_dec_frame(HeaacLayoutDec *d, const uint8_t *buf, int size, void
             }
             HeaacSbrFrame sbr;
             const HeaacAacElementInfo &ei = c->h_elem[k];
-            if (ei.sbr_payload_bit >= 0)
-                (void)heaac_sbr_parse_payload(&c->sst[k], d->tab, d->m4ac.sample_rate, buf, size, ei.sbr_payload_bit, ei.sbr_payload_bytes,
-                                              ei.sbr_crc, 1, ei.sbr_misplaced ? HEAAC_SBR_MISPLACED : 0, &sbr, NULL, NULL);
-            else if (after)
-                heaac_sbr_no_payload(&c->sst[k], 1, &sbr, NULL);
+            // (no record, and the reader stays, where there is no payload and the channel is not transformed)
+            if (ei.sbr_payload_bit >= 0 || after)
+                heaac_lay_read_sbr(&c->sst[k], NULL, d->tab, d->m4ac.sample_rate, buf, size, &ei, 1, &sbr, NULL);
             if (!after) continue;
             if (sync_headers()) return -1;
             if (heaac_validate_frame(HEAAC_CFG_HEV1_MONO, &sbr, d->hdr, LAY_MAX_HDRS, NULL)) return -1;
@@ -372,19 +308,10 @@ int heaac_layout_dec_frame(HeaacLayoutDec *d, const uint8_t *buf, int size, void
             rc = heaac_lc_decode_batch(d->dev, e.channels, e.d_coeffs, e.d_ics, e.d_state, e.d_state, e.d_f32,
                                        HEAAC_PCM_F32_PLANAR, 1, NULL);
         } else {
-            HeaacSbrFrame sbr;
-            HeaacPsFrame ps;
+            HeaacSbrFrame sbr; HeaacPsFrame ps;
             const bool with_ps = e.cfg_he == HEAAC_CFG_HEV2;
-            const HeaacAacElementInfo &ei = d->h_elem[i];
-            if (ei.sbr_payload_bit >= 0) {
-                // a failed payload leaves its degraded record (start = 0) and the decode goes on, as ff_sbr_apply does
-                (void)heaac_sbr_parse_payload(&e.sst, d->tab, d->m4ac.sample_rate, buf, size, ei.sbr_payload_bit,
-                                              ei.sbr_payload_bytes, ei.sbr_crc, e.channels,
-                                              (ei.sbr_misplaced ? HEAAC_SBR_MISPLACED : 0) | (with_ps ? HEAAC_SBR_ALLOW_PS : 0),
-                                              &sbr, with_ps ? &ps : NULL, NULL);
-            } else {
-                heaac_sbr_no_payload(&e.sst, e.channels, &sbr, with_ps ? &ps : NULL);
-            }
+            heaac_lay_read_sbr(&e.sst, NULL, d->tab, d->m4ac.sample_rate, buf, size, &d->h_elem[i], e.channels, &sbr,
+                               with_ps ? &ps : NULL);
             if (sync_headers()) return -1;
             if (heaac_validate_frame(e.cfg_he, &sbr, d->hdr, LAY_MAX_HDRS, with_ps ? &ps : NULL)) return -1;
             if (hipMemcpy(e.d_sbr, &sbr, sizeof(sbr), hipMemcpyHostToDevice) != hipSuccess) return -1;
@@ -398,7 +325,7 @@ int heaac_layout_dec_frame(HeaacLayoutDec *d, const uint8_t *buf, int size, void
         // :1870-1898; apply_independent_coupling :1849-1862 over 1024 << sbr samples): one target channel at a time,
         // its plane and the coupling channel's as len / 1024 "frames" of the batched op
         for (int k = 0; k < HEAAC_MAX_CCE; k++) {
-            if (!cce_here[k] || c->h_cce[i][k].coupling_point != HEAAC_CC_AFTER_IMDCT) continue;
+            if (!place[k].present || c->h_cce[i][k].coupling_point != HEAAC_CC_AFTER_IMDCT) continue;
             for (int l = 0; l < c->h_cce[i][k].n_links; l++) {
                 HeaacCoupling g[2];
                 memset(g, 0, sizeof(g));
@@ -410,7 +337,7 @@ int heaac_layout_dec_frame(HeaacLayoutDec *d, const uint8_t *buf, int size, void
                     return -1;
             }
         }
-        const int np = he ? e.out_channels : e.channels;
+        const int np = he ? e.out : e.channels;
         for (int c = 0; c < np; c++) {
             planes[e.first_out + c].d_base = e.d_f32 + (size_t)c * len;
             planes[e.first_out + c].frame_stride = (size_t)np * len;

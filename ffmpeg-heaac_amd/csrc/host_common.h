@@ -1,5 +1,6 @@
 // host_common.h -- internal: the host-side decisions that the pipelines (pipeline.hip, pipeline_layout.hip), the
-// codec contexts (shim.hip, codec_layout.hip) and the C ABI (capi.hip) share.  Not part of include/*.h.
+// codec contexts (shim.hip, codec_layout.hip), the layout walk they share (layout_common.hip) and the C ABI (capi.hip)
+// share.  Not part of include/*.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -11,6 +12,21 @@
 
 static inline int pinned(void **p, size_t bytes) { return hipHostMalloc(p, bytes, hipHostMallocDefault) == hipSuccess; }
 static inline int devmem(void **p, size_t bytes) { return hipMalloc(p, bytes) == hipSuccess; }
+
+// ---- what an object owns ----
+// Every block an object allocates is recorded with its owner, and destroy releases the list: no free list to keep in
+// step with create, and a half-built object is released the same way.  HOST blocks are zeroed (calloc).
+struct HeaacMem;
+enum { HEAAC_MEM_HOST, HEAAC_MEM_PINNED, HEAAC_MEM_DEVICE };
+int heaac_mem(HeaacMem **owner, int kind, void **p, size_t bytes);          // 1: *p allocated and recorded
+void heaac_mem_release(HeaacMem **owner);
+template <class T> static inline int heaac_host(HeaacMem **o, T **p, size_t bytes) { return heaac_mem(o, HEAAC_MEM_HOST, (void **)p, bytes); }
+template <class T> static inline int heaac_dev(HeaacMem **o, T **p, size_t bytes) { return heaac_mem(o, HEAAC_MEM_DEVICE, (void **)p, bytes); }
+// a buffer the host fills and the device reads, or the other way round: pinned host memory and its device twin
+template <class T> static inline int heaac_pair(HeaacMem **o, T **h, T **d, size_t bytes)
+{
+    return heaac_mem(o, HEAAC_MEM_PINNED, (void **)h, bytes) && heaac_mem(o, HEAAC_MEM_DEVICE, (void **)d, bytes);
+}
 
 // ---- configuration -> shape ----
 struct HeaacCfgShape {

@@ -1,5 +1,6 @@
-// host_common.hip -- host_common.h: the worker pool, the parking of failed streams' rows, per-stream device seeding,
-// the SBR header upload and the configuration's shape, once for the pipelines, the codec contexts and the C ABI.
+// host_common.hip -- host_common.h: what an object owns, the worker pool, the parking of failed streams' rows,
+// per-stream device seeding, the SBR header upload and the configuration's shape, once for the pipelines, the codec
+// contexts and the C ABI.
 #include <pthread.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -17,6 +18,35 @@ HeaacCfgShape heaac_cfg_shape(int cfg)
     case HEAAC_CFG_HEV2:      return { 1, 2, 1, HEAAC_STATE_WORDS_HEV2 };
     }
     return { 0, 0, 0, 0 };
+}
+
+// ---------------------------------------------------------------------------
+// what an object owns
+// ---------------------------------------------------------------------------
+struct HeaacMem { HeaacMem *next; void *p; int kind; };
+
+int heaac_mem(HeaacMem **owner, int kind, void **p, size_t bytes)
+{
+    HeaacMem *m = (HeaacMem *)malloc(sizeof(*m));
+    if (!m) return 0;
+    *p = NULL;
+    const int ok = kind == HEAAC_MEM_HOST ? (*p = calloc(1, bytes)) != NULL : kind == HEAAC_MEM_PINNED ? pinned(p, bytes) : devmem(p, bytes);
+    if (!ok) { *p = NULL; free(m); return 0; }
+    m->next = *owner; m->p = *p; m->kind = kind;
+    *owner = m;
+    return 1;
+}
+
+void heaac_mem_release(HeaacMem **owner)
+{
+    while (*owner) {
+        HeaacMem *m = *owner;
+        *owner = m->next;
+        if (m->kind == HEAAC_MEM_HOST) free(m->p);
+        else if (m->kind == HEAAC_MEM_PINNED) (void)hipHostFree(m->p);
+        else (void)hipFree(m->p);
+        free(m);
+    }
 }
 
 // ---------------------------------------------------------------------------

@@ -41,6 +41,7 @@ struct Set {
 };
 
 struct HeaacPipeline {
+    HeaacMem *mem;                  // every block but the parking areas
     HeaacAacConfig aac;
     int he_cfg, ncore, nout, he, out_len;
     size_t n, words;
@@ -157,18 +158,10 @@ extern "C" void heaac_pipeline_destroy(HeaacPipeline *p)
     if (p->out) (void)hipStreamSynchronize(p->out);
     for (int k = 0; k < PL_DEPTH; k++) {
         Set *s = &p->set[k];
-        void *h[] = { s->h_coeffs, s->h_ics, s->h_tools, s->h_sbr, s->h_ps, s->h_pcm, s->h_list, s->h_hold };
-        void *d[] = { s->d_coeffs, s->d_ics, s->d_tools, s->d_sbr, s->d_ps, s->d_pcm, s->d_list, s->d_hold };
-        for (void *x : h) if (x) (void)hipHostFree(x);
-        for (void *x : d) if (x) (void)hipFree(x);
         hipEvent_t ev[] = { s->in_start, s->in_done, s->run_done, s->out_done };
         for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
-        free(s->failed);
     }
-    if (p->d_state) (void)hipFree(p->d_state);
-    if (p->d_rng) (void)hipFree(p->d_rng);
-    if (p->d_pred) (void)hipFree(p->d_pred);
-    if (p->d_hdr) (void)hipFree(p->d_hdr);
+    heaac_mem_release(&p->mem);
     if (p->d_park_state) (void)hipFree(p->d_park_state);
     if (p->d_park_rng) (void)hipFree(p->d_park_rng);
     if (p->d_park_pred) (void)hipFree(p->d_park_pred);
@@ -176,7 +169,6 @@ extern "C" void heaac_pipeline_destroy(HeaacPipeline *p)
     if (p->run) (void)hipStreamDestroy(p->run);
     if (p->out) (void)hipStreamDestroy(p->out);
     heaac_sbr_table_destroy(p->tab);
-    free(p->ast); free(p->sst); free(p->sst_tmp);
     heaac_device_destroy(p->dev);
     free(p);
 }
@@ -221,6 +213,7 @@ extern "C" int heaac_pipeline_create_streams(HeaacPipeline **out, const HeaacAac
         return HEAAC_ERR_ARG;
     }
     const size_t nf = p->nf;
+    HeaacMem **m = &p->mem;
     bool ok = hipStreamCreateWithFlags(&p->in, hipStreamNonBlocking) == hipSuccess &&
               hipStreamCreateWithFlags(&p->run, hipStreamNonBlocking) == hipSuccess &&
               hipStreamCreateWithFlags(&p->out, hipStreamNonBlocking) == hipSuccess;
@@ -228,19 +221,13 @@ extern "C" int heaac_pipeline_create_streams(HeaacPipeline **out, const HeaacAac
     for (int k = 0; k < PL_DEPTH && ok; k++) {
         Set *s = &p->set[k];
         const size_t nc = nf * (size_t)p->ncore;
-        ok = pinned((void **)&s->h_coeffs, nc * 4096) && pinned((void **)&s->h_ics, nc * sizeof(HeaacIcs)) &&
-             pinned((void **)&s->h_tools, nf * sizeof(HeaacToolsFrame)) &&
-             (!p->he || pinned((void **)&s->h_sbr, nf * sizeof(HeaacSbrFrame))) &&
-             (!with_ps || pinned((void **)&s->h_ps, nf * sizeof(HeaacPsFrame))) &&
-             pinned((void **)&s->h_pcm, nf * (size_t)p->nout * p->out_len * 2) &&
-             devmem((void **)&s->d_coeffs, nc * 4096) && devmem((void **)&s->d_ics, nc * sizeof(HeaacIcs)) &&
-             devmem((void **)&s->d_tools, nf * sizeof(HeaacToolsFrame)) &&
-             (!p->he || devmem((void **)&s->d_sbr, nf * sizeof(HeaacSbrFrame))) &&
-             (!with_ps || devmem((void **)&s->d_ps, nf * sizeof(HeaacPsFrame))) &&
-             devmem((void **)&s->d_pcm, nf * (size_t)p->nout * p->out_len * 2) &&
-             (T > 1 ? pinned((void **)&s->h_hold, 2 * nf) && devmem((void **)&s->d_hold, 2 * nf)
-                    : (s->failed = (unsigned char *)calloc(n, 1)) != NULL &&
-                      pinned((void **)&s->h_list, 4 * n * sizeof(unsigned)) && devmem((void **)&s->d_list, 4 * n * sizeof(unsigned))) &&
+        ok = heaac_pair(m, &s->h_coeffs, &s->d_coeffs, nc * 4096) && heaac_pair(m, &s->h_ics, &s->d_ics, nc * sizeof(HeaacIcs)) &&
+             heaac_pair(m, &s->h_tools, &s->d_tools, nf * sizeof(HeaacToolsFrame)) &&
+             (!p->he || heaac_pair(m, &s->h_sbr, &s->d_sbr, nf * sizeof(HeaacSbrFrame))) &&
+             (!with_ps || heaac_pair(m, &s->h_ps, &s->d_ps, nf * sizeof(HeaacPsFrame))) &&
+             heaac_pair(m, &s->h_pcm, &s->d_pcm, nf * (size_t)p->nout * p->out_len * 2) &&
+             (T > 1 ? heaac_pair(m, &s->h_hold, &s->d_hold, 2 * nf)
+                    : heaac_host(m, &s->failed, n) && heaac_pair(m, &s->h_list, &s->d_list, 4 * n * sizeof(unsigned))) &&
              hipEventCreate(&s->in_start) == hipSuccess && hipEventCreate(&s->in_done) == hipSuccess &&
              hipEventCreate(&s->run_done) == hipSuccess && hipEventCreate(&s->out_done) == hipSuccess;
         if (ok) {
@@ -251,19 +238,17 @@ extern "C" int heaac_pipeline_create_streams(HeaacPipeline **out, const HeaacAac
             ok = hipMemset(s->d_tools, 0, nf * sizeof(HeaacToolsFrame)) == hipSuccess;
         }
     }
-    ok = ok && devmem((void **)&p->d_state, n * p->words * 4) && devmem((void **)&p->d_rng, n * 4) &&
-         devmem((void **)&p->d_hdr, PL_MAX_HDRS * sizeof(HeaacSbrHeader)) &&
+    ok = ok && heaac_dev(m, &p->d_state, n * p->words * 4) && heaac_dev(m, &p->d_rng, n * 4) &&
+         heaac_dev(m, &p->d_hdr, PL_MAX_HDRS * sizeof(HeaacSbrHeader)) &&
          hipMemset(p->d_state, 0, n * p->words * 4) == hipSuccess;
     if (ok && aac->object_type == HEAAC_AOT_AAC_MAIN) {
         // every predictor of every channel
         const size_t np = n * (size_t)p->ncore * HEAAC_MAX_PREDICTORS;
-        ok = devmem((void **)&p->d_pred, np * sizeof(HeaacPredictorState)) && heaac_reset_predictors(p->d_pred, np);
+        ok = heaac_dev(m, &p->d_pred, np * sizeof(HeaacPredictorState)) && heaac_reset_predictors(p->d_pred, np);
     }
     ok = ok && heaac_seed_generators(p->d_rng, n);
     p->tab = heaac_sbr_table_create(PL_MAX_HDRS);
-    p->ast = (HeaacAacStream *)calloc(n, sizeof(HeaacAacStream));
-    p->sst = (HeaacSbrStream *)malloc(n * heaac_sbr_stream_bytes());
-    ok = ok && p->tab && p->ast && p->sst;
+    ok = ok && p->tab && heaac_host(m, &p->ast, n * sizeof(HeaacAacStream)) && heaac_host(m, &p->sst, n * heaac_sbr_stream_bytes());
     if (ok) {
         heaac_sbr_stream_init(p->sst, n);
         // the null header (table entry 0) is what frames before their stream's first header point at
@@ -277,7 +262,7 @@ extern "C" int heaac_pipeline_create_streams(HeaacPipeline **out, const HeaacAac
         if ((size_t)threads > n) threads = (int)n;
         ok = (p->pool = heaac_pool_create(threads, pl_slice, p)) != NULL;
         if (ok) p->threads = heaac_pool_threads(p->pool);
-        ok = ok && (!p->he || (p->sst_tmp = (HeaacSbrStream *)malloc(p->threads * heaac_sbr_stream_bytes())) != NULL);
+        ok = ok && (!p->he || heaac_host(m, &p->sst_tmp, p->threads * heaac_sbr_stream_bytes()));
     }
     if (!ok) { heaac_pipeline_destroy(p); return HEAAC_ERR_NOMEM; }
     *out = p;

@@ -130,13 +130,17 @@ static size_t he_chunk_frames(size_t max_frames)
     return chunk < 64 ? 64 : chunk;
 }
 
+// one workspace set per lane, at most one per chunk; a batch that fits one chunk runs on the caller's stream alone
+static size_t he_sets(size_t max_frames)
+{
+    const size_t chunk = he_chunk_frames(max_frames), chunks = (max_frames + chunk - 1) / chunk;
+    const size_t lanes = (size_t)HE_LANES;
+    return chunks <= 1 ? 1 : chunks < lanes ? chunks : lanes;
+}
+
 extern "C" size_t heaac_device_workspace_bytes(size_t max_frames)
 {
-    // one workspace set per lane; a batch that fits one chunk runs on the caller's stream alone
-    const size_t chunk = he_chunk_frames(max_frames);
-    size_t sets = max_frames > chunk ? (size_t)HE_LANES : 1;
-    if (sets > 1 && (max_frames + chunk - 1) / chunk < sets) sets = (max_frames + chunk - 1) / chunk;
-    return sets * chunk * (WS_W_FLOATS + WS_X_FLOATS) * sizeof(float);
+    return he_sets(max_frames) * he_chunk_frames(max_frames) * (WS_W_FLOATS + WS_X_FLOATS) * sizeof(float);
 }
 
 extern "C" int heaac_device_create(HeaacDevice **out, size_t max_frames)
@@ -161,9 +165,7 @@ extern "C" int heaac_device_create(HeaacDevice **out, size_t max_frames)
     d->max_frames = max_frames;
     d->work_bytes = heaac_device_workspace_bytes(max_frames);
     d->chunk = he_chunk_frames(max_frames);
-    d->sets = max_frames > d->chunk ? HE_LANES : 1;
-    if (d->sets > 1 && (max_frames + d->chunk - 1) / d->chunk < (size_t)d->sets)
-        d->sets = (int)((max_frames + d->chunk - 1) / d->chunk);
+    d->sets = (int)he_sets(max_frames);
     int rc = HEAAC_OK;
     if (hipMalloc((void **)&d->d_tab, sizeof(t->f)) != hipSuccess ||
         hipMalloc((void **)&d->d_rev, sizeof(t->rev)) != hipSuccess ||
@@ -239,7 +241,7 @@ extern "C" int heaac_lc_decode_batch(HeaacDevice *dev, int channels,
     if (!d_coeffs || !d_ics || !d_state_in || !d_state_out || !d_pcm)
         return HEAAC_ERR_ARG;
     return heaac_launch_lc(dev->d_tab, dev->d_rev, channels, d_coeffs, d_ics, d_state_in, d_state_out,
-                           d_pcm, pcm_format, n, (hipStream_t)stream);
+                           d_pcm, pcm_format, n, 1, NULL, (hipStream_t)stream);
 }
 
 extern "C" int heaac_lc_decode_streams(HeaacDevice *dev, int channels,
@@ -269,12 +271,8 @@ extern "C" int heaac_lc_decode_streams_ex(HeaacDevice *dev, int channels,
     const size_t frame_bytes = (size_t)channels * 1024 * sizeof(float);
     if (n_streams > SIZE_MAX / frames_per_stream || n_streams * frames_per_stream > SIZE_MAX / frame_bytes)
         return HEAAC_ERR_ARG;
-    // one frame per stream: the per-frame arrays and the state are exactly the batch call's (which knows no mask)
-    if (frames_per_stream == 1 && !d_hold)
-        return heaac_launch_lc(dev->d_tab, dev->d_rev, channels, d_coeffs, d_ics, d_state_in, d_state_out,
-                               d_pcm, pcm_format, n_streams, (hipStream_t)stream);
-    return heaac_launch_lc_streams(dev->d_tab, dev->d_rev, channels, d_coeffs, d_ics, d_state_in, d_state_out,
-                                   d_pcm, pcm_format, n_streams, frames_per_stream, d_hold, (hipStream_t)stream);
+    return heaac_launch_lc(dev->d_tab, dev->d_rev, channels, d_coeffs, d_ics, d_state_in, d_state_out,
+                           d_pcm, pcm_format, n_streams, frames_per_stream, d_hold, (hipStream_t)stream);
 }
 
 extern "C" int heaac_aac_parse_device(HeaacDevice *dev, const HeaacAacConfig *cfg, HeaacAacStream *d_st,
@@ -355,22 +353,13 @@ extern "C" int heaac_spectral_tools_streams_ex(HeaacDevice *dev, int channels, f
     if (n > SIZE_MAX / ((size_t)channels * 1024 * sizeof(float)) || n > SIZE_MAX / sizeof(HeaacToolsFrame) ||
         n > 0x7fffffffull * 256 / (3 * (size_t)channels))
         return HEAAC_ERR_ARG;
-    // one frame per stream: the per-frame arrays and the state are exactly the batch call's
-    // (the batch kernels know no mask: with one, every case runs the chain kernel)
-    if (frames_per_stream == 1 && !d_hold)
-        return heaac_launch_spectral_tools(channels, d_coeffs, d_tools, d_rng_in, d_rng_out, d_pred_in, d_pred_out,
-                                           HEAAC_TOOLS_ALL, NULL, NULL, 0, n_streams, (hipStream_t)stream);
-    // no state: every frame stands alone, one batch call over the S * T frames
-    if (!d_rng_in && !d_pred_in && !d_hold)
-        return heaac_launch_spectral_tools(channels, d_coeffs, d_tools, NULL, NULL, NULL, NULL, HEAAC_TOOLS_ALL,
-                                           NULL, NULL, 0, n, (hipStream_t)stream);
     return heaac_launch_spectral_tools_streams(channels, d_coeffs, d_tools, d_rng_in, d_rng_out, d_pred_in,
                                                d_pred_out, n_streams, frames_per_stream, d_hold, (hipStream_t)stream);
 }
 
 // The HE calls behind their argument checks: n_streams streams of T consecutive frames each.  Whole streams per
 // workspace set (a stream's T frames hand W / X over inside one set); with T = 1 a stream is a frame and the
-// per-frame arrays and the state are exactly the batch call's.
+// per-frame arrays and the state are exactly the batch call's (heaac_launch_he chooses the kernels).
 static int he_walk(HeaacDevice *dev, int cfg, int flags, const float *d_coeffs, const HeaacIcs *d_ics,
                    const HeaacSbrFrame *d_sbr, const HeaacSbrHeader *d_hdr, size_t n_hdr, const HeaacPsFrame *d_ps,
                    const float *d_state_in, float *d_state_out, void *d_pcm, int pcm_format,
@@ -401,27 +390,22 @@ static int he_walk(HeaacDevice *dev, int cfg, int flags, const float *d_coeffs, 
             else forked = k + 1;
         }
     }
+    HeaacHeLaunch a = {};
+    a.d_tab = dev->d_tab; a.d_rev = dev->d_rev; a.cfg = cfg; a.flags = flags; a.d_hdr = d_hdr; a.n_hdr = hdrs;
+    a.pcm_format = pcm_format; a.d_zero = (const float *)dev->d_aux; a.T = T;
     size_t c = 0;
     for (size_t s0 = 0; s0 < n_streams && rc == HEAAC_OK; s0 += per_chunk, c++) {
-        const size_t ns = n_streams - s0 < per_chunk ? n_streams - s0 : per_chunk;
         const size_t f0 = s0 * T;
         const int k = (int)(c % nl);
-        float *ws_W = (float *)dev->d_work + k * set_floats;
-        float *ws_X = ws_W + dev->chunk * WS_W_FLOATS;
-        unsigned char *xtop = dev->d_aux + HE_ZERO_BYTES + 2 * (size_t)k * dev->chunk;
-        hipStream_t ls = lanes ? dev->lane[k] : s;
-        // (the batch kernels know no mask: with one, T = 1 runs the streams kernels too)
-        rc = T == 1 && !d_hold
-            ? heaac_launch_he(dev->d_tab, dev->d_rev, cfg, d_coeffs + f0 * ncore * 1024, d_ics + f0 * ncore,
-                              d_sbr + f0, d_hdr, hdrs, d_ps ? d_ps + f0 : NULL,
-                              d_state_in + s0 * words, d_state_out + s0 * words,
-                              (char *)d_pcm + f0 * pcm_bytes, pcm_format, ws_W, ws_X, dev->d_queue + 16 * k,
-                              xtop, (const float *)dev->d_aux, ns, 0, flags, ls)
-            : heaac_launch_he_streams(dev->d_tab, dev->d_rev, cfg, d_coeffs + f0 * ncore * 1024, d_ics + f0 * ncore,
-                                      d_sbr + f0, d_hdr, hdrs, d_ps ? d_ps + f0 : NULL,
-                                      d_state_in + s0 * words, d_state_out + s0 * words,
-                                      (char *)d_pcm + f0 * pcm_bytes, pcm_format, ws_W, ws_X, dev->d_queue + 16 * k,
-                                      xtop, (const float *)dev->d_aux, ns, T, flags, d_hold ? d_hold + f0 : NULL, ls);
+        a.n_streams = n_streams - s0 < per_chunk ? n_streams - s0 : per_chunk;
+        a.d_coeffs = d_coeffs + f0 * ncore * 1024; a.d_ics = d_ics + f0 * ncore; a.d_sbr = d_sbr + f0;
+        a.d_ps = d_ps ? d_ps + f0 : NULL; a.d_hold = d_hold ? d_hold + f0 : NULL;
+        a.d_state_in = d_state_in + s0 * words; a.d_state_out = d_state_out + s0 * words;
+        a.d_pcm = (char *)d_pcm + f0 * pcm_bytes;
+        a.d_ws_W = (float *)dev->d_work + k * set_floats; a.d_ws_X = a.d_ws_W + dev->chunk * WS_W_FLOATS;
+        a.d_queue = dev->d_queue + 16 * k; a.d_xtop = dev->d_aux + HE_ZERO_BYTES + 2 * (size_t)k * dev->chunk;
+        a.s = lanes ? dev->lane[k] : s;
+        rc = heaac_launch_he(&a);
     }
     if (lanes) {
         // always rejoin, also after a failed launch (a capture must not be left forked)

@@ -33,6 +33,8 @@ struct HeaacCfgShape {
     int ncore, nout;              // core channels, output channels; ncore = 0: not a configuration
     int he;                       // SBR behind the core (2048 samples per frame unless downsampled)
     size_t words;                 // state words per stream
+    // where the parts of a stream's state record begin (the saved overlap is at 0): [ncore] SBR, [nout] synthesis, PS
+    int off_sbr, off_syn, off_ps;
 };
 HeaacCfgShape heaac_cfg_shape(int cfg);
 // the largest state record of the configurations: what a context allocates before its stream has said which it is

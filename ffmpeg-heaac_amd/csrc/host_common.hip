@@ -10,14 +10,20 @@
 
 HeaacCfgShape heaac_cfg_shape(int cfg)
 {
+    HeaacCfgShape c = {};
     switch (cfg) {
-    case HEAAC_CFG_LC_MONO:   return { 1, 1, 0, HEAAC_STATE_WORDS_LC_MONO };
-    case HEAAC_CFG_LC_STEREO: return { 2, 2, 0, HEAAC_STATE_WORDS_LC_STEREO };
-    case HEAAC_CFG_HEV1:      return { 2, 2, 1, HEAAC_STATE_WORDS_HEV1 };
-    case HEAAC_CFG_HEV1_MONO: return { 1, 1, 1, HEAAC_STATE_WORDS_HEV1_MONO };
-    case HEAAC_CFG_HEV2:      return { 1, 2, 1, HEAAC_STATE_WORDS_HEV2 };
+    case HEAAC_CFG_LC_MONO:   c = { 1, 1, 0, HEAAC_STATE_WORDS_LC_MONO }; break;
+    case HEAAC_CFG_LC_STEREO: c = { 2, 2, 0, HEAAC_STATE_WORDS_LC_STEREO }; break;
+    case HEAAC_CFG_HEV1:      c = { 2, 2, 1, HEAAC_STATE_WORDS_HEV1 }; break;
+    case HEAAC_CFG_HEV1_MONO: c = { 1, 1, 1, HEAAC_STATE_WORDS_HEV1_MONO }; break;
+    case HEAAC_CFG_HEV2:      c = { 1, 2, 1, HEAAC_STATE_WORDS_HEV2 }; break;
+    default: return c;
     }
-    return { 0, 0, 0, 0 };
+    // the record of include/heaac_dsp.h: [ncore] saved overlap | [ncore] SBR | [nout] synthesis | PS (HE-AACv2)
+    c.off_sbr = c.ncore * HEAAC_ST_SAVED;
+    c.off_syn = c.off_sbr + c.he * c.ncore * HEAAC_ST_SBR;
+    c.off_ps = c.off_syn + c.he * c.nout * HEAAC_ST_SYNTH;
+    return c;
 }
 
 // ---------------------------------------------------------------------------

@@ -14,6 +14,7 @@
 #include <hip/hip_runtime.h>
 #include "heaac_dsp.h"
 #include <stdint.h>
+#include <type_traits>
 #include "tables.h"
 
 #define WAVE 64
@@ -418,4 +419,56 @@ __device__ __forceinline__ void wg_copy_f4(float *dst, const float *src, int cou
     float4 *d4 = reinterpret_cast<float4 *>(dst);
     for (int i = threadIdx.x; i < count / 4; i += blockDim.x)
         d4[i] = s4[i];
+}
+
+// ---------------------------------------------------------------------------
+// Host side: choosing and launching an instantiation.  The kernels take their variants as template arguments; a
+// launcher writes the launch once, as a generic lambda, and these helpers call it with the run-time choice made a
+// compile-time constant (`auto fmt` -> k<fmt()>) or with the optional trailing argument (`auto... mask`).  Only the
+// combinations a helper names are instantiated.
+// ---------------------------------------------------------------------------
+// "One persistent workgroup per CU" (blocks_per_cu of them for the kernels that fit more), fewer where the work is less
+static inline dim3 persistent_grid(unsigned long long units, int per_block, int blocks_per_cu = 1)
+{
+    const unsigned long long g = (units + per_block - 1) / per_block, cap = 256ull * blocks_per_cu;
+    return dim3((unsigned)(g > cap ? cap : g < 1 ? 1 : g));
+}
+
+// f(std::integral_constant<int, FMT>{}) for a HEAAC_PCM_* value; false: not one (nothing ran)
+template <class F>
+static inline bool with_pcm_format(int pcm_format, F &&f)
+{
+    switch (pcm_format) {
+    case HEAAC_PCM_F32_PLANAR:           f(std::integral_constant<int, HEAAC_PCM_F32_PLANAR>{}); return true;
+    case HEAAC_PCM_S16_INTERLEAVED:      f(std::integral_constant<int, HEAAC_PCM_S16_INTERLEAVED>{}); return true;
+    case HEAAC_PCM_S16_INTERLEAVED_SSE2: f(std::integral_constant<int, HEAAC_PCM_S16_INTERLEAVED_SSE2>{}); return true;
+    }
+    return false;
+}
+
+// the same for channels = 1 or 2
+template <class F>
+static inline bool with_channels(int channels, F &&f)
+{
+    if (channels == 1) f(std::integral_constant<int, 1>{});
+    else if (channels == 2) f(std::integral_constant<int, 2>{});
+    else return false;
+    return true;
+}
+
+// f() without a hold mask, f(mask) with one: the lambda hands `mask...` on as the kernel's trailing argument (hold_mask)
+template <class F>
+static inline void with_hold(const uint8_t *mask, F &&f)
+{
+    if (mask) f(mask);
+    else f();
+}
+
+// The stages that have a batch kernel and a strided one: f(std::false_type{}) for the batch kernel, f(std::true_type{},
+// mask...) for the strided one, which a mask always takes (the batch kernels have no hold test)
+template <class F>
+static inline void with_strided_hold(bool strided, const uint8_t *mask, F &&f)
+{
+    if (strided || mask) with_hold(mask, [&](auto... m) { f(std::true_type{}, m...); });
+    else f(std::false_type{});
 }

@@ -16,6 +16,7 @@
 #include "k_core.h"
 #include "k_core2.h"
 #include "kernels.h"
+#include "host_common.h"
 
 #include "k_hf.h"
 
@@ -1008,194 +1009,91 @@ void k_synth_ds_streams(const float *__restrict__ g_tab, const float *g_X,
 }
 
 // ===========================================================================
-// host side: launch the HE pipeline over one chunk of frames
+// host side: launch the HE pipeline over one chunk of whole streams
 // ===========================================================================
-static int he_grid(unsigned long long units, int per_block)
+// n_streams x T frames: frame (s, t) at record s * T + t of the per-frame arrays, the state one record per stream.  The
+// core + analysis and HF (+ PS) stages run one launch per t, in t order, over the n_streams frames of position t (the
+// record stride is T; frame t reads the state that frame t - 1 left in d_state_out); their W / X hand-over units are
+// t-major (unit t * n_streams + s).  The synthesis stage runs each (stream, channel) chain inside one launch with the
+// ring on chip (k_synth_streams).  One frame per stream without a hold mask is the batch call: its kernels have no
+// record stride and no hold test, and k_synth draws frames where k_synth_streams draws chains.
+extern "C" int heaac_launch_he(const HeaacHeLaunch *a)
 {
-    unsigned long long g = (units + per_block - 1) / per_block;
-    if (g > 256) g = 256;           // one persistent workgroup per CU (LDS-bound kernels)
-    if (g < 1) g = 1;
-    return (int)g;
-}
-
-extern "C" int heaac_launch_he(const float *d_tab, const uint16_t *d_rev, int cfg,
-                               const float *d_coeffs, const HeaacIcs *d_ics,
-                               const HeaacSbrFrame *d_sbr, const HeaacSbrHeader *d_hdr, unsigned n_hdr,
-                               const HeaacPsFrame *d_ps,
-                               const float *d_state_in, float *d_state_out,
-                               void *d_pcm, int pcm_format,
-                               float *d_ws_W, float *d_ws_X, unsigned *d_queue,
-                               unsigned char *d_xtop, const float *d_zero,
-                               size_t n, size_t pcm_frame0, int flags, hipStream_t s)
-{
-    const int ncore = cfg == HEAAC_CFG_HEV1 ? 2 : 1;
-    const int nout  = cfg == HEAAC_CFG_HEV1_MONO ? 1 : 2;
-    int words, off_saved0 = 0, off_sbr0, off_syn0;
-    if (cfg == HEAAC_CFG_HEV1) {
-        words = HEAAC_STATE_WORDS_HEV1; off_sbr0 = 2 * HEAAC_ST_SAVED; off_syn0 = off_sbr0 + 2 * HEAAC_ST_SBR;
-    } else if (cfg == HEAAC_CFG_HEV1_MONO) {
-        words = HEAAC_STATE_WORDS_HEV1_MONO; off_sbr0 = HEAAC_ST_SAVED; off_syn0 = off_sbr0 + HEAAC_ST_SBR;
-    } else if (cfg == HEAAC_CFG_HEV2) {
-        words = HEAAC_STATE_WORDS_HEV2; off_sbr0 = HEAAC_ST_SAVED; off_syn0 = off_sbr0 + HEAAC_ST_SBR;
-    } else
-        return HEAAC_ERR_ARG;
-    const unsigned long long units = (unsigned long long)n * ncore;
+    const HeaacCfgShape c = heaac_cfg_shape(a->cfg);
+    if (!c.he) return HEAAC_ERR_ARG;
+    if (!a->n_streams || !a->T) return HEAAC_OK;
+    const bool strided = a->T > 1 || a->d_hold;
+    const int ncore = c.ncore, nout = c.nout, words = (int)c.words;
+    const unsigned long long S = a->n_streams, T = a->T, units = S * ncore;
+    const float *const d_tab = a->d_tab;
+    float *const state_out = a->d_state_out;
+    hipStream_t s = a->s;
     // ac->sf_scale / ac->add_bias: the C conversion's, or the SIMD configuration's (aacdec.c:573-581)
-    const bool simd = pcm_format == HEAAC_PCM_S16_INTERLEAVED_SSE2;
+    const bool simd = a->pcm_format == HEAAC_PCM_S16_INTERLEAVED_SSE2;
     const float sf_scale = simd ? -1.0f / 1024.0f : HEAAC_SF_SCALE;
-
-    // queue heads of the kernels that draw frames dynamically (k_hfps: [0], k_synth: [2]); the static
-    // stride stays where it measured faster (k_core_ana, k_hfadj: neighbouring waves share lines)
-    if (hipMemsetAsync(d_queue, 0, 64, s) != hipSuccess) return HEAAC_ERR_HIP;
     // every frame's X rows are whole (64 bands) unless the fused HF + PS kernel says otherwise
-    if (hipMemsetAsync(d_xtop, 64, 2 * n, s) != hipSuccess) return HEAAC_ERR_HIP;
-    hipLaunchKernelGGL(k_core_ana<false>, dim3(he_grid((units + 1) / 2, CA_WAVES)), dim3(CA_WAVES * WAVE), 0, s,
-                       d_tab, d_rev, d_coeffs, d_ics, d_state_in, d_state_out, words, ncore,
-                       off_saved0, off_sbr0, d_ws_W, 1 / (-1024 * sf_scale), units, 1ull);
-    if (cfg == HEAAC_CFG_HEV2) {
-        // HF adjustment + baseline PS in one kernel; the general PS kernel finishes the
-        // frames with another PS layout (it skips the rest)
-        const int off_ps = off_syn0 + 2 * HEAAC_ST_SYNTH;
-        int rc = heaac_launch_hfps(d_tab, d_sbr, d_hdr, n_hdr, d_ps, d_ws_W, d_state_in, d_state_out, words,
-                                   off_sbr0, off_ps, d_ws_X, n, d_queue, d_xtop, 1, nullptr, s);
-        if (rc != HEAAC_OK) return rc;
-        rc = heaac_launch_ps(d_tab, d_ps, d_sbr, d_hdr, n_hdr, d_state_in, d_state_out, words, off_ps, d_ws_X, n, 1, nullptr, s);
-        if (rc != HEAAC_OK) return rc;
-    } else {
-        hipLaunchKernelGGL(k_hfadj<false>, dim3(he_grid((units + 1) / 2, HF_WAVES)), dim3(HF_WAVES * WAVE), 0, s,
-                           d_tab, d_sbr, d_hdr, n_hdr, d_ws_W, d_state_in, d_state_out, words, ncore, off_sbr0,
-                           d_ws_X, units, d_queue + 1, d_xtop, 1ull);
-    }
-    const float scale = -1024 * sf_scale, bias = simd ? 0.0f : HEAAC_ADD_BIAS;
-    if (flags & HEAAC_HE_DOWNSAMPLED) {
-        const dim3 gd(he_grid(n, DS_WAVES)), bd(DS_WAVES * WAVE);
-        char *pcm = (char *)d_pcm + pcm_frame0 * nout * 1024 * (pcm_format == HEAAC_PCM_F32_PLANAR ? 4 : 2);
-        if (pcm_format == HEAAC_PCM_F32_PLANAR)
-            hipLaunchKernelGGL((k_synth_ds<HEAAC_PCM_F32_PLANAR>), gd, bd, 0, s, d_tab, d_ws_X, d_state_in, d_state_out,
-                               words, off_syn0, nout, (void *)pcm, scale, bias, (unsigned long long)n);
-        else if (simd)
-            hipLaunchKernelGGL((k_synth_ds<HEAAC_PCM_S16_INTERLEAVED_SSE2>), gd, bd, 0, s, d_tab, d_ws_X, d_state_in, d_state_out,
-                               words, off_syn0, nout, (void *)pcm, scale, bias, (unsigned long long)n);
-        else
-            hipLaunchKernelGGL((k_synth_ds<HEAAC_PCM_S16_INTERLEAVED>), gd, bd, 0, s, d_tab, d_ws_X, d_state_in, d_state_out,
-                               words, off_syn0, nout, (void *)pcm, scale, bias, (unsigned long long)n);
-        return hipGetLastError() == hipSuccess ? HEAAC_OK : HEAAC_ERR_HIP;
-    }
-    const dim3 g(he_grid(n, SYN_WAVES_F32)), b(SYN_WAVES_F32 * WAVE);
-    if (pcm_format == HEAAC_PCM_F32_PLANAR)
-        hipLaunchKernelGGL((k_synth<HEAAC_PCM_F32_PLANAR>), g, b, 0, s, d_tab, d_ws_X, d_state_in, d_state_out,
-                           words, off_syn0, nout, d_pcm, scale, bias,
-                           (unsigned long long)n, (unsigned long long)pcm_frame0, d_queue + 2, d_xtop, d_zero);
-    else if (pcm_format == HEAAC_PCM_S16_INTERLEAVED)
-        hipLaunchKernelGGL((k_synth<HEAAC_PCM_S16_INTERLEAVED>), g, b, 0, s, d_tab, d_ws_X, d_state_in, d_state_out,
-                           words, off_syn0, nout, d_pcm, scale, bias,
-                           (unsigned long long)n, (unsigned long long)pcm_frame0, d_queue + 2, d_xtop, d_zero);
-    else if (simd)
-        hipLaunchKernelGGL((k_synth<HEAAC_PCM_S16_INTERLEAVED_SSE2>), g, b, 0, s, d_tab, d_ws_X, d_state_in, d_state_out,
-                           words, off_syn0, nout, d_pcm, scale, bias,
-                           (unsigned long long)n, (unsigned long long)pcm_frame0, d_queue + 2, d_xtop, d_zero);
-    else
-        return HEAAC_ERR_ARG;
-    return hipGetLastError() == hipSuccess ? HEAAC_OK : HEAAC_ERR_HIP;
-}
-
-// A streams kernel on stream `s` (a variable of the caller): the plain instantiation, or with a hold mask the one that
-// takes it as its trailing argument (k_common.h hold_mask)
-#define HE_LAUNCH_STREAMS(PLAIN, HOLD, mask, grid, block, ...)                                        \
-    do {                                                                                          \
-        const uint8_t *he_mask_ = (mask);                                                         \
-        if (he_mask_) hipLaunchKernelGGL(HOLD, grid, block, 0, s, __VA_ARGS__, he_mask_);         \
-        else hipLaunchKernelGGL(PLAIN, grid, block, 0, s, __VA_ARGS__);                           \
-    } while (0)
-
-// The streams form (heaac_he_decode_streams) over one chunk of whole streams: n_streams x T frames, frame (s, t) at
-// record s * T + t of the per-frame arrays, the state one record per stream.  The core + analysis and HF (+ PS) stages
-// run one launch per t, in t order, over the n_streams frames of position t (the record stride is T; frame t reads the
-// state that frame t - 1 left in d_state_out); their W / X hand-over units are t-major (unit t * n_streams + s).  The
-// synthesis stage runs each (stream, channel) chain inside one launch with the ring on chip (k_synth_streams).
-extern "C" int heaac_launch_he_streams(const float *d_tab, const uint16_t *d_rev, int cfg,
-                                       const float *d_coeffs, const HeaacIcs *d_ics,
-                                       const HeaacSbrFrame *d_sbr, const HeaacSbrHeader *d_hdr, unsigned n_hdr,
-                                       const HeaacPsFrame *d_ps,
-                                       const float *d_state_in, float *d_state_out,
-                                       void *d_pcm, int pcm_format,
-                                       float *d_ws_W, float *d_ws_X, unsigned *d_queue,
-                                       unsigned char *d_xtop, const float *d_zero,
-                                       size_t n_streams, size_t T, int flags, const uint8_t *d_hold, hipStream_t s)
-{
-    const int ncore = cfg == HEAAC_CFG_HEV1 ? 2 : 1;
-    const int nout  = cfg == HEAAC_CFG_HEV1_MONO ? 1 : 2;
-    int words, off_saved0 = 0, off_sbr0, off_syn0;
-    if (cfg == HEAAC_CFG_HEV1) {
-        words = HEAAC_STATE_WORDS_HEV1; off_sbr0 = 2 * HEAAC_ST_SAVED; off_syn0 = off_sbr0 + 2 * HEAAC_ST_SBR;
-    } else if (cfg == HEAAC_CFG_HEV1_MONO) {
-        words = HEAAC_STATE_WORDS_HEV1_MONO; off_sbr0 = HEAAC_ST_SAVED; off_syn0 = off_sbr0 + HEAAC_ST_SBR;
-    } else if (cfg == HEAAC_CFG_HEV2) {
-        words = HEAAC_STATE_WORDS_HEV2; off_sbr0 = HEAAC_ST_SAVED; off_syn0 = off_sbr0 + HEAAC_ST_SBR;
-    } else
-        return HEAAC_ERR_ARG;
-    if (!n_streams || !T) return HEAAC_OK;
-    const unsigned long long units = (unsigned long long)n_streams * ncore;
-    const bool simd = pcm_format == HEAAC_PCM_S16_INTERLEAVED_SSE2;
-    const float sf_scale = simd ? -1.0f / 1024.0f : HEAAC_SF_SCALE;
-    if (hipMemsetAsync(d_xtop, 64, 2 * n_streams * T, s) != hipSuccess) return HEAAC_ERR_HIP;
+    HIP_OK(hipMemsetAsync(a->d_xtop, 64, 2 * S * T, s));
     // With a hold mask the first frame of a stream that runs may be any t, or none: the state is carried over in front
     // of the launches and every stage reads and writes d_state_out.
-    if (d_hold && d_state_in != d_state_out) {
-        if (hipMemcpyAsync(d_state_out, d_state_in, n_streams * (size_t)words * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess)
-            return HEAAC_ERR_HIP;
-        d_state_in = d_state_out;
+    const float *state_in = a->d_state_in;
+    if (a->d_hold && state_in != state_out) {
+        HIP_OK(hipMemcpyAsync(state_out, state_in, S * (size_t)words * sizeof(float), hipMemcpyDeviceToDevice, s));
+        state_in = state_out;
     }
     for (size_t t = 0; t < T; t++) {
-        const float *st_in = t ? d_state_out : d_state_in;
-        float *W = d_ws_W + t * units * 2048;
-        float *X = d_ws_X + t * n_streams * 2 * HE_X_CHANNEL;
-        unsigned char *xtop = d_xtop + 2 * t * n_streams;
-        HE_LAUNCH_STREAMS((k_core_ana<true>), (k_core_ana<true, const uint8_t *>), d_hold ? d_hold + t : nullptr,
-                          dim3(he_grid((units + 1) / 2, CA_WAVES)), dim3(CA_WAVES * WAVE),
-                          d_tab, d_rev, d_coeffs + t * ncore * 1024, d_ics + t * ncore, st_in, d_state_out, words, ncore,
-                          off_saved0, off_sbr0, W, 1 / (-1024 * sf_scale), units, (unsigned long long)T);
-        // queue heads (k_hfps: [0], k_hfadj: [1]; k_synth_streams: [2], which no launch before it draws from)
-        if (hipMemsetAsync(d_queue, 0, 64, s) != hipSuccess) return HEAAC_ERR_HIP;
-        if (cfg == HEAAC_CFG_HEV2) {
-            const int off_ps = off_syn0 + 2 * HEAAC_ST_SYNTH;
-            int rc = heaac_launch_hfps(d_tab, d_sbr + t, d_hdr, n_hdr, d_ps + t, W, st_in, d_state_out, words,
-                                       off_sbr0, off_ps, X, n_streams, d_queue, xtop, T, d_hold ? d_hold + t : nullptr, s);
+        const float *st_in = t ? state_out : state_in;
+        float *W = a->d_ws_W + t * units * 2048;
+        float *X = a->d_ws_X + t * S * 2 * HE_X_CHANNEL;
+        unsigned char *xtop = a->d_xtop + 2 * t * S;
+        const uint8_t *hold = a->d_hold ? a->d_hold + t : nullptr;
+        // queue heads of the kernels that draw frames dynamically (k_hfps: [0], k_hfadj: [1], k_synth(_streams): [2],
+        // which no launch before it draws from); the static stride stays where it measured faster (k_core_ana:
+        // neighbouring waves share lines)
+        HIP_OK(hipMemsetAsync(a->d_queue, 0, 64, s));
+        with_strided_hold(strided, hold, [&](auto st, auto... m) {
+            k_core_ana<st()><<<persistent_grid((units + 1) / 2, CA_WAVES), CA_WAVES * WAVE, 0, s>>>(
+                d_tab, a->d_rev, a->d_coeffs + t * ncore * 1024, a->d_ics + t * ncore, st_in, state_out, words, ncore, 0,
+                c.off_sbr, W, 1 / (-1024 * sf_scale), units, T, m...);
+        });
+        if (a->cfg == HEAAC_CFG_HEV2) {
+            // HF adjustment + baseline PS in one kernel; the general PS kernel finishes the
+            // frames with another PS layout (it skips the rest)
+            int rc = heaac_launch_hfps(a, t, st_in, W, X);
             if (rc != HEAAC_OK) return rc;
-            rc = heaac_launch_ps(d_tab, d_ps + t, d_sbr + t, d_hdr, n_hdr, st_in, d_state_out, words, off_ps, X,
-                                 n_streams, T, d_hold ? d_hold + t : nullptr, s);
+            rc = heaac_launch_ps(a, t, st_in, X);
             if (rc != HEAAC_OK) return rc;
         } else {
-            HE_LAUNCH_STREAMS((k_hfadj<true>), (k_hfadj<true, const uint8_t *>), d_hold ? d_hold + t : nullptr,
-                              dim3(he_grid((units + 1) / 2, HF_WAVES)), dim3(HF_WAVES * WAVE),
-                              d_tab, d_sbr + t, d_hdr, n_hdr, W, st_in, d_state_out, words, ncore, off_sbr0,
-                              X, units, d_queue + 1, xtop, (unsigned long long)T);
+            with_strided_hold(strided, hold, [&](auto st, auto... m) {
+                k_hfadj<st()><<<persistent_grid((units + 1) / 2, HF_WAVES), HF_WAVES * WAVE, 0, s>>>(
+                    d_tab, a->d_sbr + t, a->d_hdr, a->n_hdr, W, st_in, state_out, words, ncore, c.off_sbr, X, units,
+                    a->d_queue + 1, xtop, T, m...);
+            });
         }
     }
     const float scale = -1024 * sf_scale, bias = simd ? 0.0f : HEAAC_ADD_BIAS;
-    const unsigned long long chains = (unsigned long long)n_streams * nout;
-    const unsigned long long ns = n_streams;
-    const unsigned Tu = (unsigned)T;
-    if (flags & HEAAC_HE_DOWNSAMPLED) {
-        const dim3 gd(he_grid(chains, DS_WAVES)), bd(DS_WAVES * WAVE);
-#define SYN_DS(FMT) \
-        HE_LAUNCH_STREAMS((k_synth_ds_streams<FMT>), (k_synth_ds_streams<FMT, const uint8_t *>), d_hold, gd, bd, d_tab, d_ws_X, \
-                          d_state_in, d_state_out, words, off_syn0, nout, d_pcm, scale, bias, ns, Tu)
-        if (pcm_format == HEAAC_PCM_F32_PLANAR) SYN_DS(HEAAC_PCM_F32_PLANAR);
-        else if (simd) SYN_DS(HEAAC_PCM_S16_INTERLEAVED_SSE2);
-        else SYN_DS(HEAAC_PCM_S16_INTERLEAVED);
-#undef SYN_DS
-        return hipGetLastError() == hipSuccess ? HEAAC_OK : HEAAC_ERR_HIP;
-    }
-    const dim3 g(he_grid(chains, SYN_WAVES_F32)), b(SYN_WAVES_F32 * WAVE);
-#define SYN(FMT) \
-    HE_LAUNCH_STREAMS((k_synth_streams<FMT>), (k_synth_streams<FMT, const uint8_t *>), d_hold, g, b, d_tab, d_ws_X, d_state_in, \
-                      d_state_out, words, off_syn0, nout, d_pcm, scale, bias, ns, Tu, d_queue + 2, d_xtop, d_zero)
-    if (pcm_format == HEAAC_PCM_F32_PLANAR) SYN(HEAAC_PCM_F32_PLANAR);
-    else if (pcm_format == HEAAC_PCM_S16_INTERLEAVED) SYN(HEAAC_PCM_S16_INTERLEAVED);
-    else if (simd) SYN(HEAAC_PCM_S16_INTERLEAVED_SSE2);
-    else return HEAAC_ERR_ARG;
-#undef SYN
+    const bool ds = a->flags & HEAAC_HE_DOWNSAMPLED;
+    const int waves = ds ? DS_WAVES : SYN_WAVES_F32;
+    const dim3 g = persistent_grid(strided ? S * nout : S, waves), b(waves * WAVE);
+    const bool known = with_pcm_format(a->pcm_format, [&](auto fmt) {
+        if (!strided && ds)
+            k_synth_ds<fmt()><<<g, b, 0, s>>>(d_tab, a->d_ws_X, state_in, state_out, words, c.off_syn, nout, a->d_pcm,
+                                              scale, bias, S);
+        else if (!strided)
+            k_synth<fmt()><<<g, b, 0, s>>>(d_tab, a->d_ws_X, state_in, state_out, words, c.off_syn, nout, a->d_pcm, scale,
+                                           bias, S, 0ull, a->d_queue + 2, a->d_xtop, a->d_zero);
+        else if (ds)
+            with_hold(a->d_hold, [&](auto... m) {
+                k_synth_ds_streams<fmt()><<<g, b, 0, s>>>(d_tab, a->d_ws_X, state_in, state_out, words, c.off_syn, nout,
+                                                          a->d_pcm, scale, bias, S, (unsigned)T, m...);
+            });
+        else
+            with_hold(a->d_hold, [&](auto... m) {
+                k_synth_streams<fmt()><<<g, b, 0, s>>>(d_tab, a->d_ws_X, state_in, state_out, words, c.off_syn, nout, a->d_pcm,
+                                                       scale, bias, S, (unsigned)T, a->d_queue + 2, a->d_xtop, a->d_zero,
+                                                       m...);
+            });
+    });
+    if (!known) return HEAAC_ERR_ARG;
     return hipGetLastError() == hipSuccess ? HEAAC_OK : HEAAC_ERR_HIP;
 }
 
@@ -1203,7 +1101,7 @@ extern "C" int heaac_launch_qmf_analysis(const float *d_tab, const float *d_in, 
                                          float *d_xh_out, float *d_W, float scale, size_t n, hipStream_t s)
 {
     if (!n) return HEAAC_OK;
-    hipLaunchKernelGGL(k_qmf_analysis, dim3(he_grid(n, ANA_WAVES)), dim3(ANA_WAVES * WAVE), 0, s,
+    hipLaunchKernelGGL(k_qmf_analysis, persistent_grid(n, ANA_WAVES), dim3(ANA_WAVES * WAVE), 0, s,
                        d_tab, d_in, d_xh_in, d_xh_out, d_W, scale, (unsigned long long)n);
     return hipGetLastError() == hipSuccess ? HEAAC_OK : HEAAC_ERR_HIP;
 }
@@ -1213,7 +1111,7 @@ extern "C" int heaac_launch_qmf_synthesis(const float *d_tab, const float *d_X, 
                                           size_t n, hipStream_t s)
 {
     if (!n) return HEAAC_OK;
-    hipLaunchKernelGGL(k_qmf_synthesis, dim3(he_grid(n, SYN_WAVES)), dim3(SYN_WAVES * WAVE), 0, s,
+    hipLaunchKernelGGL(k_qmf_synthesis, persistent_grid(n, SYN_WAVES), dim3(SYN_WAVES * WAVE), 0, s,
                        d_tab, d_X, d_v_in, d_v_out, d_out, scale, bias, (unsigned long long)n);
     return hipGetLastError() == hipSuccess ? HEAAC_OK : HEAAC_ERR_HIP;
 }
@@ -1223,7 +1121,7 @@ extern "C" int heaac_launch_qmf_synthesis_ds(const float *d_tab, const float *d_
                                             size_t n, hipStream_t s)
 {
     if (n == 0) return HEAAC_OK;
-    hipLaunchKernelGGL(k_qmf_synthesis_ds, dim3(he_grid(n, DS_WAVES)), dim3(DS_WAVES * WAVE), 0, s,
+    hipLaunchKernelGGL(k_qmf_synthesis_ds, persistent_grid(n, DS_WAVES), dim3(DS_WAVES * WAVE), 0, s,
                        d_tab, d_X, d_v_in, d_v_out, d_out, scale, bias, (unsigned long long)n);
     return hipGetLastError() == hipSuccess ? HEAAC_OK : HEAAC_ERR_HIP;
 }

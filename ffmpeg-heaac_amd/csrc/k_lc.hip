@@ -346,65 +346,32 @@ __global__ void k_imdct_mirror(float *g_out, int n, unsigned long long count)
 }
 
 // ---------------------------------------------------------------------------
-static int grid_for(unsigned long long units, int per_block, int blocks_per_cu)
-{
-    unsigned long long g = (units + per_block - 1) / per_block;
-    const unsigned long long cap = 256ull * blocks_per_cu;
-    if (g > cap) g = cap;
-    if (g < 1) g = 1;
-    return (int)g;
-}
-
+// S streams x T frames.  One frame per stream without a hold mask is the batch call: the per-frame arrays and the
+// state are exactly its own, and k_lc_decode takes the frames two channels to a wave.
 extern "C" int heaac_launch_lc(const float *d_tab, const uint16_t *d_rev, int channels,
                                const float *d_coeffs, const HeaacIcs *d_ics,
                                const float *d_state_in, float *d_state_out,
-                               void *d_pcm, int pcm_format, size_t n, hipStream_t s)
-{
-    if (n == 0) return HEAAC_OK;
-    const unsigned long long pairs = ((unsigned long long)n * channels + 1) / 2;
-    const int grid = grid_for(pairs, LC2_WAVES, 1);
-    const dim3 b(LC2_WAVES * WAVE);
-#define LAUNCH(CH, FMT) \
-    hipLaunchKernelGGL((k_lc_decode<CH, FMT>), dim3(grid), b, 0, s, d_tab, d_rev, d_coeffs, d_ics, \
-                       d_state_in, d_state_out, d_pcm, (unsigned long long)n)
-    if (channels == 1 && pcm_format == HEAAC_PCM_F32_PLANAR) LAUNCH(1, HEAAC_PCM_F32_PLANAR);
-    else if (channels == 1 && pcm_format == HEAAC_PCM_S16_INTERLEAVED) LAUNCH(1, HEAAC_PCM_S16_INTERLEAVED);
-    else if (channels == 2 && pcm_format == HEAAC_PCM_F32_PLANAR) LAUNCH(2, HEAAC_PCM_F32_PLANAR);
-    else if (channels == 2 && pcm_format == HEAAC_PCM_S16_INTERLEAVED) LAUNCH(2, HEAAC_PCM_S16_INTERLEAVED);
-    else if (channels == 1 && pcm_format == HEAAC_PCM_S16_INTERLEAVED_SSE2) LAUNCH(1, HEAAC_PCM_S16_INTERLEAVED_SSE2);
-    else if (channels == 2 && pcm_format == HEAAC_PCM_S16_INTERLEAVED_SSE2) LAUNCH(2, HEAAC_PCM_S16_INTERLEAVED_SSE2);
-    else return HEAAC_ERR_ARG;
-#undef LAUNCH
-    return hipGetLastError() == hipSuccess ? HEAAC_OK : HEAAC_ERR_HIP;
-}
-
-extern "C" int heaac_launch_lc_streams(const float *d_tab, const uint16_t *d_rev, int channels,
-                                       const float *d_coeffs, const HeaacIcs *d_ics,
-                                       const float *d_state_in, float *d_state_out,
-                                       void *d_pcm, int pcm_format, size_t n_streams, size_t frames_per_stream,
-                                       const uint8_t *d_hold, hipStream_t s)
+                               void *d_pcm, int pcm_format, size_t n_streams, size_t frames_per_stream,
+                               const uint8_t *d_hold, hipStream_t s)
 {
     if (n_streams == 0) return HEAAC_OK;
     const unsigned long long S = n_streams, T = frames_per_stream;
-    const unsigned long long chains = channels == 2 ? S : (S + 1) / 2;
-#define LAUNCH(CH, FMT) \
-    do { \
-        const dim3 g(grid_for(chains, lcs_waves<CH, FMT>(), 1)), b(lcs_waves<CH, FMT>() * WAVE); \
-        if (d_hold) \
-            hipLaunchKernelGGL((k_lc_decode_streams<CH, FMT, const uint8_t *>), g, b, 0, s, d_tab, d_rev, d_coeffs, d_ics, \
-                               d_state_in, d_state_out, d_pcm, S, T, d_hold); \
-        else \
-            hipLaunchKernelGGL((k_lc_decode_streams<CH, FMT>), g, b, 0, s, d_tab, d_rev, d_coeffs, d_ics, \
-                               d_state_in, d_state_out, d_pcm, S, T); \
-    } while (0)
-    if (channels == 1 && pcm_format == HEAAC_PCM_F32_PLANAR) LAUNCH(1, HEAAC_PCM_F32_PLANAR);
-    else if (channels == 1 && pcm_format == HEAAC_PCM_S16_INTERLEAVED) LAUNCH(1, HEAAC_PCM_S16_INTERLEAVED);
-    else if (channels == 2 && pcm_format == HEAAC_PCM_F32_PLANAR) LAUNCH(2, HEAAC_PCM_F32_PLANAR);
-    else if (channels == 2 && pcm_format == HEAAC_PCM_S16_INTERLEAVED) LAUNCH(2, HEAAC_PCM_S16_INTERLEAVED);
-    else if (channels == 1 && pcm_format == HEAAC_PCM_S16_INTERLEAVED_SSE2) LAUNCH(1, HEAAC_PCM_S16_INTERLEAVED_SSE2);
-    else if (channels == 2 && pcm_format == HEAAC_PCM_S16_INTERLEAVED_SSE2) LAUNCH(2, HEAAC_PCM_S16_INTERLEAVED_SSE2);
-    else return HEAAC_ERR_ARG;
-#undef LAUNCH
+    bool known = false;
+    with_channels(channels, [&](auto ch) {
+        known = with_pcm_format(pcm_format, [&](auto fmt) {
+            if (T == 1 && !d_hold) {
+                k_lc_decode<ch(), fmt()><<<persistent_grid((S * ch() + 1) / 2, LC2_WAVES), LC2_WAVES * WAVE, 0, s>>>(
+                    d_tab, d_rev, d_coeffs, d_ics, d_state_in, d_state_out, d_pcm, S);
+                return;
+            }
+            constexpr int waves = lcs_waves<ch(), fmt()>();
+            with_hold(d_hold, [&](auto... m) {
+                k_lc_decode_streams<ch(), fmt()><<<persistent_grid(ch() == 2 ? S : (S + 1) / 2, waves), waves * WAVE, 0, s>>>(
+                    d_tab, d_rev, d_coeffs, d_ics, d_state_in, d_state_out, d_pcm, S, T, m...);
+            });
+        });
+    });
+    if (!known) return HEAAC_ERR_ARG;
     return hipGetLastError() == hipSuccess ? HEAAC_OK : HEAAC_ERR_HIP;
 }
 
@@ -415,19 +382,19 @@ extern "C" int heaac_launch_imdct_half(const float *d_tab, const uint16_t *d_rev
     const unsigned long long nn = n;
     switch (which) {
     case 0:
-        hipLaunchKernelGGL((k_imdct_half_core<0>), dim3(grid_for(n, LC_WAVES, 2)), dim3(LC_WAVES * WAVE),
+        hipLaunchKernelGGL((k_imdct_half_core<0>), persistent_grid(n, LC_WAVES, 2), dim3(LC_WAVES * WAVE),
                            0, s, d_tab, d_rev, d_out, d_in, nn);
         break;
     case 1:
-        hipLaunchKernelGGL((k_imdct_half_core<1>), dim3(grid_for((n + 7) / 8, LC_WAVES, 2)),
+        hipLaunchKernelGGL((k_imdct_half_core<1>), persistent_grid((n + 7) / 8, LC_WAVES, 2),
                            dim3(LC_WAVES * WAVE), 0, s, d_tab, d_rev, d_out, d_in, nn);
         break;
     case 2:
-        hipLaunchKernelGGL((k_imdct_half_128<2>), dim3(grid_for(n, 256, 4)), dim3(256), 0, s,
+        hipLaunchKernelGGL((k_imdct_half_128<2>), persistent_grid(n, 256, 4), dim3(256), 0, s,
                            d_tab, d_out, d_in, nn);
         break;
     case 3:
-        hipLaunchKernelGGL((k_imdct_half_128<3>), dim3(grid_for(n, 256, 4)), dim3(256), 0, s,
+        hipLaunchKernelGGL((k_imdct_half_128<3>), persistent_grid(n, 256, 4), dim3(256), 0, s,
                            d_tab, d_out, d_in, nn);
         break;
     default:
@@ -439,7 +406,7 @@ extern "C" int heaac_launch_imdct_half(const float *d_tab, const uint16_t *d_rev
 extern "C" int heaac_launch_fft_calc(const float *d_tab, int nbits, float *d_z, size_t n, hipStream_t s)
 {
     if (n == 0) return HEAAC_OK;
-    const dim3 g(grid_for(n, LC_WAVES, 4)), b(LC_WAVES * WAVE);
+    const dim3 g = persistent_grid(n, LC_WAVES, 4), b(LC_WAVES * WAVE);
     const unsigned long long nn = n;
     if (nbits == 9)      hipLaunchKernelGGL((k_fft_calc<9>), g, b, 0, s, d_tab, d_z, nn);
     else if (nbits == 6) hipLaunchKernelGGL((k_fft_calc<6>), g, b, 0, s, d_tab, d_z, nn);

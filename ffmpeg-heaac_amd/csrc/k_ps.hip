@@ -11,6 +11,7 @@
 // registers; the hybrid sub-subbands of the lowest 3 / 5 QMF bands are kept in LDS.
 #include "k_common.h"
 #include "kernels.h"
+#include "host_common.h"
 
 #include "k_hf.h"
 #include "k_psf.h"
@@ -212,58 +213,32 @@ void k_hfps(const float *__restrict__ g_tab, const HeaacSbrFrame *__restrict__ g
 
 #define PS_WAVES_GEN 5
 
-// The frames k_hfps leaves (every layout but the baseline one).  rstride: records between consecutive frames of the
-// launch (1: the batch form; heaac_he_decode_streams passes its frames per stream)
-extern "C" int heaac_launch_ps(const float *d_tab, const HeaacPsFrame *d_ps, const HeaacSbrFrame *d_sbr,
-                               const HeaacSbrHeader *d_hdr, unsigned n_hdr, const float *d_state_in, float *d_state_out,
-                               int state_words, int off_ps, float *d_ws_X, size_t n, size_t rstride,
-                               const uint8_t *d_hold, hipStream_t s)
+// The two HE-AACv2 launches of heaac_launch_he (k_he.hip) for position t of its streams: the records are read with a
+// stride of T frames and the state by stream, from st_in; W / X are the hand-over units of position t.  One frame per
+// stream without a hold mask runs the batch kernels (no record stride, no hold test).
+// HF adjustment of the mono core channel fused with baseline Parametric Stereo
+extern "C" int heaac_launch_hfps(const HeaacHeLaunch *a, size_t t, const float *st_in, const float *W, float *X)
 {
-    if (!n) return HEAAC_OK;
-    const unsigned long long rs = rstride;
-    unsigned long long g = (n + PS_WAVES_GEN - 1) / PS_WAVES_GEN;
-    if (g > 256) g = 256;
-    if (d_hold)
-        hipLaunchKernelGGL((k_ps<true, PS_WAVES_GEN, true, const uint8_t *>), dim3((unsigned)g), dim3(PS_WAVES_GEN * WAVE), 0, s,
-                           d_tab, d_ps, d_sbr, d_hdr, n_hdr, d_state_in, d_state_out, state_words, off_ps, d_ws_X,
-                           (unsigned long long)n, rs, d_hold);
-    else if (rs == 1)
-        hipLaunchKernelGGL((k_ps<true, PS_WAVES_GEN>), dim3((unsigned)g), dim3(PS_WAVES_GEN * WAVE), 0, s, d_tab,
-                           d_ps, d_sbr, d_hdr, n_hdr, d_state_in, d_state_out, state_words, off_ps, d_ws_X,
-                           (unsigned long long)n, rs);
-    else
-        hipLaunchKernelGGL((k_ps<true, PS_WAVES_GEN, true>), dim3((unsigned)g), dim3(PS_WAVES_GEN * WAVE), 0, s, d_tab,
-                           d_ps, d_sbr, d_hdr, n_hdr, d_state_in, d_state_out, state_words, off_ps, d_ws_X,
-                           (unsigned long long)n, rs);
+    const HeaacCfgShape c = heaac_cfg_shape(a->cfg);
+    const unsigned long long S = a->n_streams, T = a->T;
+    with_strided_hold(T != 1, a->d_hold ? a->d_hold + t : nullptr, [&](auto st, auto... m) {
+        k_hfps<st()><<<persistent_grid(S, HFPS_WAVES), HFPS_WAVES * WAVE, 0, a->s>>>(
+            a->d_tab, a->d_sbr + t, a->d_hdr, a->n_hdr, a->d_ps + t, W, st_in, a->d_state_out, (int)c.words, c.off_sbr,
+            c.off_ps, X, S, a->d_queue, a->d_xtop + 2 * t * S, 0, T, m...);
+    });
     return hipGetLastError() == hipSuccess ? HEAAC_OK : HEAAC_ERR_HIP;
 }
 
-// HF adjustment of the mono core channel fused with baseline Parametric Stereo (rstride: as heaac_launch_ps)
-extern "C" int heaac_launch_hfps(const float *d_tab, const HeaacSbrFrame *d_sbr, const HeaacSbrHeader *d_hdr,
-                                 unsigned n_hdr, const HeaacPsFrame *d_ps, const float *d_ws_W,
-                                 const float *d_state_in, float *d_state_out, int state_words,
-                                 int off_sbr, int off_ps, float *d_ws_X, size_t n, unsigned *d_queue,
-                                 unsigned char *d_xtop, size_t rstride, const uint8_t *d_hold, hipStream_t s)
+// The frames k_hfps leaves (every layout but the baseline one)
+extern "C" int heaac_launch_ps(const HeaacHeLaunch *a, size_t t, const float *st_in, float *X)
 {
-    if (!n) return HEAAC_OK;
-    unsigned long long g = (n + HFPS_WAVES - 1) / HFPS_WAVES;
-    if (g > 256) g = 256;
-    if (d_hold) {
-        // (with a mask also at one frame per stream: the batch kernel has no hold test)
-        hipLaunchKernelGGL((k_hfps<true, const uint8_t *>), dim3((unsigned)g), dim3(HFPS_WAVES * WAVE), 0, s, d_tab, d_sbr, d_hdr,
-                           n_hdr, d_ps, d_ws_W, d_state_in, d_state_out, state_words, off_sbr, off_ps, d_ws_X,
-                           (unsigned long long)n, d_queue, d_xtop, 0, (unsigned long long)rstride, d_hold);
-        return hipGetLastError() == hipSuccess ? HEAAC_OK : HEAAC_ERR_HIP;
-    }
-    if (rstride != 1) {
-        hipLaunchKernelGGL(k_hfps<true>, dim3((unsigned)g), dim3(HFPS_WAVES * WAVE), 0, s, d_tab, d_sbr, d_hdr, n_hdr, d_ps,
-                           d_ws_W, d_state_in, d_state_out, state_words, off_sbr, off_ps, d_ws_X,
-                           (unsigned long long)n, d_queue, d_xtop, 0, (unsigned long long)rstride);
-        return hipGetLastError() == hipSuccess ? HEAAC_OK : HEAAC_ERR_HIP;
-    }
-    hipLaunchKernelGGL(k_hfps<false>, dim3((unsigned)g), dim3(HFPS_WAVES * WAVE), 0, s, d_tab, d_sbr, d_hdr, n_hdr, d_ps,
-                       d_ws_W, d_state_in, d_state_out, state_words, off_sbr, off_ps, d_ws_X,
-                       (unsigned long long)n, d_queue, d_xtop, 0, 1ull);
+    const HeaacCfgShape c = heaac_cfg_shape(a->cfg);
+    const unsigned long long S = a->n_streams, T = a->T;
+    with_strided_hold(T != 1, a->d_hold ? a->d_hold + t : nullptr, [&](auto st, auto... m) {
+        k_ps<true, PS_WAVES_GEN, st()><<<persistent_grid(S, PS_WAVES_GEN), PS_WAVES_GEN * WAVE, 0, a->s>>>(
+            a->d_tab, a->d_ps + t, a->d_sbr + t, a->d_hdr, a->n_hdr, st_in, a->d_state_out, (int)c.words, c.off_ps, X, S, T,
+            m...);
+    });
     return hipGetLastError() == hipSuccess ? HEAAC_OK : HEAAC_ERR_HIP;
 }
 

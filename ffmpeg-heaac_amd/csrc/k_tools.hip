@@ -647,6 +647,18 @@ void k_spectral_tools_streams(float *g_coeffs, const HeaacToolsFrame *__restrict
     }
 }
 
+// TNS as a pass of its own over n frames, one lane per filter of a channel (with a mask: the held frames skipped)
+static int launch_tns(int channels, float *d_coeffs, const HeaacToolsFrame *d_tools, unsigned long long n,
+                      const uint8_t *d_hold, hipStream_t s)
+{
+    const unsigned long long blocks = (n * channels * TNS_FILTERS + 255) / 256;
+    if (blocks > 0x7fffffffull) return HEAAC_ERR_ARG;
+    with_channels(channels, [&](auto ch) {
+        with_hold(d_hold, [&](auto... m) { k_tns<ch()><<<(unsigned)blocks, 256, 0, s>>>(d_coeffs, d_tools, n, m...); });
+    });
+    return HEAAC_OK;
+}
+
 extern "C" int heaac_launch_spectral_tools(int channels, float *d_coeffs, const HeaacToolsFrame *d_tools,
                                            const int *d_rng_in, int *d_rng_out,
                                            const HeaacPredictorState *d_pred_in, HeaacPredictorState *d_pred_out,
@@ -655,34 +667,21 @@ extern "C" int heaac_launch_spectral_tools(int channels, float *d_coeffs, const 
 {
     if (n == 0) return HEAAC_OK;
     if (channels != 1 && channels != 2) return HEAAC_ERR_ARG;
-    unsigned long long g = (n + TL_WAVES - 1) / TL_WAVES;
-    if (g > 256) g = 256;
     // Without coupling elements the second half is TNS alone: it runs as a pass of its own, one lane per channel of a
     // frame (k_tns), behind the first half.  With them it stays inside the frame's wave, between the two coupling points.
     const bool tns_pass = (stages & HEAAC_TOOLS_POST) && n_cce == 0;
     const int in_wave = tns_pass ? (stages & ~HEAAC_TOOLS_POST) : stages;
-    if (in_wave) {
-        if (channels == 2)
-            hipLaunchKernelGGL(k_spectral_tools<2>, dim3((unsigned)g), dim3(TL_WAVES * WAVE), 0, s, d_coeffs, d_tools,
-                               d_rng_in, d_rng_out, d_pred_in, d_pred_out, in_wave, d_cce, d_cce_coeffs, n_cce,
-                               (unsigned long long)n);
-        else
-            hipLaunchKernelGGL(k_spectral_tools<1>, dim3((unsigned)g), dim3(TL_WAVES * WAVE), 0, s, d_coeffs, d_tools,
-                               d_rng_in, d_rng_out, d_pred_in, d_pred_out, in_wave, d_cce, d_cce_coeffs, n_cce,
-                               (unsigned long long)n);
-    }
-    if (tns_pass) {
-        const unsigned long long units = (unsigned long long)n * channels * TNS_FILTERS, blocks = (units + 255) / 256;
-        if (blocks > 0x7fffffffull) return HEAAC_ERR_ARG;
-        if (channels == 2) hipLaunchKernelGGL(k_tns<2>, dim3((unsigned)blocks), dim3(256), 0, s, d_coeffs, d_tools, (unsigned long long)n);
-        else               hipLaunchKernelGGL(k_tns<1>, dim3((unsigned)blocks), dim3(256), 0, s, d_coeffs, d_tools, (unsigned long long)n);
-    }
+    if (in_wave)
+        with_channels(channels, [&](auto ch) {
+            k_spectral_tools<ch()><<<persistent_grid(n, TL_WAVES), TL_WAVES * WAVE, 0, s>>>(
+                d_coeffs, d_tools, d_rng_in, d_rng_out, d_pred_in, d_pred_out, in_wave, d_cce, d_cce_coeffs, n_cce, n);
+        });
+    if (tns_pass && launch_tns(channels, d_coeffs, d_tools, n, nullptr, s) != HEAAC_OK) return HEAAC_ERR_ARG;
     return hipGetLastError() == hipSuccess ? HEAAC_OK : HEAAC_ERR_HIP;
 }
 
-// S streams x T frames (the plain call comes here with T > 1 and some state given and routes its other cases to
-// heaac_launch_spectral_tools; with a hold mask every case comes here).
-// The chain kernel runs the PRE half one wave per stream; TNS follows as k_tns over the S * T frames.
+// S streams x T frames.  The chain kernel runs the PRE half one wave per stream; TNS follows as k_tns over the S * T
+// frames.  Two cases are the batch call's (whose kernels know no mask: with one, every case runs the chain kernel).
 extern "C" int heaac_launch_spectral_tools_streams(int channels, float *d_coeffs, const HeaacToolsFrame *d_tools,
                                                    const int *d_rng_in, int *d_rng_out,
                                                    const HeaacPredictorState *d_pred_in, HeaacPredictorState *d_pred_out,
@@ -691,32 +690,26 @@ extern "C" int heaac_launch_spectral_tools_streams(int channels, float *d_coeffs
 {
     if (n_streams == 0) return HEAAC_OK;
     if (channels != 1 && channels != 2) return HEAAC_ERR_ARG;
-    const unsigned long long S = n_streams, T = frames_per_stream, n = S * T;
-    const unsigned long long units = n * channels * TNS_FILTERS, blocks = (units + 255) / 256;
-    if (blocks > 0x7fffffffull) return HEAAC_ERR_ARG;
-#define LAUNCH(CH, PRED)                                                                                                 \
-    do {                                                                                                             \
-        unsigned long long g = (S + tss_waves<CH, PRED>() - 1) / tss_waves<CH, PRED>();                            \
-        if (g > 256) g = 256;                                                                                        \
-        if (d_hold)                                                                                                  \
-            hipLaunchKernelGGL((k_spectral_tools_streams<CH, PRED, const uint8_t *>), dim3((unsigned)g),            \
-                               dim3(tss_waves<CH, PRED>() * WAVE), 0, s, d_coeffs, d_tools, d_rng_in, d_rng_out,    \
-                               d_pred_in, d_pred_out, S, T, d_hold);                                                 \
-        else                                                                                                         \
-            hipLaunchKernelGGL((k_spectral_tools_streams<CH, PRED>), dim3((unsigned)g),                             \
-                               dim3(tss_waves<CH, PRED>() * WAVE), 0, s, d_coeffs, d_tools, d_rng_in, d_rng_out,    \
-                               d_pred_in, d_pred_out, S, T);                                                         \
-    } while (0)
-    const bool pred = d_pred_in != nullptr;
-    if (channels == 2) { if (pred) LAUNCH(2, true); else LAUNCH(2, false); }
-    else               { if (pred) LAUNCH(1, true); else LAUNCH(1, false); }
-#undef LAUNCH
-    if (d_hold) {
-        if (channels == 2) hipLaunchKernelGGL((k_tns<2, const uint8_t *>), dim3((unsigned)blocks), dim3(256), 0, s, d_coeffs, d_tools, n, d_hold);
-        else               hipLaunchKernelGGL((k_tns<1, const uint8_t *>), dim3((unsigned)blocks), dim3(256), 0, s, d_coeffs, d_tools, n, d_hold);
-    } else {
-        if (channels == 2) hipLaunchKernelGGL(k_tns<2>, dim3((unsigned)blocks), dim3(256), 0, s, d_coeffs, d_tools, n);
-        else               hipLaunchKernelGGL(k_tns<1>, dim3((unsigned)blocks), dim3(256), 0, s, d_coeffs, d_tools, n);
-    }
+    const unsigned long long S = n_streams, T = frames_per_stream;
+    // one frame per stream: the per-frame arrays and the state are exactly the batch call's
+    if (T == 1 && !d_hold)
+        return heaac_launch_spectral_tools(channels, d_coeffs, d_tools, d_rng_in, d_rng_out, d_pred_in, d_pred_out,
+                                           HEAAC_TOOLS_ALL, nullptr, nullptr, 0, S, s);
+    // no state: every frame stands alone, one batch call over the S * T frames
+    if (!d_rng_in && !d_pred_in && !d_hold)
+        return heaac_launch_spectral_tools(channels, d_coeffs, d_tools, nullptr, nullptr, nullptr, nullptr, HEAAC_TOOLS_ALL,
+                                           nullptr, nullptr, 0, S * T, s);
+    auto chain = [&](auto ch, auto pred) {
+        constexpr int waves = tss_waves<ch(), pred()>();
+        with_hold(d_hold, [&](auto... m) {
+            k_spectral_tools_streams<ch(), pred()><<<persistent_grid(S, waves), waves * WAVE, 0, s>>>(
+                d_coeffs, d_tools, d_rng_in, d_rng_out, d_pred_in, d_pred_out, S, T, m...);
+        });
+    };
+    with_channels(channels, [&](auto ch) {
+        if (d_pred_in) chain(ch, std::true_type{});
+        else chain(ch, std::false_type{});
+    });
+    if (launch_tns(channels, d_coeffs, d_tools, S * T, d_hold, s) != HEAAC_OK) return HEAAC_ERR_ARG;
     return hipGetLastError() == hipSuccess ? HEAAC_OK : HEAAC_ERR_HIP;
 }

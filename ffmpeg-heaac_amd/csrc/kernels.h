@@ -8,16 +8,12 @@
 #include "heaac_dsp.h"
 
 extern "C" {
+/* n_streams x frames_per_stream frames; one frame per stream without a mask runs the batch kernel */
 int heaac_launch_lc(const float *d_tab, const uint16_t *d_rev, int channels,
                     const float *d_coeffs, const HeaacIcs *d_ics,
                     const float *d_state_in, float *d_state_out,
-                    void *d_pcm, int pcm_format, size_t n, hipStream_t s);
-
-int heaac_launch_lc_streams(const float *d_tab, const uint16_t *d_rev, int channels,
-                            const float *d_coeffs, const HeaacIcs *d_ics,
-                            const float *d_state_in, float *d_state_out,
-                            void *d_pcm, int pcm_format, size_t n_streams, size_t frames_per_stream,
-                            const uint8_t *d_hold, hipStream_t s);
+                    void *d_pcm, int pcm_format, size_t n_streams, size_t frames_per_stream,
+                    const uint8_t *d_hold, hipStream_t s);
 
 int heaac_launch_imdct_half(const float *d_tab, const uint16_t *d_rev, int which,
                             float *d_out, const float *d_in, size_t n, hipStream_t s);
@@ -27,40 +23,36 @@ int heaac_launch_couple(int channels, float *d_pcm, const float *d_cce, const He
 
 int heaac_launch_interleave(int channels, const HeaacPlaneRef *planes, int len, int pcm_format, int16_t *d_out,
                             size_t n, hipStream_t s);
-}
 
-extern "C" {
-int heaac_launch_he(const float *d_tab, const uint16_t *d_rev, int cfg,
-                    const float *d_coeffs, const HeaacIcs *d_ics,
-                    const HeaacSbrFrame *d_sbr, const HeaacSbrHeader *d_hdr, unsigned n_hdr,
-                    const HeaacPsFrame *d_ps,
-                    const float *d_state_in, float *d_state_out,
-                    void *d_pcm, int pcm_format,
-                    float *d_ws_W, float *d_ws_X, unsigned *d_queue,
-                    unsigned char *d_xtop, const float *d_zero,
-                    size_t n, size_t pcm_frame0, int flags, hipStream_t s);
+/* One HE call over a chunk of whole streams: everything heaac_launch_he reads.  Frame (s, t) is record s * T + t of the
+ * per-frame arrays; the state is one record per stream.  T == 1 without a mask runs the batch kernels. */
+struct HeaacHeLaunch {
+    const float *d_tab;                 /* tables */
+    const uint16_t *d_rev;
+    int cfg, flags;                     /* HEAAC_CFG_*, HEAAC_HE_* */
+    const HeaacSbrHeader *d_hdr;
+    unsigned n_hdr;
+    const float *d_coeffs;              /* per frame */
+    const HeaacIcs *d_ics;
+    const HeaacSbrFrame *d_sbr;
+    const HeaacPsFrame *d_ps;           /* HE-AACv2 only */
+    const float *d_state_in;            /* per stream */
+    float *d_state_out;
+    void *d_pcm;
+    int pcm_format;
+    float *d_ws_W, *d_ws_X;             /* one workspace set: W / X hand-over, queue heads, X band counts, zero page */
+    unsigned *d_queue;
+    unsigned char *d_xtop;
+    const float *d_zero;
+    size_t n_streams, T;
+    const uint8_t *d_hold;
+    hipStream_t s;
+};
+int heaac_launch_he(const struct HeaacHeLaunch *a);
 
-int heaac_launch_he_streams(const float *d_tab, const uint16_t *d_rev, int cfg,
-                            const float *d_coeffs, const HeaacIcs *d_ics,
-                            const HeaacSbrFrame *d_sbr, const HeaacSbrHeader *d_hdr, unsigned n_hdr,
-                            const HeaacPsFrame *d_ps,
-                            const float *d_state_in, float *d_state_out,
-                            void *d_pcm, int pcm_format,
-                            float *d_ws_W, float *d_ws_X, unsigned *d_queue,
-                            unsigned char *d_xtop, const float *d_zero,
-                            size_t n_streams, size_t frames_per_stream, int flags, const uint8_t *d_hold,
-                            hipStream_t s);
-
-int heaac_launch_ps(const float *d_tab, const HeaacPsFrame *d_ps, const HeaacSbrFrame *d_sbr,
-                    const HeaacSbrHeader *d_hdr, unsigned n_hdr, const float *d_state_in, float *d_state_out,
-                    int state_words, int off_ps, float *d_ws_X, size_t n, size_t rstride,
-                    const uint8_t *d_hold, hipStream_t s);
-
-int heaac_launch_hfps(const float *d_tab, const HeaacSbrFrame *d_sbr, const HeaacSbrHeader *d_hdr,
-                      unsigned n_hdr, const HeaacPsFrame *d_ps, const float *d_ws_W,
-                      const float *d_state_in, float *d_state_out, int state_words,
-                      int off_sbr, int off_ps, float *d_ws_X, size_t n, unsigned *d_queue, unsigned char *d_xtop,
-                      size_t rstride, const uint8_t *d_hold, hipStream_t s);
+/* k_ps.hip: the HE-AACv2 launches of heaac_launch_he for position t of its streams (st_in: the state frame t reads) */
+int heaac_launch_hfps(const struct HeaacHeLaunch *a, size_t t, const float *st_in, const float *W, float *X);
+int heaac_launch_ps(const struct HeaacHeLaunch *a, size_t t, const float *st_in, float *X);
 
 int heaac_launch_qmf_analysis(const float *d_tab, const float *d_in, const float *d_xh_in,
                               float *d_xh_out, float *d_W, float scale, size_t n, hipStream_t s);
@@ -72,15 +64,14 @@ int heaac_launch_qmf_synthesis(const float *d_tab, const float *d_X, const float
 int heaac_launch_qmf_synthesis_ds(const float *d_tab, const float *d_X, const float *d_v_in,
                                   float *d_v_out, float *d_out, float scale, float bias,
                                   size_t n, hipStream_t s);
-}
 
-extern "C" {
 int heaac_launch_spectral_tools(int channels, float *d_coeffs, const HeaacToolsFrame *d_tools,
                                 const int *d_rng_in, int *d_rng_out,
                                 const HeaacPredictorState *d_pred_in, HeaacPredictorState *d_pred_out,
                                 int stages, const HeaacCceFrame *d_cce, const float *d_cce_coeffs, int n_cce,
                                 size_t n, hipStream_t s);
 
+/* one frame per stream, or no state at all, is one call of the batch launcher -- never with a mask */
 int heaac_launch_spectral_tools_streams(int channels, float *d_coeffs, const HeaacToolsFrame *d_tools,
                                         const int *d_rng_in, int *d_rng_out,
                                         const HeaacPredictorState *d_pred_in, HeaacPredictorState *d_pred_out,

@@ -140,6 +140,7 @@ EXPORTED = [
     "heaac_sbr_table_create", "heaac_sbr_table_destroy", "heaac_sbr_table_count", "heaac_sbr_table_data",
     "heaac_sbr_stream_init", "heaac_sbr_stream_bytes", "heaac_sbr_parse_payload", "heaac_sbr_no_payload",
     "heaac_heaac_parse_frame", "heaac_heaac_parse_batch", "heaac_sbr_tables_fingerprint",
+    "heaac_sbr_parse_device", "heaac_heaac_parse_device", "heaac_debug_sbr_parse_core",
 ]
 
 
@@ -446,6 +447,88 @@ class Device:
                                             C.c_size_t(n), cc, _ptr(coeffs), _ptr(ics), _ptr(tools), _ptr(info),
                                             _ptr(status), _stream()), "heaac_aac_parse_device")
         return dict(coeffs=coeffs, ics=ics, tools=tools, info=info, status=status)
+
+    # -- the SBR / PS payloads of the same units -> the records of he_decode, on the device --
+    def _sbr_parse_args(self, cfg, sst_in, sst_out, n, hdr, sbr, ps, status, dv):
+        import torch
+        L = lib()
+        L.heaac_sbr_stream_bytes.restype = C.c_size_t
+        sb = int(L.heaac_sbr_stream_bytes())
+        assert sst_in.dtype == torch.uint8 and sst_in.numel() == n * sb, "sst_in"
+        if sst_out is None:
+            sst_out = torch.empty(n * sb, dtype=torch.uint8, device=dv)
+        else:
+            assert sst_out.dtype == torch.uint8 and sst_out.numel() == n * sb, "sst_out"
+        assert hdr.dtype == torch.uint8 and hdr.numel() >= SBR_HDR_DT.itemsize and hdr.numel() % SBR_HDR_DT.itemsize == 0, "hdr"
+        if sbr is None:
+            sbr = torch.empty(n * SBR_FRAME_DT.itemsize, dtype=torch.uint8, device=dv)
+        else:
+            assert sbr.dtype == torch.uint8 and sbr.numel() == n * SBR_FRAME_DT.itemsize, "sbr"
+        if ps is None:
+            if cfg.ps != 0 and cfg.chan_config == 1:
+                ps = torch.empty(n * PS_FRAME_DT.itemsize, dtype=torch.uint8, device=dv)
+        else:
+            assert ps.dtype == torch.uint8 and ps.numel() == n * PS_FRAME_DT.itemsize, "ps"
+        if status is None:
+            status = torch.empty(n, dtype=torch.int32, device=dv)
+        else:
+            assert status.dtype == torch.int32 and status.numel() == n, "status"
+        return sst_out, sbr, ps, status
+
+    def sbr_parse_device(self, cfg, sst_in, au_bytes, au_offset, info, hdr, aac_status=None, sst_out=None, sbr=None,
+                         ps=None, status=None):
+        """heaac_sbr_parse_device behind aac_parse: sst_in / sst_out: uint8 tensors of n HeaacSbrStream records (the
+        two must not overlap; sst_out is allocated when None), au_offset: the int32 device tensor of n + 1 offsets
+        aac_parse used, info / aac_status: its `info` and `status`, hdr: uint8 tensor of SBR_HDR_DT records.  ps is
+        allocated when cfg.ps != 0 on a mono configuration.  Returns dict(sst=sst_out, sbr, ps, status)."""
+        import torch
+        assert isinstance(au_offset, torch.Tensor) and au_offset.dtype == torch.int32 and au_offset.numel() >= 1, "au_offset"
+        n = au_offset.numel() - 1
+        assert au_bytes.dtype == torch.uint8, "au_bytes"
+        assert info.dtype == torch.uint8 and info.numel() == n * AAC_INFO_DT.itemsize, "info"
+        assert aac_status is None or (aac_status.dtype == torch.int32 and aac_status.numel() == n), "aac_status"
+        sst_out, sbr, ps, status = self._sbr_parse_args(cfg, sst_in, sst_out, n, hdr, sbr, ps, status, au_bytes.device)
+        _check(lib().heaac_sbr_parse_device(self._h, C.byref(cfg), _ptr(sst_in), _ptr(sst_out), _ptr(au_bytes), _ptr(au_offset),
+                                            _ptr(info), _ptr(aac_status), C.c_size_t(n), _ptr(hdr),
+                                            C.c_size_t(hdr.numel() // SBR_HDR_DT.itemsize), _ptr(sbr), _ptr(ps), _ptr(status),
+                                            _stream()), "heaac_sbr_parse_device")
+        return dict(sst=sst_out, sbr=sbr, ps=ps, status=status)
+
+    def heaac_parse_device(self, cfg, streams, sst_in, au_bytes, au_offset, hdr, coeff_channels=2, coeffs=None, ics=None,
+                           tools=None, info=None, sst_out=None, sbr=None, ps=None, status=None):
+        """heaac_heaac_parse_device: aac_parse and sbr_parse_device as one call (one status per unit, PARSE_OK only
+        where both halves took it).  au_offset: an int32 device tensor of n + 1 offsets the caller vouches for.
+        Returns the dict of aac_parse plus sst, sbr, ps."""
+        import torch
+        assert isinstance(au_offset, torch.Tensor) and au_offset.dtype == torch.int32 and au_offset.numel() >= 1, "au_offset"
+        n = au_offset.numel() - 1
+        cc = int(coeff_channels)
+        assert cc in (1, 2), "coeff_channels"
+        assert au_bytes.dtype == torch.uint8, "au_bytes"
+        assert streams.dtype == torch.uint8 and streams.numel() == n * AAC_STREAM_DT.itemsize, "streams"
+        dv = au_bytes.device
+        if coeffs is None:
+            coeffs = torch.empty((n, cc, 1024), dtype=torch.float32, device=dv)
+        else:
+            assert coeffs.dtype == torch.float32 and coeffs.numel() == n * cc * 1024, "coeffs"
+        if ics is None:
+            ics = torch.empty(n * cc * ICS_DT.itemsize, dtype=torch.uint8, device=dv)
+        else:
+            assert ics.dtype == torch.uint8 and ics.numel() == n * cc * ICS_DT.itemsize, "ics"
+        if tools is None:
+            tools = torch.empty(n * TOOLS_FRAME_DT.itemsize, dtype=torch.uint8, device=dv)
+        else:
+            assert tools.dtype == torch.uint8 and tools.numel() == n * TOOLS_FRAME_DT.itemsize, "tools"
+        if info is None:
+            info = torch.empty(n * AAC_INFO_DT.itemsize, dtype=torch.uint8, device=dv)
+        else:
+            assert info.dtype == torch.uint8 and info.numel() == n * AAC_INFO_DT.itemsize, "info"
+        sst_out, sbr, ps, status = self._sbr_parse_args(cfg, sst_in, sst_out, n, hdr, sbr, ps, status, dv)
+        _check(lib().heaac_heaac_parse_device(self._h, C.byref(cfg), _ptr(streams), _ptr(sst_in), _ptr(sst_out), _ptr(au_bytes),
+                                              _ptr(au_offset), C.c_size_t(n), cc, _ptr(coeffs), _ptr(ics), _ptr(tools),
+                                              _ptr(info), _ptr(hdr), C.c_size_t(hdr.numel() // SBR_HDR_DT.itemsize), _ptr(sbr),
+                                              _ptr(ps), _ptr(status), _stream()), "heaac_heaac_parse_device")
+        return dict(coeffs=coeffs, ics=ics, tools=tools, info=info, status=status, sst=sst_out, sbr=sbr, ps=ps)
 
     # -- spectral tools before the IMDCT (M/S, intensity stereo, TNS), in place --
     def spectral_tools(self, channels, coeffs, tools, rng=None, pred=None):
@@ -988,6 +1071,36 @@ def aac_parse_core(cfg, streams, aus, coeff_channels=2, out=None):
                                           out["tools"].ctypes.data_as(C.c_void_p), out["info"].ctypes.data_as(C.c_void_p),
                                           out["status"].ctypes.data_as(C.c_void_p), out["why"].ctypes.data_as(C.c_void_p))
     _check(rc, "heaac_debug_aac_parse_core")
+    return out
+
+
+SBR_WHY_HEADER, SBR_WHY_HDR_INDEX, SBR_WHY_MISPLACED, SBR_WHY_REFUSED, SBR_WHY_AAC = 1, 2, 4, 8, 16
+
+
+def sbr_parse_core(cfg, sst_in, aus, info, hdr, aac_status=None, with_ps=True, out=None):
+    """heaac_debug_sbr_parse_core (include/heaac_debug.h): the walk of heaac_sbr_parse_device on the host.  sst_in:
+    sbr_streams(n) rows (left alone), aus: the access units, info: AAC_INFO_DT [n] as the AAC parser left it, hdr:
+    SBR_HDR_DT records, aac_status: int32 [n] or None.  Returns dict(sst [n][bytes], sbr [n], ps [n] or None, status
+    [n], why [n]: 0 or the SBR_WHY_* reason).  `out`: a dict of pre-filled sst / sbr / ps arrays to write into."""
+    n = len(aus)
+    buf, off = pack_units(aus)
+    off = off.astype(np.uint32)
+    keep = np.concatenate([buf, np.zeros(1, np.uint8)])
+    sst_in = np.ascontiguousarray(sst_in)
+    info = np.ascontiguousarray(info, dtype=AAC_INFO_DT)
+    hdr = np.ascontiguousarray(hdr, dtype=SBR_HDR_DT).reshape(-1)
+    assert sst_in.dtype == np.uint8 and sst_in.shape[0] == n and info.shape == (n,)
+    if out is None:
+        out = dict(sst=np.zeros_like(sst_in), sbr=np.zeros(n, SBR_FRAME_DT), ps=np.zeros(n, PS_FRAME_DT) if with_ps else None)
+    out["status"] = np.zeros(n, np.int32)
+    out["why"] = np.zeros(n, np.int32)
+    if aac_status is not None:
+        aac_status = np.ascontiguousarray(aac_status, dtype=np.int32)
+    p = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None
+    rc = lib().heaac_debug_sbr_parse_core(C.byref(cfg), p(sst_in), p(out["sst"]), p(keep), p(off), p(info), p(aac_status),
+                                          C.c_size_t(n), p(hdr), C.c_size_t(hdr.shape[0]), p(out["sbr"]), p(out.get("ps")),
+                                          p(out["status"]), p(out["why"]))
+    _check(rc, "heaac_debug_sbr_parse_core")
     return out
 
 

@@ -11,6 +11,7 @@
 #include "heaac_debug.h"
 #include "heaac_parse.h"
 #include "parse_core.h"
+#include "sbr_core.h"
 #include "tables.h"
 #include "kernels.h"
 #include "host_common.h"
@@ -22,6 +23,7 @@ struct HeaacDevice {
     float *d_tab;
     uint16_t *d_rev;
     HeaacParseTables *d_ptab;   // parse_core.h: what heaac_aac_parse_device reads (code trees, dequantisation and band tables)
+    HeaacSbrParseTables *d_stab;    // sbr_core.h: the SBR / PS code books heaac_sbr_parse_device reads
     void *d_work;
     unsigned *d_queue;      // frame-queue heads of the kernels that draw frames dynamically (one set per lane)
     // X hand-over side data: a page of zeros, then per workspace set one byte per frame and channel = the number of QMF
@@ -172,10 +174,14 @@ extern "C" int heaac_device_create(HeaacDevice **out, size_t max_frames)
         hipMalloc((void **)&d->d_queue, 64 * HE_MAX_LANES) != hipSuccess ||
         hipMalloc((void **)&d->d_aux, HE_ZERO_BYTES + 2 * (size_t)(d->sets > 0 ? d->sets : 1) * (d->chunk ? d->chunk : 1)) != hipSuccess ||
         hipMalloc((void **)&d->d_ptab, sizeof(HeaacParseTables)) != hipSuccess ||
+        hipMalloc((void **)&d->d_stab, sizeof(HeaacSbrParseTables)) != hipSuccess ||
         (d->work_bytes && hipMalloc(&d->d_work, d->work_bytes) != hipSuccess))
         rc = HEAAC_ERR_NOMEM;
     const HeaacParseTables *pt = heaac_parse_tables();
     if (rc == HEAAC_OK && (!pt || hipMemcpy(d->d_ptab, pt, sizeof(*pt), hipMemcpyHostToDevice) != hipSuccess))
+        rc = HEAAC_ERR_HIP;
+    const HeaacSbrParseTables *spt = heaac_sbr_parse_tables();
+    if (rc == HEAAC_OK && (!spt || hipMemcpy(d->d_stab, spt, sizeof(*spt), hipMemcpyHostToDevice) != hipSuccess))
         rc = HEAAC_ERR_HIP;
     if (rc == HEAAC_OK &&
         (hipMemset(d->d_aux, 0, HE_ZERO_BYTES) != hipSuccess ||
@@ -205,6 +211,7 @@ extern "C" void heaac_device_destroy(HeaacDevice *d)
     if (d->d_tab) (void)hipFree(d->d_tab);
     if (d->d_rev) (void)hipFree(d->d_rev);
     if (d->d_ptab) (void)hipFree(d->d_ptab);
+    if (d->d_stab) (void)hipFree(d->d_stab);
     if (d->d_work) (void)hipFree(d->d_work);
     if (d->d_queue) (void)hipFree(d->d_queue);
     if (d->d_aux) (void)hipFree(d->d_aux);
@@ -290,6 +297,49 @@ extern "C" int heaac_aac_parse_device(HeaacDevice *dev, const HeaacAacConfig *cf
         return HEAAC_ERR_ARG;
     return heaac_launch_aac_parse(dev->d_ptab, cfg, d_st, d_au, d_au_offset, n, coeff_channels, d_coeffs, d_ics, d_tools,
                                   d_info, d_status, (hipStream_t)stream);
+}
+
+#define PARSE_GRID_MAX (0x7fffffffull * 64)     // units: one lane each, 64 per block (k_parse.hip)
+
+extern "C" int heaac_sbr_parse_device(HeaacDevice *dev, const HeaacAacConfig *cfg, const HeaacSbrStream *d_sst_in,
+                                      HeaacSbrStream *d_sst_out, const uint8_t *d_au, const uint32_t *d_au_offset,
+                                      const HeaacAacFrameInfo *d_info, const int32_t *d_aac_status, size_t n,
+                                      const HeaacSbrHeader *d_hdr, size_t n_hdr, HeaacSbrFrame *d_sbr, HeaacPsFrame *d_ps,
+                                      int32_t *d_status, void *stream)
+{
+    if (!dev || !cfg)
+        return HEAAC_ERR_ARG;
+    if (n == 0)
+        return HEAAC_OK;
+    if (n > PARSE_GRID_MAX || ((uintptr_t)d_aac_status & 3) ||
+        !heaac_sbr_parse_args_ok(cfg, d_sst_in, d_sst_out, d_au, d_au_offset, d_info, n, d_hdr, n_hdr, d_sbr, d_ps, d_status))
+        return HEAAC_ERR_ARG;
+    return heaac_launch_sbr_parse(dev->d_stab, cfg, d_sst_in, d_sst_out, d_au, d_au_offset, d_info, d_aac_status, n, d_hdr, n_hdr,
+                                  d_sbr, d_ps, d_status, (hipStream_t)stream);
+}
+
+extern "C" int heaac_heaac_parse_device(HeaacDevice *dev, const HeaacAacConfig *cfg, HeaacAacStream *d_st,
+                                        const HeaacSbrStream *d_sst_in, HeaacSbrStream *d_sst_out, const uint8_t *d_au,
+                                        const uint32_t *d_au_offset, size_t n, int coeff_channels, float *d_coeffs,
+                                        HeaacIcs *d_ics, HeaacToolsFrame *d_tools, HeaacAacFrameInfo *d_info,
+                                        const HeaacSbrHeader *d_hdr, size_t n_hdr, HeaacSbrFrame *d_sbr, HeaacPsFrame *d_ps,
+                                        int32_t *d_status, void *stream)
+{
+    if (!dev || !heaac_parse_args_ok(cfg, coeff_channels))
+        return HEAAC_ERR_ARG;
+    if (n == 0)
+        return HEAAC_OK;
+    // everything either half refuses is refused before the first launch
+    if (n > PARSE_GRID_MAX ||
+        !heaac_sbr_parse_args_ok(cfg, d_sst_in, d_sst_out, d_au, d_au_offset, d_info, n, d_hdr, n_hdr, d_sbr, d_ps, d_status))
+        return HEAAC_ERR_ARG;
+    int rc = heaac_aac_parse_device(dev, cfg, d_st, d_au, d_au_offset, n, coeff_channels, d_coeffs, d_ics, d_tools, d_info, d_status,
+                                    stream);
+    if (rc != HEAAC_OK)
+        return rc;
+    // the SBR half reads each unit's AAC status from d_status and writes the unit's one status there
+    return heaac_sbr_parse_device(dev, cfg, d_sst_in, d_sst_out, d_au, d_au_offset, d_info, d_status, n, d_hdr, n_hdr, d_sbr, d_ps,
+                                  d_status, stream);
 }
 
 extern "C" int heaac_spectral_tools_batch(HeaacDevice *dev, int channels, float *d_coeffs,

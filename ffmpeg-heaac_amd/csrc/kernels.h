@@ -90,4 +90,16 @@ int heaac_launch_aac_parse(const struct HeaacParseTables *d_tab, const struct He
                            const uint8_t *d_au, const uint32_t *d_au_offset, size_t n, int coeff_channels,
                            float *d_coeffs, HeaacIcs *d_ics, HeaacToolsFrame *d_tools, struct HeaacAacFrameInfo *d_info,
                            int32_t *d_status, hipStream_t s);
+
+/* k_parse.hip: heaac_sbr_parse_device; d_tab = the device copy of heaac_sbr_parse_tables() (sbr_core.h) */
+struct HeaacSbrParseTables;
+struct HeaacSbrStream;
+int heaac_sbr_parse_args_ok(const struct HeaacAacConfig *cfg, const void *sst_in, const void *sst_out, const void *au,
+                            const void *au_offset, const void *info, size_t n, const void *hdr, size_t n_hdr, const void *sbr,
+                            const void *ps, const void *status);
+int heaac_launch_sbr_parse(const struct HeaacSbrParseTables *d_tab, const struct HeaacAacConfig *cfg,
+                           const struct HeaacSbrStream *d_sst_in, struct HeaacSbrStream *d_sst_out, const uint8_t *d_au,
+                           const uint32_t *d_au_offset, const struct HeaacAacFrameInfo *d_info, const int32_t *d_aac_status,
+                           size_t n, const HeaacSbrHeader *d_hdr, size_t n_hdr, HeaacSbrFrame *d_sbr, HeaacPsFrame *d_ps,
+                           int32_t *d_status, hipStream_t s);
 }

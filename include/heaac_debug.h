@@ -39,6 +39,15 @@ int heaac_debug_aac_parse_core(const HeaacAacConfig *cfg, HeaacAacStream *st, co
                                HeaacIcs *ics, HeaacToolsFrame *tools, HeaacAacFrameInfo *info, int32_t *status,
                                int32_t *why);
 
+/* The payload walk of heaac_sbr_parse_device (csrc/sbr_core.h) instantiated for the host: the same arguments with host
+ * pointers, a plain loop over the n units, no device.  `why` (may be NULL) receives per unit 0 for HEAAC_PARSE_OK, or
+ * why the unit was deferred: 1 a header that resets or touches the derived record, 2 the stream's header index is not
+ * below n_hdr, 4 a misplaced payload, 8 the host parser would not return HEAAC_PARSE_OK, 16 the AAC status is not OK. */
+int heaac_debug_sbr_parse_core(const HeaacAacConfig *cfg, const HeaacSbrStream *sst_in, HeaacSbrStream *sst_out,
+                               const uint8_t *au, const uint32_t *au_offset, const HeaacAacFrameInfo *info,
+                               const int32_t *aac_status, size_t n, const HeaacSbrHeader *hdr, size_t n_hdr,
+                               HeaacSbrFrame *sbr, HeaacPsFrame *ps, int32_t *status, int32_t *why);
+
 #ifdef __cplusplus
 }
 #endif

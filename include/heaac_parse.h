@@ -491,6 +491,59 @@ int heaac_heaac_parse_batch(const HeaacAacConfig *cfg, HeaacAacStream *st, Heaac
                             HeaacSbrFrame *sbr, HeaacPsFrame *ps,
                             HeaacAacFrameInfo *info, int *status, int threads);
 
+/* ---- the same two records from compressed units already in device memory (csrc/k_parse.hip, csrc/sbr_core.h) ----
+ * The SBR / PS half of heaac_heaac_parse_frame_ex for n independent streams, one access unit each, behind
+ * heaac_aac_parse_device: unit i is d_au[d_au_offset[i] .. d_au_offset[i + 1]), d_info[i] is what the AAC walk left for
+ * it (where the payload lies, its crc flag, sbr_misplaced, the channels) and d_aac_status[i] its status there (NULL: every
+ * unit is vouched for as HEAAC_PARSE_OK).  d_hdr[n_hdr] is the array of derived headers the HE decode calls take: the
+ * walk reads the band counts of the stream's current header (d_sst[i].hdr) from it and derives nothing.  Parametric
+ * Stereo is read when cfg->ps != 0, d_info[i].channels == 1 and d_ps is given; d_ps, when given, receives a record for
+ * every unit (as the host call writes one whenever it is handed the pointer).  Every pointer but cfg is device memory,
+ * 4-byte aligned (d_au: any).
+ *
+ * State.  A lane cannot hold the copies the host parser rolls a HeaacSbrStream (3 336 bytes) back from, so the call
+ * takes the states of all units in d_sst_in and leaves them in d_sst_out; the two arrays must not overlap, and a caller
+ * ping-pongs two of them.  Per unit, d_status[i] is
+ *   HEAAC_PARSE_OK        d_sst_out[i] and the whole of d_sbr[i] (680 bytes) and d_ps[i] (532 bytes) are byte for byte
+ *                         what heaac_heaac_parse_frame_ex leaves from d_sst_in[i] where it returns HEAAC_PARSE_OK or
+ *                         HEAAC_PARSE_NO_SBR.  A unit without a payload, and every unit where cfg->sbr == 0, gets the
+ *                         record of heaac_sbr_no_payload and is OK as well (HEAAC_PARSE_NO_SBR and HEAAC_PARSE_DEFERRED
+ *                         are both 1: whether a unit had a payload is read from d_info[i].sbr_payload_bit)
+ *   HEAAC_PARSE_DEFERRED  not parsed here: d_sst_out[i] equals d_sst_in[i], d_sbr[i] and d_ps[i] are unspecified; parse
+ *                         the unit's payload on the host from that state (heaac_sbr_parse_payload, which registers
+ *                         headers in the host's table; upload new entries before the decode) and upload its records.
+ * Taken are: a payload without a header; a payload whose header changes nothing (read_header's reset == 0 and
+ * tables_touched == 0); a unit without a payload.  Deferred are: a header that resets the band tables or touches the
+ * derived record, the first header of a stream included (the device never registers a header); d_sst_in[i].hdr >=
+ * n_hdr; a payload flagged sbr_misplaced; every unit the host call would return anything but HEAAC_PARSE_OK for from
+ * the same state -- a grid error, a scalefactor outside 0 .. 255, a read past the unit, a PS error (ps_status != 0), a
+ * bad code (the device never decides a refusal); every unit whose AAC status is not OK.  Nothing else.
+ * Returns HEAAC_OK (0; n = 0 included), or HEAAC_ERR_ARG before anything is launched for a NULL pointer with n > 0
+ * (d_aac_status may be NULL; d_ps may be unless cfg->ps != 0 and cfg->chan_config == 1), state arrays that overlap,
+ * n_hdr == 0, a misaligned pointer, or n beyond the grid (2^31 - 1 blocks of 64).  As the other batch calls: no
+ * allocation, no synchronisation, capturable into a graph (two kernels, in line: one copies the states and zeroes the
+ * records, one walks), no use of the context's workspace. */
+int heaac_sbr_parse_device(HeaacDevice *dev, const HeaacAacConfig *cfg /* host */,
+                           const HeaacSbrStream *d_sst_in, HeaacSbrStream *d_sst_out,   /* [n], must not alias */
+                           const uint8_t *d_au, const uint32_t *d_au_offset /* [n + 1] */,
+                           const HeaacAacFrameInfo *d_info /* [n], as heaac_aac_parse_device wrote it */,
+                           const int32_t *d_aac_status /* [n] or NULL = all OK */,
+                           size_t n, const HeaacSbrHeader *d_hdr, size_t n_hdr,
+                           HeaacSbrFrame *d_sbr /* [n] */, HeaacPsFrame *d_ps /* [n], NULL unless cfg->ps != 0 */,
+                           int32_t *d_status /* [n] */, void *stream);
+
+/* heaac_aac_parse_device and then heaac_sbr_parse_device on its d_info and statuses, in line on one stream (four
+ * kernels; one capturable call): the arguments of the two, d_status[i] = HEAAC_PARSE_OK only where both halves took the
+ * unit.  What either call refuses is refused before anything is launched.  For a deferred unit d_sst_out[i] equals
+ * d_sst_in[i]; d_st[i] is as it was where the AAC half deferred the unit and has moved on where only the SBR half
+ * did -- a caller that must tell the two apart keeps d_st from before the call, or makes the two calls itself. */
+int heaac_heaac_parse_device(HeaacDevice *dev, const HeaacAacConfig *cfg /* host */, HeaacAacStream *d_st /* [n] in / out */,
+                             const HeaacSbrStream *d_sst_in, HeaacSbrStream *d_sst_out,
+                             const uint8_t *d_au, const uint32_t *d_au_offset, size_t n, int coeff_channels,
+                             float *d_coeffs, HeaacIcs *d_ics, HeaacToolsFrame *d_tools, HeaacAacFrameInfo *d_info,
+                             const HeaacSbrHeader *d_hdr, size_t n_hdr, HeaacSbrFrame *d_sbr, HeaacPsFrame *d_ps,
+                             int32_t *d_status, void *stream);
+
 /* FNV-1a of the generated SBR / PS Huffman tables (sbr_iso_tables.h). */
 uint64_t heaac_sbr_tables_fingerprint(void);
 

@@ -11,7 +11,14 @@
       and heaac_aac_parse_batch on 16 threads plus the H2D of its records from pinned memory (host clock around work
       that ends in a synchronise).  One JSON line per form: ms per call over the rounds (median, min, max), bytes over
       the link per unit, and for the device form a nominal store rate: the record sizes (an upper bound of what the kernels write; the
-      counter is rocprofv3 --pmc WRITE_SIZE, in a run of its own) over the call time."""
+      counter is rocprofv3 --pmc WRITE_SIZE, in a run of its own) over the call time.
+
+  python tools/parse_rate.py --device --he [--units 32768] [--distinct 256] [--rounds 12] [--out FILE.jsonl]
+      heaac_heaac_parse_device (the AAC walk and the SBR / PS payload walk, four kernels) against
+      heaac_heaac_parse_batch on 16 host threads plus the upload of all its records, the HeaacSbrFrame / HeaacPsFrame
+      among them, A/B alternating in one process.  Two corpora from tests/sbr_bitwriter.py, one after the other: stereo
+      (coupled and not) and mono + PS HE units, each stream in steady state -- its first header parsed on the host
+      ahead of the timing, the timed unit without a header change -- tiled to --units.  Two JSON lines per corpus."""
 import importlib, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -129,8 +136,121 @@ def device_mode(argv):
                 f.write(json.dumps(l) + "\n")
 
 
+def he_mode(argv):
+    import argparse, ctypes as C, json
+    import torch
+    import sbr_device_common as SD
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--device", action="store_true")
+    ap.add_argument("--he", action="store_true")
+    ap.add_argument("--units", type=int, default=32768)
+    ap.add_argument("--distinct", type=int, default=256)
+    ap.add_argument("--rounds", type=int, default=12)
+    ap.add_argument("--threads", type=int, default=16)
+    ap.add_argument("--out", default="")
+    a = ap.parse_args(argv)
+    assert torch.cuda.is_available(), "parse_rate --device needs a GPU"
+    dev = pkg.Device()
+    L = pkg.lib()
+    n = a.units
+    vp = lambda t: C.c_void_p(t.data_ptr())
+    sp = lambda v: dict(median=round(float(np.median(v)), 3), min=round(float(min(v)), 3), max=round(float(max(v)), 3))
+    lines = []
+    for cpe in (True, False):
+        rng = np.random.default_rng(2025 + cpe)
+        cfg = SD.he_cfg(pkg, cpe)
+        with_ps = not cpe
+        d = a.distinct
+        writers = SD.make_writers(pkg, d, cpe)
+        tab = pkg.SbrHeaderTable(256)
+        st0, sst0 = np.zeros(d, pkg.AAC_STREAM_DT), pkg.sbr_streams(d)
+        first = pkg.heaac_parse_batch(cfg, st0, sst0, tab, SD.he_units(rng, writers, cpe), with_ps=with_ps)
+        assert first["failed"] == 0
+        units = SD.he_units(rng, writers, cpe)                 # the timed units: no header, from the states st0 / sst0
+        tile = np.arange(n) % d
+        aus = [units[i] for i in tile]
+        mean_size = float(np.mean([len(u) for u in aus]))
+        hdr = tab.headers()
+        d_hdr = pkg.to_device(hdr)
+        buf, off = pkg.pack_units(aus)
+        h_buf = torch.from_numpy(buf).pin_memory()
+        h_off = torch.from_numpy(off.astype(np.int32)).pin_memory()
+        d_buf = torch.empty_like(h_buf, device="cuda"); d_off = torch.empty_like(h_off, device="cuda")
+        d_st0 = pkg.to_device(st0[tile]); d_st = torch.empty_like(d_st0)
+        d_sst_in = pkg.to_device(sst0[tile]); d_sst_out = torch.empty_like(d_sst_in)
+        sizes_of = dict(coeffs=(n, 2, 1024), ics=n * 8, tools=n * pkg.TOOLS_FRAME_DT.itemsize, info=n * pkg.AAC_INFO_DT.itemsize,
+                        status=n, sbr=n * pkg.SBR_FRAME_DT.itemsize, ps=n * pkg.PS_FRAME_DT.itemsize)
+        dt_of = dict(coeffs=torch.float32, status=torch.int32)
+        names = [k for k in sizes_of if with_ps or k != "ps"]
+        d_out = {k: torch.empty(sizes_of[k], dtype=dt_of.get(k, torch.uint8), device="cuda") for k in names}
+        h_out = {k: torch.empty(sizes_of[k], dtype=dt_of.get(k, torch.uint8)).pin_memory() for k in names}
+        u_out = {k: torch.empty_like(v, device="cuda") for k, v in h_out.items()}
+        keep = [C.create_string_buffer(u, len(u)) for u in units]
+        ptrs = (C.c_char_p * n)(*[C.cast(keep[i], C.c_char_p) for i in tile])
+        sizes = (C.c_int * n)(*[len(u) for u in aus])
+        h_st0, h_sst0 = st0[tile].copy(), sst0[tile].copy()
+        h_st, h_sst = h_st0.copy(), h_sst0.copy()
+
+        def host_round():
+            h_st[...] = h_st0; h_sst[...] = h_sst0            # the same units from the same states every round
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            failed = L.heaac_heaac_parse_batch(C.byref(cfg), h_st.ctypes.data_as(C.c_void_p), h_sst.ctypes.data_as(C.c_void_p),
+                                               C.c_void_p(tab._h), ptrs, sizes, C.c_size_t(n), vp(h_out["coeffs"]), vp(h_out["ics"]),
+                                               vp(h_out["tools"]), vp(h_out["sbr"]), vp(h_out["ps"]) if with_ps else None,
+                                               vp(h_out["info"]), vp(h_out["status"]), C.c_int(a.threads))
+            t1 = time.perf_counter()
+            for k in h_out:
+                u_out[k].copy_(h_out[k], non_blocking=True)
+            torch.cuda.synchronize()
+            t2 = time.perf_counter()
+            assert failed == 0
+            return (t1 - t0) * 1e3, (t2 - t1) * 1e3
+
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+
+        def device_round():
+            d_st.copy_(d_st0)
+            torch.cuda.synchronize()
+            ev[0].record()
+            d_buf.copy_(h_buf, non_blocking=True); d_off.copy_(h_off, non_blocking=True)
+            ev[1].record()
+            dev.heaac_parse_device(cfg, d_st, d_sst_in, d_buf, d_off, d_hdr, coeff_channels=2, sst_out=d_sst_out,
+                                   **{k: d_out[k] for k in names})
+            ev[2].record()
+            torch.cuda.synchronize()
+            return ev[1].elapsed_time(ev[2]), ev[0].elapsed_time(ev[1])
+
+        for _ in range(3):
+            device_round(); host_round()
+        deferred = int(d_out["status"].cpu().numpy().astype(bool).sum())
+        same = deferred == 0 and all(np.array_equal(d_out[k].cpu().numpy().reshape(-1).view(np.uint8),
+                                                    u_out[k].cpu().numpy().reshape(-1).view(np.uint8)) for k in names) and \
+            np.array_equal(d_sst_out.cpu().numpy(), h_sst.reshape(-1))
+        dev_ms, dev_h2d, host_ms, host_h2d = [], [], [], []
+        for _ in range(a.rounds):
+            x, y = device_round(); dev_ms.append(x); dev_h2d.append(y)
+            x, y = host_round(); host_ms.append(x); host_h2d.append(y)
+        rec = sum(int(np.prod(sizes_of[k])) * (4 if k in dt_of else 1) for k in names) // n
+        corpus = "stereo" if cpe else "mono_ps"
+        lines += [
+            dict(form="heaac_heaac_parse_device", corpus=corpus, units=n, distinct=d, mean_unit_bytes=round(mean_size, 1),
+                 rounds=a.rounds, call_ms=sp(dev_ms), h2d_bytes_ms=sp(dev_h2d), link_bytes_per_unit=round(mean_size + 4, 1),
+                 units_per_s=round(n / (np.median(dev_ms) * 1e-3)), deferred=deferred, records_equal_host=bool(same)),
+            dict(form="heaac_heaac_parse_batch + H2D", corpus=corpus, units=n, threads=a.threads, rounds=a.rounds,
+                 parse_ms=sp(host_ms), h2d_records_ms=sp(host_h2d), total_ms=sp([x + y for x, y in zip(host_ms, host_h2d)]),
+                 link_bytes_per_unit=rec, units_per_s=round(n / ((np.median(host_ms) + np.median(host_h2d)) * 1e-3))),
+        ]
+    for l in lines:
+        print(json.dumps(l))
+    if a.out:
+        with open(a.out, "a") as f:
+            for l in lines:
+                f.write(json.dumps(l) + "\n")
+
+
 if "--device" in sys.argv:
-    device_mode(sys.argv[1:])
+    (he_mode if "--he" in sys.argv else device_mode)(sys.argv[1:])
     sys.exit(0)
 
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 512

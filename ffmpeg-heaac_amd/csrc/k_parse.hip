@@ -11,9 +11,11 @@
 // The same walk is instantiated for the host as heaac_debug_aac_parse_core (include/heaac_debug.h).
 //
 // heaac_sbr_parse_device: the payload walk of sbr_core.h in the same layout (k_sbr_parse, one lane per unit, the 3.4 KB
-// of code-book nodes in LDS).  A kernel ahead of it (k_sbr_prep, every lane of the grid, coalesced words) copies the
-// state rows in -> out and zeroes the records; the walk works on the out row and a lane that gives its unit up copies
-// the row once more.  heaac_debug_sbr_parse_core is the host form.
+// of code-book nodes in LDS).  sbr_core.h is the one writing of the payload syntax: the host parser (sbr_parse.c) reads
+// through the same sc_* functions and adds header registration, roll-backs and statuses; the device defers every unit
+// that needs one of those (sc_walk).  A kernel ahead of it (k_sbr_prep, every lane of the grid, coalesced words) copies
+// the state rows in -> out and zeroes the records; the walk works on the out row and a lane that gives its unit up
+// copies the row once more.  heaac_debug_sbr_parse_core is the host form.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>

@@ -1,17 +1,20 @@
-/* sbr_parse.c -- host-side parser of the SBR extension payload and its Parametric Stereo data
+/* sbr_parse.c -- the host's side of the SBR extension payload and its Parametric Stereo data
  * (include/heaac_parse.h, second slice).
  *
- * Own structure: the stream state is a plain record (HeaacSbrStream) the caller owns, one per stream;
- * derived band tables are never kept per stream -- a header that changes the tables is looked up in (or
- * added to) a table shared by the whole batch and the frame records carry its index, which is what
- * heaac_he_decode_batch takes.  Huffman codes are walked through binary trees built once from the ISO
- * (code, length) pairs of sbr_iso_tables.h.
+ * The payload syntax itself -- header fields, grid, dtdf, invf, envelopes, noise floors, harmonics, coupling, the PS
+ * reader, the emit of the two records -- is written once, in sbr_core.h, for this file and for the device walk
+ * (k_parse.hip); it is host-exact on every exit.  What stands here is what only the host does: the header table and a
+ * header's application and registration, the misplaced-payload rule, the roll-back of a refused element, the private
+ * PS cursor, the statuses and their order, the code-book table both callers walk (with the prefix table the host puts in
+ * front of the walk), and the whole-unit entries with their threads.  The device defers every unit that needs one of
+ * these.
  *
- * The bit order and every value follow the reference: ff_decode_sbr_extension (aacsbr.c:1044-1090),
- * read_sbr_header (:207-262), read_sbr_grid (:609-745), copy_sbr_grid (:747-766), read_sbr_dtdf /
- * read_sbr_invf / read_sbr_envelope / read_sbr_noise (:768-898), read_sbr_extension (:900-926),
- * read_sbr_single_channel_element / read_sbr_channel_pair_element / read_sbr_data (:928-1020),
- * ff_ps_read_data with its parameter readers (aacps.c:84-279).
+ * Own structure: the stream state is a plain record (HeaacSbrStream) the caller owns, one per stream; derived band
+ * tables are never kept per stream -- a header that changes the tables is looked up in (or added to) a table shared by
+ * the whole batch and the frame records carry its index, which is what heaac_he_decode_batch takes.
+ *
+ * The order of the payload follows the reference: ff_decode_sbr_extension (aacsbr.c:1044-1090), read_sbr_extension
+ * (:900-926), read_sbr_data (:982-1020); for the readers see sbr_core.h.
  */
 #include <pthread.h>
 #include <stdlib.h>
@@ -20,28 +23,57 @@
 #include "heaac_parse.h"
 #include "sbr_iso_tables.h"
 #include "parse_bits.h"
+#include "sbr_core.h"
 #include "validate.h"
 
-/* table order of sbr_iso_tables.h = the reference's enums (aacsbr.c:45-56, aacps.c:50-61) */
-enum { T_ENV_15, F_ENV_15, T_ENV_BAL_15, F_ENV_BAL_15, T_ENV_30, F_ENV_30, T_ENV_BAL_30, F_ENV_BAL_30,
-       T_NOISE_30, T_NOISE_BAL_30 };
-enum { PS_IID_DF1, PS_IID_DT1, PS_IID_DF0, PS_IID_DT0, PS_ICC_DF, PS_ICC_DT, PS_IPD_DF, PS_IPD_DT,
-       PS_OPD_DF, PS_OPD_DT };
-enum { FIXFIX, FIXVAR, VARFIX, VARVAR };
 enum { EXTENSION_ID_PS = 2 };
 
-static Tree g_sbr_tree[10], g_ps_tree[10];
-static pthread_once_t g_once = PTHREAD_ONCE_INIT;
-static int g_tables_bad;                              /* a code book did not fit its tree (never with the shipped tables) */
+/* ------------------------------------------------------------------------------------------ */
+/* code books: the ten SBR and the ten PS books of sbr_iso_tables.h (the order of the reference's enums,       */
+/* aacsbr.c:45-56, aacps.c:50-61) as one flat table of tree nodes, built once with parse_bits.h's tree_build;    */
+/* read here, and uploaded once per device context next to the tables of parse_core.h                           */
+/* ------------------------------------------------------------------------------------------ */
+static HeaacSbrParseTables g_st;
+static uint16_t g_st_lut[HEAAC_ST_BOOKS << SC_LUT_BITS];  /* the host's prefix table in front of the walk (sc_tree) */
+static int g_st_bad;                                   /* a code book did not fit (never with the shipped tables) */
+static pthread_once_t g_st_once = PTHREAD_ONCE_INIT;
 
-static void tables_init(void)
+static void st_init(void)
 {
-    for (int t = 0; t < 10; t++) {
-        g_tables_bad |= tree_build(&g_sbr_tree[t], sbr_huff_code + sbr_huff_first[t], NULL, sbr_huff_bits + sbr_huff_first[t],
-                   sbr_huff_first[t + 1] - sbr_huff_first[t]);
-        g_tables_bad |= tree_build(&g_ps_tree[t], ps_huff_code + ps_huff_first[t], NULL, ps_huff_bits + ps_huff_first[t],
-                   ps_huff_first[t + 1] - ps_huff_first[t]);
+    static Tree t;                                     /* 6 KB: not on the stack of whoever calls first */
+    int total = 0;
+    for (int k = 0; k < HEAAC_ST_BOOKS; k++) {
+        const int ps = k >= 10, j = k % 10;
+        const uint16_t *first = ps ? ps_huff_first : sbr_huff_first;
+        g_st_bad |= tree_build(&t, (ps ? ps_huff_code : sbr_huff_code) + first[j], NULL,
+                               (ps ? ps_huff_bits : sbr_huff_bits) + first[j], first[j + 1] - first[j]);
+        if (total + t.count > HEAAC_ST_NODES) { g_st_bad = 1; return; }
+        g_st.root[k] = (uint16_t)total;
+        g_st.bias[k] = ps ? ps_huff_offset[j] : sbr_huff_lav[j];
+        for (int i = 0; i < t.count; i++) {
+            g_st.node[total + i][0] = t.n[i].child[0];
+            g_st.node[total + i][1] = t.n[i].child[1];
+        }
+        total += t.count;
     }
+    /* the prefix table: every code of up to SC_LUT_BITS bits, found by walking the nodes just laid down */
+    for (int k = 0; k < HEAAC_ST_BOOKS; k++)
+        for (int p = 0; p < 1 << SC_LUT_BITS; p++) {
+            int at = g_st.root[k], c = 1;
+            for (int d = 1; d <= SC_LUT_BITS && c > 0; d++) {
+                c = g_st.node[at][(p >> (SC_LUT_BITS - d)) & 1];
+                at = g_st.root[k] + c;
+                if (c < 0) g_st_lut[(k << SC_LUT_BITS) + p] = (uint16_t)(d << 12 | (-c - 1));
+            }
+        }
+}
+
+/* The one host copy (NULL if a code book did not fit). */
+const HeaacSbrParseTables *heaac_sbr_parse_tables(void)
+{
+    pthread_once(&g_st_once, st_init);
+    (void)bits_init;                                   /* parse_bits.h's non-inline static, unused here: no warning */
+    return g_st_bad ? NULL : &g_st;
 }
 
 uint64_t heaac_sbr_tables_fingerprint(void)
@@ -149,634 +181,50 @@ void heaac_sbr_stream_init(HeaacSbrStream *st, size_t n)
 size_t heaac_sbr_stream_bytes(void) { return sizeof(HeaacSbrStream); }
 
 /* ------------------------------------------------------------------------------------------ */
-/* SBR header (read_sbr_header, aacsbr.c:207-262).  Returns 1 if the band tables must be rebuilt. */
+/* payload                                                                                       */
 /* ------------------------------------------------------------------------------------------ */
-static int read_header(HeaacSbrStream *s, Bits *b, int *tables_touched)
+/* A header is always applied (read_sbr_header stores what it reads), whatever it changes. */
+static void apply_header(HeaacSbrStream *s, const ScHeader *hd)
 {
-    const uint8_t old[6] = { s->bs_start_freq, s->bs_stop_freq, s->bs_xover_band,
-                             s->bs_freq_scale, s->bs_alter_scale, s->bs_noise_bands };
-    const uint8_t old_rest[5] = { s->bs_limiter_bands, s->bs_limiter_gains, s->bs_interpol_freq,
-                                  s->bs_smoothing_mode, s->bs_amp_res_header };
     s->start = 1;
-    s->bs_amp_res_header = (uint8_t)bit1(b);
-    s->bs_start_freq     = (uint8_t)bits(b, 4);
-    s->bs_stop_freq      = (uint8_t)bits(b, 4);
-    s->bs_xover_band     = (uint8_t)bits(b, 3);
-    bits(b, 2);                                        /* bs_reserved */
-    const unsigned extra_1 = bit1(b), extra_2 = bit1(b);
-    if (extra_1) {
-        s->bs_freq_scale  = (uint8_t)bits(b, 2);
-        s->bs_alter_scale = (uint8_t)bit1(b);
-        s->bs_noise_bands = (uint8_t)bits(b, 2);
-    } else {
-        s->bs_freq_scale = 2; s->bs_alter_scale = 1; s->bs_noise_bands = 2;
+    s->bs_amp_res_header = hd->amp_res;
+    s->bs_start_freq = hd->start_freq;   s->bs_stop_freq = hd->stop_freq;       s->bs_xover_band = hd->xover_band;
+    s->bs_freq_scale = hd->freq_scale;   s->bs_alter_scale = hd->alter_scale;   s->bs_noise_bands = hd->noise_bands;
+    s->bs_limiter_bands = hd->limiter_bands; s->bs_limiter_gains = hd->limiter_gains;
+    s->bs_interpol_freq = hd->interpol_freq; s->bs_smoothing_mode = hd->smoothing_mode;
+}
+
+/* Parametric Stereo through a private cursor: the SBR reader's own moves over the frame only when it is good.  On an
+ * error PS is switched off (ps->start = 0; the rest of *ps is as sc_ps left it), the rest of the extension is skipped
+ * and *status says which error it was.  Returns the bits the SBR reader steps over. */
+static int read_ps(const HeaacSbrParseTables *t, PcBits *host, HeaacPsState *ps, int bits_left_in_ext, int *status)
+{
+    PcBits own = *host;
+    const int used = sc_ps(t, g_st_lut, &own, ps, bits_left_in_ext);
+    if (used >= 0) {
+        *host = own;
+        *status = HEAAC_PARSE_OK;
+        return used;
     }
-    const uint8_t now[6] = { s->bs_start_freq, s->bs_stop_freq, s->bs_xover_band,
-                             s->bs_freq_scale, s->bs_alter_scale, s->bs_noise_bands };
-    const int reset = !s->have_spectrum || memcmp(old, now, 6) != 0;
-    if (extra_2) {
-        s->bs_limiter_bands  = (uint8_t)bits(b, 2);
-        s->bs_limiter_gains  = (uint8_t)bits(b, 2);
-        s->bs_interpol_freq  = (uint8_t)bit1(b);
-        s->bs_smoothing_mode = (uint8_t)bit1(b);
-    } else {
-        s->bs_limiter_bands = 2; s->bs_limiter_gains = 2; s->bs_interpol_freq = 1; s->bs_smoothing_mode = 1;
-    }
-    const uint8_t rest[5] = { s->bs_limiter_bands, s->bs_limiter_gains, s->bs_interpol_freq,
-                              s->bs_smoothing_mode, s->bs_amp_res_header };
-    /* the limiter table (:258-259) and the four scalars live in the derived record: any change of them
-     * selects another record without a reset */
-    *tables_touched = memcmp(old_rest, rest, 5) != 0;
-    return reset;
-}
-
-/* ------------------------------------------------------------------------------------------ */
-/* time / frequency grid.  VALUES as read_sbr_grid / copy_sbr_grid leave them (aacsbr.c:609-766); */
-/* the form is this parser's own: the syntax is read into a description of the two frame ends,   */
-/* and the envelope borders, the noise border and the transient envelope are derived from it.    */
-/* ------------------------------------------------------------------------------------------ */
-/* sbr_grid() transmits, for each END of the frame that the frame class declares variable, an absolute
- * border and up to three relative borders walking inwards from it; a fixed end sits at slot 0 / 16 and
- * has no relative borders (FIXFIX instead spreads 1, 2 or 4 envelopes evenly).  Class bit 1 = the
- * leading end is variable, bit 0 = the trailing end is. */
-#define GRID_LEAD_VAR(cls)  (((cls) >> 1) & 1)
-#define GRID_TRAIL_VAR(cls) ((cls) & 1)
-#define GRID_SLOTS 16                                  /* numTimeSlots (1024-sample frames) */
-
-typedef struct GridSyntax {
-    int cls, L;                                        /* frame class, envelopes */
-    int lead_abs, trail_abs;                           /* first and last border */
-    int n_lead, n_trail;                               /* relative borders at either end */
-    int lead_step[3], trail_step[3];                   /* their distances (2 r + 2), walking inwards */
-    unsigned pointer;                                  /* bs_pointer; 0 where none is sent */
-    uint8_t res[5];                                    /* bs_freq_res of envelope 1..L */
-} GridSyntax;
-
-/* bits of bs_pointer for L envelopes: ceil(log2(L + 1)) */
-static int grid_pointer_bits(int L) { int n = 0; while ((1 << n) < L + 1) n++; return n; }
-
-static int grid_read_syntax(Bits *b, GridSyntax *g)
-{
-    memset(g, 0, sizeof(*g));
-    g->cls = (int)bits(b, 2);
-    g->trail_abs = GRID_SLOTS;
-    if (g->cls == FIXFIX) {
-        g->L = 1 << bits(b, 2);
-        if (g->L > 4) return HEAAC_PARSE_ERR_DATA;     /* "too many SBR envelopes in FIXFIX" */
-        const unsigned r = bit1(b);                    /* one resolution bit for all envelopes */
-        for (int e = 0; e < g->L; e++) g->res[e] = (uint8_t)r;
-        return HEAAC_PARSE_OK;
-    }
-    /* absolute borders, then the counts, then the relative borders: leading end first */
-    if (GRID_LEAD_VAR(g->cls))  g->lead_abs = (int)bits(b, 2);
-    if (GRID_TRAIL_VAR(g->cls)) g->trail_abs += (int)bits(b, 2);
-    if (GRID_LEAD_VAR(g->cls))  g->n_lead = (int)bits(b, 2);
-    if (GRID_TRAIL_VAR(g->cls)) g->n_trail = (int)bits(b, 2);
-    g->L = g->n_lead + g->n_trail + 1;
-    if (g->L > 5) return HEAAC_PARSE_ERR_DATA;         /* "too many SBR envelopes in VARVAR" */
-    for (int i = 0; i < g->n_lead; i++)  g->lead_step[i]  = 2 * (int)bits(b, 2) + 2;
-    for (int i = 0; i < g->n_trail; i++) g->trail_step[i] = 2 * (int)bits(b, 2) + 2;
-    g->pointer = bits(b, grid_pointer_bits(g->L));
-    /* one resolution bit per envelope; a frame with only its trailing end variable sends them last
-     * envelope first */
-    const int backwards = g->cls == FIXVAR;
-    for (int e = 0; e < g->L; e++) g->res[backwards ? g->L - 1 - e : e] = (uint8_t)bit1(b);
-    return HEAAC_PARSE_OK;
-}
-
-/* Envelope borders t[0..L].  0 = fine; non-zero = two borders meet or cross (the reference's uint8
- * arithmetic wraps a border walked below zero to > 235, which its own monotony check then refuses;
- * meeting borders are refused here as well, see heaac_parse.h). */
-static int grid_borders(const GridSyntax *g, int t[6])
-{
-    const int L = g->L;
-    t[0] = g->lead_abs;
-    t[L] = g->trail_abs;
-    if (g->cls == FIXFIX) {
-        for (int e = 1; e < L; e++) t[e] = e * (GRID_SLOTS / L);      /* L in {1, 2, 4} */
-    } else {
-        for (int i = 0; i < g->n_lead; i++)  t[1 + i] = t[i] + g->lead_step[i];
-        for (int i = 0; i < g->n_trail; i++) t[L - 1 - i] = t[L - i] - g->trail_step[i];
-    }
-    for (int e = 0; e < L; e++)
-        if (t[e] >= t[e + 1] || t[e] < 0) return 1;
-    return 0;
-}
-
-/* Index into t_env[] of the middle noise border (two noise floors only).  ISO/IEC 14496-3 4.6.18.3.3 counts
- * the pointer from the variable end; the reference's expression for a variable trailing end is
- * `bs_num_env - FFMAX(bs_pointer - 1, 1)` on an UNSIGNED bs_pointer (aacsbr.c:613, 729): with bs_pointer = 0
- * the subtraction wraps and the index comes out as L + 1, one past the last border -- t_env[] keeps what an
- * earlier frame with more envelopes left there (0 in a new stream).  The reference is the contract, so the
- * same entry is taken here (ISO would give L - 1); tests/test_sbr_parse.py pins the case. */
-static int grid_noise_border_index(const GridSyntax *g)
-{
-    const int L = g->L, p = (int)g->pointer;
-    if (g->cls == FIXFIX) return L >> 1;
-    if (GRID_TRAIL_VAR(g->cls)) return p == 0 ? L + 1 : L - (p > 2 ? p - 1 : 1);
-    return p == 0 ? 1 : p == 1 ? L - 1 : p - 1;        /* VARFIX: counted from the leading end */
-}
-
-/* l_A: the envelope that starts at the transient, or -1 */
-static int grid_transient_envelope(const GridSyntax *g)
-{
-    const int p = (int)g->pointer;
-    if (GRID_TRAIL_VAR(g->cls)) return p ? g->L + 1 - p : -1;
-    if (g->cls == VARFIX) return p > 1 ? p - 1 : -1;
-    return -1;
-}
-
-/* What a channel keeps of the PREVIOUS frame's grid when a new one arrives: the resolution and the end of
- * its last envelope, and whether its transient envelope was its last (l_APrev). */
-static void grid_carry(HeaacSbrChanState *c)
-{
-    const int L_old = c->bs_num_env;
-    c->bs_freq_res[0] = c->bs_freq_res[L_old];
-    c->t_env_num_env_old = c->t_env[L_old];
-    c->e_a[0] = (int8_t)-(c->e_a[1] != L_old);
-}
-
-static int read_grid(const HeaacSbrStream *s, Bits *b, HeaacSbrChanState *c)
-{
-    GridSyntax g;
-    int t[6];
-    /* the previous frame's values move first, as in the reference, also when this grid is refused */
-    c->bs_freq_res[0] = c->bs_freq_res[c->bs_num_env];
-    c->t_env_num_env_old = c->t_env[c->bs_num_env];
-    const int L_old = c->bs_num_env;
-    const int rc = grid_read_syntax(b, &g);
-    if (rc) return rc;                                 /* (the caller rolls a refused element's channel state back) */
-    c->bs_frame_class = (uint8_t)g.cls;
-    c->bs_amp_res = (g.cls == FIXFIX && g.L == 1) ? 0 : s->bs_amp_res_header;
-    c->bs_num_env = (uint8_t)g.L;
-    const int crossed = grid_borders(&g, t);
-    for (int e = 0; e <= g.L; e++) c->t_env[e] = (uint8_t)t[e];
-    for (int e = 0; e < g.L; e++) c->bs_freq_res[1 + e] = g.res[e];
-    if (g.pointer > (unsigned)g.L + 1 || crossed) return HEAAC_PARSE_ERR_DATA;
-
-    c->bs_num_noise = (uint8_t)(g.L > 1 ? 2 : 1);
-    c->t_q[0] = c->t_env[0];
-    c->t_q[c->bs_num_noise] = c->t_env[g.L];
-    if (c->bs_num_noise > 1) c->t_q[1] = c->t_env[grid_noise_border_index(&g)];
-    c->e_a[0] = (int8_t)-(c->e_a[1] != L_old);
-    c->e_a[1] = (int8_t)grid_transient_envelope(&g);
-    return HEAAC_PARSE_OK;
-}
-
-/* The second channel of a coupled pair takes the first one's grid (copy_sbr_grid): its own carries, then
- * every transmitted grid field of the partner. */
-static void copy_grid(HeaacSbrChanState *dst, const HeaacSbrChanState *src)
-{
-    grid_carry(dst);
-    dst->bs_frame_class = src->bs_frame_class;
-    dst->bs_num_env = src->bs_num_env;
-    dst->bs_num_noise = src->bs_num_noise;
-    dst->bs_amp_res = src->bs_amp_res;
-    dst->e_a[1] = src->e_a[1];
-    for (int i = 0; i < 8; i++) dst->t_env[i] = src->t_env[i];
-    for (int i = 1; i < 8; i++) dst->bs_freq_res[i] = src->bs_freq_res[i];
-    for (int i = 0; i < 3; i++) dst->t_q[i] = src->t_q[i];
-}
-
-static void read_dtdf(Bits *b, HeaacSbrChanState *c)
-{
-    for (int i = 0; i < c->bs_num_env; i++)   c->bs_df_env[i]   = (uint8_t)bit1(b);
-    for (int i = 0; i < c->bs_num_noise; i++) c->bs_df_noise[i] = (uint8_t)bit1(b);
-}
-
-static void read_invf(const HeaacSbrHeader *h, Bits *b, HeaacSbrChanState *c)
-{
-    memcpy(c->bs_invf_mode[1], c->bs_invf_mode[0], 5);
-    for (int i = 0; i < h->n_q; i++) c->bs_invf_mode[0][i] = (uint8_t)bits(b, 2);
-}
-
-static inline int huff(Bits *b, int table, int *bad)
-{
-    const int s = tree_read(&g_sbr_tree[table], b);
-    if (s < 0) { *bad = 1; return 0; }                /* complete codes: reachable only past the end */
-    return s - sbr_huff_lav[table];
-}
-
-/* read_sbr_envelope (:783-858) */
-static void read_envelope(const HeaacSbrStream *s, const HeaacSbrHeader *h, Bits *b, HeaacSbrChanState *c, int ch, int *bad)
-{
-    int start_bits, t_huff, f_huff;
-    const int delta = (ch == 1 && s->bs_coupling == 1) + 1;
-    const int odd = h->n[1] & 1;
-
-    if (s->bs_coupling && ch) {
-        if (c->bs_amp_res) { start_bits = 5; t_huff = T_ENV_BAL_30; f_huff = F_ENV_BAL_30; }
-        else               { start_bits = 6; t_huff = T_ENV_BAL_15; f_huff = F_ENV_BAL_15; }
-    } else {
-        if (c->bs_amp_res) { start_bits = 6; t_huff = T_ENV_30; f_huff = F_ENV_30; }
-        else               { start_bits = 7; t_huff = T_ENV_15; f_huff = F_ENV_15; }
-    }
-    for (int i = 0; i < c->bs_num_env; i++) {
-        const int res = c->bs_freq_res[i + 1], nb = h->n[res];
-        int32_t *cur = c->env_facs[i + 1];
-        const int32_t *prev = c->env_facs[i];
-        if (c->bs_df_env[i]) {
-            if (res == c->bs_freq_res[i]) {
-                for (int j = 0; j < nb; j++) cur[j] = prev[j] + delta * huff(b, t_huff, bad);
-            } else if (res) {
-                for (int j = 0; j < nb; j++) cur[j] = prev[(j + odd) >> 1] + delta * huff(b, t_huff, bad);
-            } else {
-                for (int j = 0; j < nb; j++) cur[j] = prev[j ? 2 * j - odd : 0] + delta * huff(b, t_huff, bad);
-            }
-        } else {
-            cur[0] = delta * (int)bits(b, start_bits);
-            for (int j = 1; j < nb; j++) cur[j] = cur[j - 1] + delta * huff(b, f_huff, bad);
-        }
-    }
-    memcpy(c->env_facs[0], c->env_facs[c->bs_num_env], sizeof(c->env_facs[0]));
-}
-
-/* read_sbr_noise (:860-898) */
-static void read_noise(const HeaacSbrStream *s, const HeaacSbrHeader *h, Bits *b, HeaacSbrChanState *c, int ch, int *bad)
-{
-    const int delta = (ch == 1 && s->bs_coupling == 1) + 1;
-    const int t_huff = (s->bs_coupling && ch) ? T_NOISE_BAL_30 : T_NOISE_30;
-    const int f_huff = (s->bs_coupling && ch) ? F_ENV_BAL_30 : F_ENV_30;
-    for (int i = 0; i < c->bs_num_noise; i++) {
-        int32_t *cur = c->noise_facs[i + 1];
-        const int32_t *prev = c->noise_facs[i];
-        if (c->bs_df_noise[i]) {
-            for (int j = 0; j < h->n_q; j++) cur[j] = prev[j] + delta * huff(b, t_huff, bad);
-        } else {
-            cur[0] = delta * (int)bits(b, 5);
-            for (int j = 1; j < h->n_q; j++) cur[j] = cur[j - 1] + delta * huff(b, f_huff, bad);
-        }
-    }
-    memcpy(c->noise_facs[0], c->noise_facs[c->bs_num_noise], sizeof(c->noise_facs[0]));
-}
-
-static void read_harmonics(const HeaacSbrHeader *h, Bits *b, HeaacSbrChanState *c)
-{
-    if ((c->bs_add_harmonic_flag = (uint8_t)bit1(b)))
-        for (int i = 0; i < h->n[1]; i++) c->bs_add_harmonic[i] = (uint8_t)bit1(b);
-}
-
-/* the uint8 range of the frame record */
-static int facs_in_range(const HeaacSbrHeader *h, const HeaacSbrChanState *c)
-{
-    for (int e = 1; e <= c->bs_num_env; e++)
-        for (int k = 0; k < h->n[c->bs_freq_res[e]]; k++)
-            if (c->env_facs[e][k] < 0 || c->env_facs[e][k] > 255) return 0;
-    for (int e = 1; e <= c->bs_num_noise; e++)
-        for (int k = 0; k < h->n_q; k++)
-            if (c->noise_facs[e][k] < 0 || c->noise_facs[e][k] > 255) return 0;
-    return 1;
-}
-
-static int read_sce(HeaacSbrStream *s, const HeaacSbrHeader *h, Bits *b)
-{
-    int bad = 0;
-    HeaacSbrChanState *c = &s->data[0];
-    if (bit1(b)) bits(b, 4);                           /* bs_data_extra, bs_reserved */
-    if (read_grid(s, b, c)) return HEAAC_PARSE_ERR_DATA;
-    read_dtdf(b, c);
-    read_invf(h, b, c);
-    read_envelope(s, h, b, c, 0, &bad);
-    read_noise(s, h, b, c, 0, &bad);
-    read_harmonics(h, b, c);
-    return (bad || !facs_in_range(h, c)) ? HEAAC_PARSE_ERR_DATA : HEAAC_PARSE_OK;
-}
-
-static int read_cpe(HeaacSbrStream *s, const HeaacSbrHeader *h, Bits *b)
-{
-    int bad = 0;
-    HeaacSbrChanState *c0 = &s->data[0], *c1 = &s->data[1];
-    if (bit1(b)) bits(b, 8);
-    if ((s->bs_coupling = (uint8_t)bit1(b))) {
-        if (read_grid(s, b, c0)) return HEAAC_PARSE_ERR_DATA;
-        copy_grid(c1, c0);
-        read_dtdf(b, c0);
-        read_dtdf(b, c1);
-        read_invf(h, b, c0);
-        memcpy(c1->bs_invf_mode[1], c1->bs_invf_mode[0], 5);
-        memcpy(c1->bs_invf_mode[0], c0->bs_invf_mode[0], 5);
-        read_envelope(s, h, b, c0, 0, &bad);
-        read_noise(s, h, b, c0, 0, &bad);
-        read_envelope(s, h, b, c1, 1, &bad);
-        read_noise(s, h, b, c1, 1, &bad);
-    } else {
-        if (read_grid(s, b, c0) || read_grid(s, b, c1)) return HEAAC_PARSE_ERR_DATA;
-        read_dtdf(b, c0);
-        read_dtdf(b, c1);
-        read_invf(h, b, c0);
-        read_invf(h, b, c1);
-        read_envelope(s, h, b, c0, 0, &bad);
-        read_envelope(s, h, b, c1, 1, &bad);
-        read_noise(s, h, b, c0, 0, &bad);
-        read_noise(s, h, b, c1, 1, &bad);
-    }
-    read_harmonics(h, b, c0);
-    read_harmonics(h, b, c1);
-    return (bad || !facs_in_range(h, c0) || !facs_in_range(h, c1)) ? HEAAC_PARSE_ERR_DATA : HEAAC_PARSE_OK;
-}
-
-/* ------------------------------------------------------------------------------------------ */
-/* Parametric Stereo payload.  VALUES as ff_ps_read_data leaves them (aacps.c:84-279); the form  */
-/* is this parser's own: ps_data() is read as a mode header, a time grid and then one block per   */
-/* parameter KIND, each kind described by a record of where it lives and how it is coded.        */
-/* ------------------------------------------------------------------------------------------ */
-/* resolution mode 0..5 -> parameters per envelope (ISO/IEC 14496-3 Table 8.4x): modes 3..5 repeat 0..2 with
- * the fine IID quantiser */
-static int ps_mode_bands(int mode)  { static const int8_t n[3] = { 10, 20, 34 }; return n[mode % 3]; }
-static int ps_mode_phases(int mode) { static const int8_t n[3] = { 5, 11, 17 };  return n[mode % 3]; }
-
-/* One kind of stereo parameter of one frame. */
-typedef struct PsKind {
-    int8_t (*par)[34];            /* [envelope][band] */
-    int count;                    /* values per envelope */
-    int book[2];                  /* code book by direction: [0] along frequency, [1] along time */
-    int bias[2];                  /* what that code book adds to a difference */
-    int modulo;                   /* phases wrap modulo 8; 0 = plain integers */
-    int lo, hi;                   /* legal range of an accumulated value (ignored for phases) */
-} PsKind;
-
-static PsKind ps_kind_iid(HeaacPsState *ps)
-{
-    const int fine = ps->iid_quant;
-    const int df = fine ? PS_IID_DF1 : PS_IID_DF0, dt = fine ? PS_IID_DT1 : PS_IID_DT0;
-    const int top = fine ? 15 : 7;
-    const PsKind k = { ps->iid_par, ps->nr_iid_par, { df, dt }, { ps_huff_offset[df], ps_huff_offset[dt] }, 0, -top, top };
-    return k;
-}
-static PsKind ps_kind_icc(HeaacPsState *ps)
-{
-    const PsKind k = { ps->icc_par, ps->nr_icc_par, { PS_ICC_DF, PS_ICC_DT },
-                       { ps_huff_offset[PS_ICC_DF], ps_huff_offset[PS_ICC_DT] }, 0, 0, 7 };
-    return k;
-}
-static PsKind ps_kind_phase(HeaacPsState *ps, int opd)
-{
-    const PsKind k = { opd ? ps->opd_par : ps->ipd_par, ps->nr_ipdopd_par,
-                       { opd ? PS_OPD_DF : PS_IPD_DF, opd ? PS_OPD_DT : PS_IPD_DT }, { 0, 0 }, 8, 0, 0 };
-    return k;
-}
-
-/* One envelope of one kind: a direction bit, then `count` code words.  Along frequency a value continues
- * from its lower neighbour (from 0 for the first), along time from the same band of the previous envelope --
- * for envelope 0 the last one of the previous frame. */
-static int ps_read_envelope(Bits *b, const HeaacPsState *ps, const PsKind *k, int e)
-{
-    const int along_time = (int)bit1(b);
-    const Tree *book = &g_ps_tree[k->book[along_time]];
-    const int8_t *before = NULL;
-    if (along_time) {
-        const int src = e > 0 ? e - 1 : ps->num_env_old > 0 ? ps->num_env_old - 1 : 0;
-        before = k->par[src];
-    }
-    int run = 0;
-    for (int band = 0; band < k->count; band++) {
-        const int sym = tree_read(book, b);
-        if (sym < 0) return HEAAC_PARSE_ERR_DATA;
-        run = (before ? before[band] : run) + sym - k->bias[along_time];
-        if (k->modulo) run &= k->modulo - 1;
-        else if (run < k->lo || run > k->hi) { k->par[e][band] = (int8_t)run; return HEAAC_PARSE_ERR_DATA; }
-        k->par[e][band] = (int8_t)run;
-    }
-    return HEAAC_PARSE_OK;
-}
-
-/* All envelopes of a kind that is switched on; a kind that is off reads as zeros. */
-static int ps_read_kind(Bits *b, HeaacPsState *ps, int enabled, PsKind k)
-{
-    if (!enabled) { memset(k.par, 0, 5 * 34); return HEAAC_PARSE_OK; }
-    for (int e = 0; e < ps->num_env; e++)
-        if (ps_read_envelope(b, ps, &k, e)) return HEAAC_PARSE_ERR_DATA;
-    return HEAAC_PARSE_OK;
-}
-
-/* enable_ps_header: which kinds are on and at which resolution.  0, or non-zero for a reserved mode. */
-static int ps_read_modes(Bits *b, HeaacPsState *ps)
-{
-    if ((ps->enable_iid = (uint8_t)bit1(b))) {
-        const int mode = (int)bits(b, 3);
-        if (mode > 5) return 1;
-        ps->nr_iid_par = (uint8_t)ps_mode_bands(mode);
-        ps->nr_ipdopd_par = (uint8_t)ps_mode_phases(mode);
-        ps->iid_quant = mode >= 3;
-    }
-    if ((ps->enable_icc = (uint8_t)bit1(b))) {
-        const int mode = (int)bits(b, 3);
-        if (mode > 5) return 1;                        /* (the reference stores the reserved value before refusing it) */
-        ps->icc_mode = (uint8_t)mode;
-        ps->nr_icc_par = (uint8_t)ps_mode_bands(mode);
-    }
-    ps->enable_ext = (uint8_t)bit1(b);
-    return 0;
-}
-
-/* Envelope count and borders: class 0 = 0, 1, 2 or 4 envelopes cutting the 32 slots evenly, class 1 = 1..4
- * envelopes with transmitted borders.  border_position[0] = -1. */
-static void ps_read_time_grid(Bits *b, HeaacPsState *ps)
-{
-    ps->frame_class = (uint8_t)bit1(b);
-    const int code = (int)bits(b, 2);
-    ps->num_env_old = ps->num_env;
-    ps->num_env = (uint8_t)(ps->frame_class ? code + 1 : code == 3 ? 4 : code);
-    ps->border_position[0] = -1;
-    for (int e = 1; e <= ps->num_env; e++)
-        ps->border_position[e] = (int8_t)(ps->frame_class ? (int)bits(b, 5) : e * 32 / ps->num_env - 1);
-}
-
-/* ps_extension(): id 0 carries the phase parameters (IPD and OPD interleaved per envelope) and a
- * reserved bit; other ids carry nothing this decoder reads.  Returns the bits consumed. */
-static int ps_read_extension(Bits *b, HeaacPsState *ps, int id)
-{
-    const int at = b->pos;
-    if (id != 0) return 0;
-    if ((ps->enable_ipdopd = (uint8_t)bit1(b))) {
-        const PsKind ipd = ps_kind_phase(ps, 0), opd = ps_kind_phase(ps, 1);
-        for (int e = 0; e < ps->num_env; e++) {
-            ps_read_envelope(b, ps, &ipd, e);
-            ps_read_envelope(b, ps, &opd, e);
-        }
-    }
-    bit1(b);                                           /* reserved_ps */
-    return b->pos - at;
-}
-
-/* The extension container: a byte count (escaped at 15), then extensions while at least one byte
- * remains; what is left is padding.  Non-zero if the extensions ran past the count. */
-static int ps_read_extensions(Bits *b, HeaacPsState *ps)
-{
-    int left = (int)bits(b, 4);
-    if (left == 15) left += (int)bits(b, 8);
-    left *= 8;
-    while (left > 7) {
-        const int id = (int)bits(b, 2);
-        left -= 2 + ps_read_extension(b, ps, id);
-    }
-    if (left < 0) return 1;
-    b->pos += left;
-    return 0;
-}
-
-/* The last envelope must reach the end of the frame (slot 31): if it does not -- or no envelope was
- * sent -- one more is appended that repeats the last parameters known (this frame's last envelope, or
- * the previous frame's).  aacps.c:234-253. */
-static void ps_close_time_grid(HeaacPsState *ps)
-{
-    const int n = ps->num_env;
-    if (n && ps->border_position[n] >= 31) return;
-    const int from = n ? n - 1 : (int)ps->num_env_old - 1;
-    if (from >= 0 && from != n) {
-        int8_t (*const sets[4])[34] = { ps->iid_par, ps->icc_par, ps->ipd_par, ps->opd_par };
-        const int on[4] = { ps->enable_iid, ps->enable_icc, ps->enable_ipdopd, ps->enable_ipdopd };
-        for (int k = 0; k < 4; k++)
-            if (on[k]) memcpy(sets[k][n], sets[k][from], 34);
-    }
-    ps->num_env = (uint8_t)(n + 1);
-    ps->border_position[n + 1] = 31;
-}
-
-/* What this parser refuses although the reference goes on (heaac_parse.h): borders that do not ascend, and
- * values outside the quantiser of THIS frame in an envelope borrowed from an earlier one. */
-static int ps_frame_is_usable(const HeaacPsState *ps_c)
-{
-    HeaacPsState *ps = (HeaacPsState *)ps_c;           /* (the kind records are not const-qualified) */
-    for (int e = 0; e < ps->num_env; e++)
-        if (ps->border_position[e] >= ps->border_position[e + 1]) return 0;
-    const PsKind kinds[2] = { ps_kind_iid(ps), ps_kind_icc(ps) };
-    const int on[2] = { ps->enable_iid, ps->enable_icc };
-    for (int k = 0; k < 2; k++)
-        for (int e = 0; on[k] && e < ps->num_env; e++)
-            for (int band = 0; band < kinds[k].count; band++)
-                if (kinds[k].par[e][band] < kinds[k].lo || kinds[k].par[e][band] > kinds[k].hi) return 0;
-    return 1;
-}
-
-/* Returns the bits the SBR reader must step over; *status = OK or the error that cleared ps->start. */
-static int read_ps(Bits *host, HeaacPsState *ps, int bits_left_in_ext, int *status)
-{
-    Bits own = *host, *b = &own;                       /* a private cursor: the host only moves on success */
-    const int at = b->pos;
-    int ok;
-    *status = HEAAC_PARSE_ERR_DATA;
-
-    const int has_modes = (int)bit1(b);
-    ok = !(has_modes && ps_read_modes(b, ps));
-    if (ok) {
-        ps_read_time_grid(b, ps);
-        ok = ps_read_kind(b, ps, ps->enable_iid, ps_kind_iid(ps)) == HEAAC_PARSE_OK &&
-             ps_read_kind(b, ps, ps->enable_icc, ps_kind_icc(ps)) == HEAAC_PARSE_OK;
-    }
-    if (ok && ps->enable_ext) ok = !ps_read_extensions(b, ps);
-    if (ok) {
-        ps_close_time_grid(ps);
-        /* band layout of this frame: 34 bands as soon as one kind is sent at that resolution; a frame
-         * that sends neither keeps the layout it had */
-        ps->is34bands_old = ps->is34bands;
-        if (ps->enable_iid || ps->enable_icc)
-            ps->is34bands = (ps->enable_iid && ps->nr_iid_par == 34) || (ps->enable_icc && ps->nr_icc_par == 34);
-        if (!ps->enable_ipdopd) {
-            memset(ps->ipd_par, 0, sizeof(ps->ipd_par));
-            memset(ps->opd_par, 0, sizeof(ps->opd_par));
-        }
-        if (has_modes) ps->start = 1;
-        ok = ps_frame_is_usable(ps);
-    }
-    if (ok) {
-        const int used = b->pos - at;
-        if (used <= bits_left_in_ext) {
-            host->pos += used;
-            if (b->over) host->over = 1;
-            *status = HEAAC_PARSE_OK;
-            return used;
-        }
-        *status = HEAAC_PARSE_ERR_OVERREAD;
-    }
+    *status = used == SC_PS_ERR_OVERREAD ? HEAAC_PARSE_ERR_OVERREAD : HEAAC_PARSE_ERR_DATA;
     ps->start = 0;
     host->pos += bits_left_in_ext;
     return bits_left_in_ext;
 }
 
-/* ------------------------------------------------------------------------------------------ */
-/* records                                                                                       */
-/* ------------------------------------------------------------------------------------------ */
-static void emit_ps(const HeaacPsState *s, HeaacPsFrame *p)
-{
-    memset(p, 0, sizeof(*p));
-    p->border_position[0] = -1;
-    p->border_position[1] = 31;
-    p->num_env = 1;
-    p->nr_iid_par = p->nr_icc_par = 20;
-    p->nr_ipdopd_par = 11;
-    p->is34bands = s->is34bands;
-    p->is34bands_old = s->is34bands_old;
-    if (!s->start) return;                             /* mono copy: nothing else is read */
-    p->start = 1;
-    p->num_env = s->num_env;
-    p->num_env_old = s->num_env_old;
-    p->enable_ipdopd = s->enable_ipdopd;
-    p->iid_quant = s->iid_quant;
-    p->icc_mode = s->icc_mode;
-    /* a parameter set that was never enabled has no count yet; its values are all zero, for which every
-     * count maps to the same thing (aacps.c:826-871) */
-    p->nr_iid_par = s->nr_iid_par ? s->nr_iid_par : 20;
-    p->nr_icc_par = s->nr_icc_par ? s->nr_icc_par : 20;
-    p->nr_ipdopd_par = s->nr_ipdopd_par ? s->nr_ipdopd_par : 11;
-    memcpy(p->border_position, s->border_position, 6);
-    for (int e = 0; e < 5; e++) {
-        memcpy(p->iid_par[e], s->iid_par[e], 34);
-        memcpy(p->icc_par[e], s->icc_par[e], 34);
-        memcpy(p->ipd_par[e], s->ipd_par[e], 17);
-        memcpy(p->opd_par[e], s->opd_par[e], 17);
-    }
-}
-
-static void emit_sbr(const HeaacSbrStream *s, const HeaacSbrHeader *h, int channels, HeaacSbrFrame *f)
-{
-    memset(f, 0, sizeof(*f));
-    f->hdr = (uint16_t)s->hdr;
-    f->start = s->start;
-    f->reset = s->reset;
-    f->kx_old = s->kx[0];
-    f->m_old = s->m[0];
-    f->bs_coupling = channels == 2 ? s->bs_coupling : 0;
-    for (int ch = 0; ch < channels; ch++) {
-        const HeaacSbrChanState *c = &s->data[ch];
-        HeaacSbrChannel *o = &f->ch[ch];
-        o->t_env_num_env_old = c->t_env_num_env_old;
-        if (!s->start) continue;                       /* nothing else of the channel is read */
-        o->bs_num_env = c->bs_num_env;
-        o->bs_num_noise = c->bs_num_noise;
-        o->bs_amp_res = c->bs_amp_res;
-        o->bs_add_harmonic_flag = c->bs_add_harmonic_flag;
-        memcpy(o->bs_freq_res, c->bs_freq_res, 8);
-        memcpy(o->t_env, c->t_env, 8);
-        memcpy(o->t_q, c->t_q, 3);
-        o->e_a[0] = c->e_a[0];
-        o->e_a[1] = c->e_a[1];
-        memcpy(o->bs_invf_mode, c->bs_invf_mode, 10);
-        memcpy(o->bs_add_harmonic, c->bs_add_harmonic, 48);
-        /* the bands of each envelope's resolution; what a state row holds beyond them is not data */
-        for (int e = 0; e < c->bs_num_env; e++)
-            for (int k = 0; k < h->n[c->bs_freq_res[e + 1]]; k++) o->env_facs_q[e][k] = (uint8_t)c->env_facs[e + 1][k];
-        for (int e = 0; e < c->bs_num_noise; e++)
-            for (int k = 0; k < h->n_q; k++) o->noise_facs_q[e][k] = (uint8_t)c->noise_facs[e + 1][k];
-    }
-}
-
 void heaac_sbr_no_payload(HeaacSbrStream *st, int channels, HeaacSbrFrame *sbr, HeaacPsFrame *ps)
 {
-    HeaacSbrStream t = *st;
-    t.start = 0;
-    t.reset = 0;
-    t.kx[0] = t.kx[1];
-    t.m[0] = t.m[1];
-    emit_sbr(&t, NULL, channels, sbr);
-    if (ps) emit_ps(&st->ps, ps);
     st->kx[0] = st->kx[1];
     st->m[0] = st->m[1];
+    memset(sbr, 0, sizeof(*sbr));
+    sc_emit_sbr(st, NULL, channels, 0, 0, sbr);
+    if (ps) {
+        memset(ps, 0, sizeof(*ps));
+        sc_emit_ps(&st->ps, ps);
+    }
 }
 
-/* ------------------------------------------------------------------------------------------ */
-/* ff_decode_sbr_extension (aacsbr.c:1044-1090) + read_sbr_data (:982-1020)                      */
-/* ------------------------------------------------------------------------------------------ */
+/* ff_decode_sbr_extension (aacsbr.c:1044-1090) + read_sbr_data (:982-1020) */
 int heaac_sbr_parse_payload(HeaacSbrStream *st, HeaacSbrHeaderTable *tab, int sample_rate,
                             const uint8_t *au, int size, int bit, int cnt, int crc,
                             int channels, int allow_ps,
@@ -788,24 +236,27 @@ int heaac_sbr_parse_payload(HeaacSbrStream *st, HeaacSbrHeaderTable *tab, int sa
         return HEAAC_PARSE_ERR_ARG;
     const int misplaced = allow_ps & HEAAC_SBR_MISPLACED;
     allow_ps &= HEAAC_SBR_ALLOW_PS;
-    pthread_once(&g_once, tables_init);
-    if (g_tables_bad) return HEAAC_PARSE_ERR_ARG;
+    const HeaacSbrParseTables *t = heaac_sbr_parse_tables();
+    if (!t) return HEAAC_PARSE_ERR_ARG;
 
-    Bits gb, *b = &gb;
-    bits_init(b, au, size);
+    PcBits gb, *b = &gb;
+    pc_init(b, au, size);
     b->pos = bit;
     int ret = HEAAC_PARSE_OK;
     HeaacSbrParseInfo fi = { 0, 0, 0, HEAAC_PARSE_OK };
 
     st->reset = 0;
-    if (crc) bits(b, 10);                              /* bs_sbr_crc_bits: not checked by the reference either */
+    if (crc) pc_bits(b, 10);                           /* bs_sbr_crc_bits: not checked by the reference either */
     st->kx[0] = st->kx[1];
     st->m[0]  = st->m[1];
 
-    if (bit1(b)) {                                     /* bs_header_flag */
-        int touched = 0;
+    if (pc_bit1(b)) {                                  /* bs_header_flag */
+        ScHeader hd;
         fi.header = 1;
-        st->reset = (uint8_t)read_header(st, b, &touched);
+        sc_read_header(b, &hd);
+        const int touched = sc_header_touches(st, &hd);
+        st->reset = (uint8_t)sc_header_resets(st, &hd);
+        apply_header(st, &hd);
         if (st->reset || (touched && st->hdr)) {
             HdrKey k;
             make_key(&k, st, 2 * sample_rate);
@@ -832,21 +283,20 @@ int heaac_sbr_parse_payload(HeaacSbrStream *st, HeaacSbrHeaderTable *tab, int sa
         const HeaacSbrHeader *h = &tab->h[st->hdr];
         const HeaacSbrChanState keep0 = st->data[0], keep1 = st->data[1];
         const uint8_t keep_coupling = st->bs_coupling;
-        const int r = channels == 2 ? read_cpe(st, h, b) : read_sce(st, h, b);
-        if (r) {
+        if (sc_element(t, g_st_lut, st, h, b, channels)) {       /* refused: the channels are as they were before it */
             st->data[0] = keep0; st->data[1] = keep1; st->bs_coupling = keep_coupling;
             st->start = 0;
-            ret = r;
-        } else if (bit1(b)) {                          /* bs_extended_data */
-            int left = (int)bits(b, 4);
-            if (left == 15) left += (int)bits(b, 8);
+            ret = HEAAC_PARSE_ERR_DATA;
+        } else if (pc_bit1(b)) {                       /* bs_extended_data */
+            int left = (int)pc_bits(b, 4);
+            if (left == 15) left += (int)pc_bits(b, 8);
             left <<= 3;
             while (left > 7) {
                 left -= 2;
-                const int id = (int)bits(b, 2);
+                const int id = (int)pc_bits(b, 2);
                 if (id == EXTENSION_ID_PS && allow_ps) {
                     fi.ps_present = 1;
-                    left -= read_ps(b, &st->ps, left, &fi.ps_status);
+                    left -= read_ps(t, b, &st->ps, left, &fi.ps_status);
                 } else {                               /* PS signalled absent, or a reserved extension */
                     b->pos += left;
                     left = 0;
@@ -858,8 +308,12 @@ int heaac_sbr_parse_payload(HeaacSbrStream *st, HeaacSbrHeaderTable *tab, int sa
     fi.sbr_bits = b->pos - bit;
     if (b->over && ret == HEAAC_PARSE_OK) ret = HEAAC_PARSE_ERR_OVERREAD;
 
-    emit_sbr(st, &tab->h[st->hdr], channels, sbr);
-    if (ps) emit_ps(&st->ps, ps);
+    memset(sbr, 0, sizeof(*sbr));
+    sc_emit_sbr(st, &tab->h[st->hdr], channels, st->start, st->reset, sbr);
+    if (ps) {
+        memset(ps, 0, sizeof(*ps));
+        sc_emit_ps(&st->ps, ps);
+    }
     if (info) *info = fi;
     if (ret == HEAAC_PARSE_OK && fi.ps_status) ret = fi.ps_status;
     return ret;

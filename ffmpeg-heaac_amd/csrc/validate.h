@@ -81,7 +81,7 @@ HEAAC_HD int heaac_check_sbr_channel(const HeaacSbrChannel *c, int n_q)
         return HEAAC_BAD_SBR_T_Q;
     /* The middle noise border is an envelope border of this frame -- or, for a frame with a variable trailing
      * end and bs_pointer = 0, the entry behind the last border that an EARLIER frame left in t_env[] (the
-     * reference's unsigned pointer arithmetic, aacsbr.c:729; csrc/sbr_parse.c grid_noise_border_index): any time
+     * reference's unsigned pointer arithmetic, aacsbr.c:729; csrc/sbr_core.h sc_grid): any time
      * slot a border can have, or 0.  It only enters `t_env[e] >= t_q[1]` (sbr_mapping, aacsbr.c:1467). */
     if (c->bs_num_noise > 1 && c->t_q[1] > 19) return HEAAC_BAD_SBR_T_Q;
     if (c->bs_amp_res > 1 || c->bs_add_harmonic_flag > 1 || c->t_env_num_env_old > 19 ||

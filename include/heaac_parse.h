@@ -501,6 +501,10 @@ int heaac_heaac_parse_batch(const HeaacAacConfig *cfg, HeaacAacStream *st, Heaac
  * every unit (as the host call writes one whenever it is handed the pointer).  Every pointer but cfg is device memory,
  * 4-byte aligned (d_au: any).
  *
+ * One writing.  The payload syntax stands once, in csrc/sbr_core.h: heaac_sbr_parse_payload reads through the same
+ * functions as the kernel, host-exact on every exit, and adds what only the host does -- applying and registering a
+ * header, the roll-back of a refused element, the statuses.  The device decides none of these and defers instead.
+ *
  * State.  A lane cannot hold the copies the host parser rolls a HeaacSbrStream (3 336 bytes) back from, so the call
  * takes the states of all units in d_sst_in and leaves them in d_sst_out; the two arrays must not overlap, and a caller
  * ping-pongs two of them.  Per unit, d_status[i] is
@@ -512,7 +516,7 @@ int heaac_heaac_parse_batch(const HeaacAacConfig *cfg, HeaacAacStream *st, Heaac
  *   HEAAC_PARSE_DEFERRED  not parsed here: d_sst_out[i] equals d_sst_in[i], d_sbr[i] and d_ps[i] are unspecified; parse
  *                         the unit's payload on the host from that state (heaac_sbr_parse_payload, which registers
  *                         headers in the host's table; upload new entries before the decode) and upload its records.
- * Taken are: a payload without a header; a payload whose header changes nothing (read_header's reset == 0 and
+ * Taken are: a payload without a header; a payload whose header changes nothing (its reset == 0 and
  * tables_touched == 0); a unit without a payload.  Deferred are: a header that resets the band tables or touches the
  * derived record, the first header of a stream included (the device never registers a header); d_sst_in[i].hdr >=
  * n_hdr; a payload flagged sbr_misplaced; every unit the host call would return anything but HEAAC_PARSE_OK for from

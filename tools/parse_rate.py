@@ -185,6 +185,8 @@ def he_mode(argv):
         d_out = {k: torch.empty(sizes_of[k], dtype=dt_of.get(k, torch.uint8), device="cuda") for k in names}
         h_out = {k: torch.empty(sizes_of[k], dtype=dt_of.get(k, torch.uint8)).pin_memory() for k in names}
         u_out = {k: torch.empty_like(v, device="cuda") for k, v in h_out.items()}
+        for t in list(d_out.values()) + list(h_out.values()):  # one fill on both sides: a byte neither form writes compares equal
+            t.view(-1).view(torch.uint8).fill_(0xA5)
         keep = [C.create_string_buffer(u, len(u)) for u in units]
         ptrs = (C.c_char_p * n)(*[C.cast(keep[i], C.c_char_p) for i in tile])
         sizes = (C.c_int * n)(*[len(u) for u in aus])
@@ -224,9 +226,11 @@ def he_mode(argv):
         for _ in range(3):
             device_round(); host_round()
         deferred = int(d_out["status"].cpu().numpy().astype(bool).sum())
-        same = deferred == 0 and all(np.array_equal(d_out[k].cpu().numpy().reshape(-1).view(np.uint8),
-                                                    u_out[k].cpu().numpy().reshape(-1).view(np.uint8)) for k in names) and \
-            np.array_equal(d_sst_out.cpu().numpy(), h_sst.reshape(-1))
+        differ = [k for k in names if not np.array_equal(d_out[k].cpu().numpy().reshape(-1).view(np.uint8),
+                                                         u_out[k].cpu().numpy().reshape(-1).view(np.uint8))]
+        if not np.array_equal(d_sst_out.cpu().numpy().reshape(-1), h_sst.reshape(-1)):     # (the two arrays differ in shape)
+            differ.append("sst")
+        same = deferred == 0 and not differ
         dev_ms, dev_h2d, host_ms, host_h2d = [], [], [], []
         for _ in range(a.rounds):
             x, y = device_round(); dev_ms.append(x); dev_h2d.append(y)
@@ -236,7 +240,7 @@ def he_mode(argv):
         lines += [
             dict(form="heaac_heaac_parse_device", corpus=corpus, units=n, distinct=d, mean_unit_bytes=round(mean_size, 1),
                  rounds=a.rounds, call_ms=sp(dev_ms), h2d_bytes_ms=sp(dev_h2d), link_bytes_per_unit=round(mean_size + 4, 1),
-                 units_per_s=round(n / (np.median(dev_ms) * 1e-3)), deferred=deferred, records_equal_host=bool(same)),
+                 units_per_s=round(n / (np.median(dev_ms) * 1e-3)), deferred=deferred, records_equal_host=bool(same), records_that_differ=differ),
             dict(form="heaac_heaac_parse_batch + H2D", corpus=corpus, units=n, threads=a.threads, rounds=a.rounds,
                  parse_ms=sp(host_ms), h2d_records_ms=sp(host_h2d), total_ms=sp([x + y for x, y in zip(host_ms, host_h2d)]),
                  link_bytes_per_unit=rec, units_per_s=round(n / ((np.median(host_ms) + np.median(host_h2d)) * 1e-3))),

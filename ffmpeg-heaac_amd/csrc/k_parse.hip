@@ -8,7 +8,9 @@
 // records are zeroed ahead of the walk by a fill kernel of the same call (every lane of the grid, 16-byte stores): a
 // kernel and not hipMemsetAsync (its graph node left the records unzeroed on replay with ROCm 7.0's runtime).
 //
-// The same walk is instantiated for the host as heaac_debug_aac_parse_core (include/heaac_debug.h).
+// The same walk is instantiated for the host as heaac_debug_aac_parse_core (include/heaac_debug.h).  parse_core.h is the
+// one writing of the element syntax: the host parser (aac_parse.c) reads through the same pc_* functions with a PcHost
+// record for its statuses, refusal progress and pulse data; the walk passes NULL and defers every such unit.
 //
 // heaac_sbr_parse_device: the payload walk of sbr_core.h in the same layout (k_sbr_parse, one lane per unit, the 3.4 KB
 // of code-book nodes in LDS).  sbr_core.h is the one writing of the payload syntax: the host parser (sbr_parse.c) reads

@@ -1,9 +1,8 @@
-/* parse_tables.c -- the tables of the access-unit walk of parse_core.h, built on the host with the expressions
- * aac_parse.c builds its own with (same compiler, same flags, same libm), so that the device walk's dequantisation
- * is a look-up times the scalefactor and nothing of it is computed on the device:
+/* parse_tables.c -- the tables of the AAC parsers (parse_core.h), built once on the host; the device gets a copy, so
+ * that dequantisation is a look-up times the scalefactor wherever it runs and nothing of it is computed on the device:
  *   lut / node   the code trees of parse_bits.h (book 0 = scalefactors, 1..11 = the spectral books)
- *   pow2sf       g_pow2sf: 2^((i - 200) / 4)
- *   mag          g_mag: q^(4/3), q < 16
+ *   pow2sf       ff_aac_pow2sf_tab: 2^((i - 200) / 4) (aac_tablegen.h)
+ *   mag          q^(4/3), q < 16 (aactab.c: codebook vector values)
  *   esc          cbrtf((float)q) * (float)q, q < 8192: every value an escape sequence of at most 8 ones can carry
  *   band tables, aac_tns_map
  */
@@ -57,6 +56,16 @@ static void pt_init(void)
 const HeaacParseTables *heaac_parse_tables(void)
 {
     pthread_once(&g_pt_once, pt_init);
-    (void)bits_init;                                   /* parse_bits.h's non-inline static, unused here: no warning */
     return g_pt_bad ? NULL : &g_pt;
+}
+
+uint64_t heaac_aac_tables_fingerprint(void)
+{
+    uint64_t h = 1469598103934665603ull;
+#define MIX(arr) do { const uint8_t *p_ = (const uint8_t *)(arr); for (size_t i_ = 0; i_ < sizeof(arr); i_++) { h ^= p_[i_]; h *= 1099511628211ull; } } while (0)
+    MIX(aac_sf_code); MIX(aac_sf_bits); MIX(aac_spec_first); MIX(aac_spec_code); MIX(aac_spec_bits);
+    MIX(aac_num_swb_1024); MIX(aac_num_swb_128); MIX(aac_pred_sfb_max); MIX(aac_tns_max_bands_1024);
+    MIX(aac_tns_max_bands_128); MIX(aac_swb_offset_1024); MIX(aac_swb_offset_128); MIX(aac_tns_map);
+#undef MIX
+    return h;
 }

@@ -72,7 +72,6 @@ static void st_init(void)
 const HeaacSbrParseTables *heaac_sbr_parse_tables(void)
 {
     pthread_once(&g_st_once, st_init);
-    (void)bits_init;                                   /* parse_bits.h's non-inline static, unused here: no warning */
     return g_st_bad ? NULL : &g_st;
 }
 

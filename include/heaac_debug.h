@@ -30,7 +30,8 @@ int heaac_debug_workspace(HeaacDevice *dev, float **d_W, float **d_X, size_t *ch
 int heaac_debug_xbands(HeaacDevice *dev, unsigned char *host_out, size_t n_frames);
 
 /* The access-unit walk of heaac_aac_parse_device (csrc/parse_core.h) instantiated for the host: the same arguments
- * with host pointers, a plain loop over the n units, no device.  This is where the walk is compared with
+ * with host pointers, a plain loop over the n units, no device.  The host parser reads the element syntax through the
+ * same readers of csrc/parse_core.h; this is where the walk's deferrals and its commit-on-OK are compared with
  * heaac_aac_parse_frame_ex unit by unit, fuzzed and run under sanitizers, and where a kernel fault is debugged.
  * `why` (may be NULL) receives per unit 0 for HEAAC_PARSE_OK, or why the unit was deferred: 1 pulse data, 2 a CCE /
  * PCE / LFE or a second SCE / CPE, 4 a check of the host parser it does not pass. */

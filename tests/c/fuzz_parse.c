@@ -1,6 +1,6 @@
 /* fuzz_parse.c -- the host parsers under AddressSanitizer / UBSan on mutated access units (TEST harness).
  *
- * Built by tests/test_parse_fuzz.py from the parser SOURCES (aac_parse.c, sbr_parse.c, sbr_header.c) with
+ * Built by tests/test_parse_fuzz.py from the parser SOURCES (aac_parse.c, parse_tables.c, sbr_parse.c, sbr_header.c) with
  * -fsanitize=address,undefined, so every out-of-bounds access or undefined shift aborts the run.  Input: a file
  * of seed access units (u32 kind, u32 length, bytes; kind 0 = AAC-LC CPE 48 kHz, 1 = HE-AACv1 CPE 24 kHz,
  * 2 = HE-AACv2 SCE 24 kHz, 3 = AAC-LC CPE 48 kHz with coupling / program config elements, 4 = the same around an SCE:

@@ -1,5 +1,6 @@
 /* fuzz_parse_core.c -- the access-unit walk of heaac_aac_parse_device (csrc/parse_core.h) next to the host parser on
- * damaged input, built with AddressSanitizer + UBSan by tests/test_parse_core.py.
+ * damaged input, built with AddressSanitizer + UBSan by tests/test_parse_core.py.  Both go through the pc_* readers of
+ * parse_core.h: the walk without a PcHost record (defer mode), the host parser with one (refuse mode).
  *
  *   fuzz_parse_core <seeds> <iterations>
  *

@@ -1,6 +1,11 @@
 """The access-unit walk of heaac_aac_parse_device on the host (csrc/parse_core.h through heaac_debug_aac_parse_core)
 against the host parser heaac_aac_parse_frame_ex, unit by unit: what it takes comes back byte for byte, what it does
-not take is deferred with the stream state untouched, and it never says OK where the host parser refuses."""
+not take is deferred with the stream state untouched, and it never says OK where the host parser refuses.
+
+Both read the element syntax through the same pc_* readers of csrc/parse_core.h, so this is not one writing of the
+syntax checked by another: it pins the walk's defer mode (no PcHost record, every failure gives the unit up, the
+state committed on OK only) against the host's refuse mode of the same readers, the element loop pc_walk against
+frame_walk, and the bounds.  The independent statement of the values is the bit writer (test_parse.py)."""
 import os
 import struct
 import subprocess

@@ -1,6 +1,10 @@
 """heaac_aac_parse_device on the GPU against the host parser heaac_aac_parse_frame_ex: the corpora and the assertions of
 test_parse_core.py through the kernel (one lane per unit), every output pre-filled with a NaN pattern on both sides,
-the composed chain bytes -> parse -> tools -> decode against the oracle, and the call captured into a graph."""
+the composed chain bytes -> parse -> tools -> decode against the oracle, and the call captured into a graph.
+
+Kernel and host parser read the element syntax through the same pc_* readers of csrc/parse_core.h: what is pinned
+here is the device against the host (the compiler's device code, the LDS copy of the prefix tables, the fill kernel,
+the defer mode against the host's refuse mode), not one writing of the syntax against another."""
 import numpy as np
 import pytest
 

@@ -17,8 +17,9 @@ KIND = {"lc_stereo_48k": 0, "hev1_stereo_24k": 1, "hev2_mono_24k": 2, "hev2_impl
 def test_parsers_survive_damaged_access_units():
     os.makedirs(BUILD, exist_ok=True)
     srcs = [os.path.join(ROOT, "tests", "c", "fuzz_parse.c")] + [os.path.join(CSRC, f) for f in
-                                                                ("aac_parse.c", "sbr_parse.c", "sbr_header.c", "adts_split.c")]
-    if not os.path.exists(EXE) or os.path.getmtime(EXE) < max(os.path.getmtime(s) for s in srcs):
+                                                                ("aac_parse.c", "parse_tables.c", "sbr_parse.c", "sbr_header.c", "adts_split.c")]
+    deps = srcs + [os.path.join(CSRC, f) for f in ("parse_core.h", "sbr_core.h")]
+    if not os.path.exists(EXE) or os.path.getmtime(EXE) < max(os.path.getmtime(s) for s in deps):
         subprocess.check_call(["gcc", "-std=gnu99", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
                                "-ffp-contract=off", "-I", os.path.join(ROOT, "include"), "-I", CSRC] + srcs +
                               ["-o", EXE, "-lm", "-lpthread"])

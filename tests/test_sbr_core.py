@@ -224,7 +224,7 @@ def test_walk_under_sanitizers_with_every_unit_at_the_end_of_its_buffer(pkg):
     os.makedirs(BUILD, exist_ok=True)
     exe = os.path.join(BUILD, "fuzz_sbr_core")
     srcs = [os.path.join(ROOT, "tests", "c", "fuzz_sbr_core.c")] + [os.path.join(CSRC, f) for f in (
-        "sbr_parse.c", "sbr_header.c", "aac_parse.c")]
+        "sbr_parse.c", "sbr_header.c", "aac_parse.c", "parse_tables.c")]
     deps = srcs + [os.path.join(CSRC, "sbr_core.h"), os.path.join(CSRC, "parse_core.h")]
     if not os.path.exists(exe) or os.path.getmtime(exe) < max(os.path.getmtime(s) for s in deps):
         subprocess.check_call(["gcc", "-std=gnu99", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",

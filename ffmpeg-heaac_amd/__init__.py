@@ -141,6 +141,8 @@ EXPORTED = [
     "heaac_sbr_stream_init", "heaac_sbr_stream_bytes", "heaac_sbr_parse_payload", "heaac_sbr_no_payload",
     "heaac_heaac_parse_frame", "heaac_heaac_parse_batch", "heaac_sbr_tables_fingerprint",
     "heaac_sbr_parse_device", "heaac_heaac_parse_device", "heaac_debug_sbr_parse_core",
+    "heaac_aac_parse_device_streams", "heaac_heaac_parse_device_streams", "heaac_debug_aac_parse_core_streams",
+    "heaac_debug_heaac_parse_core_streams",
 ]
 
 
@@ -179,12 +181,12 @@ KERNEL_SOURCE_EXTRA = ("kernels.h", "tables.h", "validate.h")
 def kernel_source_files():
     """The device sources of the kernels bench.py's workloads launch, relative to the repository root: csrc/k_*.hip,
     csrc/k_*.h, kernels.h, tables.h, validate.h and the record header include/heaac_dsp.h -- without k_tools.hip (the
-    spectral tools: no bench workload runs them; tools/tools_rate.py measures them by themselves) and k_parse.hip (the
-    device parser: tools/parse_rate.py --device)."""
+    spectral tools: no bench workload runs them; tools/tools_rate.py measures them by themselves), k_parse.hip and
+    k_parse_streams.hip (the device parsers: tools/parse_rate.py --device)."""
     import glob
     d = os.path.join(_HERE, "csrc")
     files = sorted(f for f in glob.glob(os.path.join(d, "k_*.hip")) + glob.glob(os.path.join(d, "k_*.h"))
-                   if os.path.basename(f) not in ("k_tools.hip", "k_parse.hip"))
+                   if os.path.basename(f) not in ("k_tools.hip", "k_parse.hip", "k_parse_streams.hip"))
     files += [os.path.join(d, f) for f in KERNEL_SOURCE_EXTRA]
     files.append(os.path.join(os.path.dirname(_HERE), "include", "heaac_dsp.h"))
     return [os.path.relpath(f, os.path.dirname(_HERE)) for f in files]
@@ -529,6 +531,88 @@ class Device:
                                               _ptr(info), _ptr(hdr), C.c_size_t(hdr.numel() // SBR_HDR_DT.itemsize), _ptr(sbr),
                                               _ptr(ps), _ptr(status), _stream()), "heaac_heaac_parse_device")
         return dict(coeffs=coeffs, ics=ics, tools=tools, info=info, status=status, sst=sst_out, sbr=sbr, ps=ps)
+
+    # -- T consecutive units per stream in one call --
+    def _parse_streams_args(self, streams, au_bytes, au_offset, T, cc, coeffs, ics, tools, info, status, taken, hold):
+        import torch
+        T = int(T)
+        assert T >= 1, "frames_per_stream"
+        assert isinstance(au_offset, torch.Tensor) and au_offset.dtype == torch.int32 and au_offset.numel() >= 1, "au_offset"
+        n = au_offset.numel() - 1
+        assert n % T == 0, "au_offset: S * T + 1 offsets"
+        S = n // T
+        assert cc in (1, 2), "coeff_channels"
+        assert au_bytes.dtype == torch.uint8, "au_bytes"
+        assert streams.dtype == torch.uint8 and streams.numel() == S * AAC_STREAM_DT.itemsize, "streams"
+        dv = au_bytes.device
+
+        def arr(a, dtype, count, name):
+            if a is None:
+                return torch.empty(count, dtype=dtype, device=dv)
+            assert a.dtype == dtype and a.numel() == count, name
+            return a
+        coeffs = arr(coeffs, torch.float32, n * cc * 1024, "coeffs").view(n, cc, 1024)
+        ics = arr(ics, torch.uint8, n * cc * ICS_DT.itemsize, "ics")
+        tools = arr(tools, torch.uint8, n * TOOLS_FRAME_DT.itemsize, "tools")
+        info = arr(info, torch.uint8, n * AAC_INFO_DT.itemsize, "info")
+        status = arr(status, torch.int32, n, "status")
+        taken = arr(taken, torch.int32, S, "taken")
+        hold = arr(hold, torch.uint8, n, "hold")
+        return S, T, n, dict(coeffs=coeffs, ics=ics, tools=tools, info=info, status=status, taken=taken, hold=hold)
+
+    def aac_parse_streams(self, cfg, streams, au_bytes, au_offset, frames_per_stream, coeff_channels=2, coeffs=None, ics=None,
+                          tools=None, info=None, status=None, taken=None, hold=None):
+        """heaac_aac_parse_device_streams: S streams x T = frames_per_stream consecutive units, unit t of stream s at
+        index s * T + t.  streams: uint8 tensor of S AAC_STREAM_DT records (updated in place: each stands as after the
+        last unit taken), au_offset: int32 device tensor of S * T + 1 offsets the caller vouches for (an empty unit
+        stops its stream).  Returns the dict of aac_parse with n = S * T, plus taken int32 [S] (units taken from the
+        head of each stream) and hold uint8 [S * T] (the mask of the *_streams_ex decode calls)."""
+        cc = int(coeff_channels)
+        S, T, n, out = self._parse_streams_args(streams, au_bytes, au_offset, frames_per_stream, cc, coeffs, ics, tools, info,
+                                                status, taken, hold)
+        _check(lib().heaac_aac_parse_device_streams(self._h, C.byref(cfg), _ptr(streams), _ptr(au_bytes), _ptr(au_offset),
+                                                    C.c_size_t(S), C.c_size_t(T), cc, _ptr(out["coeffs"]), _ptr(out["ics"]),
+                                                    _ptr(out["tools"]), _ptr(out["info"]), _ptr(out["status"]), _ptr(out["taken"]),
+                                                    _ptr(out["hold"]), _stream()), "heaac_aac_parse_device_streams")
+        return out
+
+    def heaac_parse_device_streams(self, cfg, streams, sst_in, au_bytes, au_offset, hdr, frames_per_stream, coeff_channels=2,
+                                   coeffs=None, ics=None, tools=None, info=None, sst_out=None, sbr=None, ps=None, status=None,
+                                   taken=None, hold=None):
+        """heaac_heaac_parse_device_streams: aac_parse_streams with the SBR / PS payload of every unit behind its AAC
+        half.  sst_in / sst_out: uint8 tensors of S HeaacSbrStream records (must not overlap; sst_out is allocated when
+        None), hdr: uint8 tensor of SBR_HDR_DT records.  Both states stand as after the last unit taken.  Returns the
+        dict of aac_parse_streams plus sst, sbr [S * T], ps [S * T] (None unless cfg.ps != 0 on a mono configuration)."""
+        cc = int(coeff_channels)
+        S, T, n, out = self._parse_streams_args(streams, au_bytes, au_offset, frames_per_stream, cc, coeffs, ics, tools, info,
+                                                status, taken, hold)
+        L = lib()
+        L.heaac_sbr_stream_bytes.restype = C.c_size_t
+        sb = int(L.heaac_sbr_stream_bytes())
+        import torch
+        assert sst_in.dtype == torch.uint8 and sst_in.numel() == S * sb, "sst_in"
+        if sst_out is None:
+            sst_out = torch.empty(S * sb, dtype=torch.uint8, device=au_bytes.device)
+        else:
+            assert sst_out.dtype == torch.uint8 and sst_out.numel() == S * sb, "sst_out"
+        assert hdr.dtype == torch.uint8 and hdr.numel() >= SBR_HDR_DT.itemsize and hdr.numel() % SBR_HDR_DT.itemsize == 0, "hdr"
+        if sbr is None:
+            sbr = torch.empty(n * SBR_FRAME_DT.itemsize, dtype=torch.uint8, device=au_bytes.device)
+        else:
+            assert sbr.dtype == torch.uint8 and sbr.numel() == n * SBR_FRAME_DT.itemsize, "sbr"
+        if ps is None:
+            if cfg.ps != 0 and cfg.chan_config == 1:
+                ps = torch.empty(n * PS_FRAME_DT.itemsize, dtype=torch.uint8, device=au_bytes.device)
+        else:
+            assert ps.dtype == torch.uint8 and ps.numel() == n * PS_FRAME_DT.itemsize, "ps"
+        _check(L.heaac_heaac_parse_device_streams(self._h, C.byref(cfg), _ptr(streams), _ptr(sst_in), _ptr(sst_out), _ptr(au_bytes),
+                                                  _ptr(au_offset), C.c_size_t(S), C.c_size_t(T), cc, _ptr(out["coeffs"]),
+                                                  _ptr(out["ics"]), _ptr(out["tools"]), _ptr(out["info"]), _ptr(hdr),
+                                                  C.c_size_t(hdr.numel() // SBR_HDR_DT.itemsize), _ptr(sbr), _ptr(ps),
+                                                  _ptr(out["status"]), _ptr(out["taken"]), _ptr(out["hold"]), _stream()),
+               "heaac_heaac_parse_device_streams")
+        out.update(sst=sst_out, sbr=sbr, ps=ps)
+        return out
 
     # -- spectral tools before the IMDCT (M/S, intensity stereo, TNS), in place --
     def spectral_tools(self, channels, coeffs, tools, rng=None, pred=None):
@@ -1101,6 +1185,53 @@ def sbr_parse_core(cfg, sst_in, aus, info, hdr, aac_status=None, with_ps=True, o
                                           C.c_size_t(n), p(hdr), C.c_size_t(hdr.shape[0]), p(out["sbr"]), p(out.get("ps")),
                                           p(out["status"]), p(out["why"]))
     _check(rc, "heaac_debug_sbr_parse_core")
+    return out
+
+
+PARSE_WHY_SBR, PARSE_WHY_STOPPED = 256, 1 << 20
+
+
+def parse_core_streams(cfg, streams, aus, frames_per_stream, coeff_channels=2, sst_in=None, hdr=None, with_ps=True, out=None):
+    """heaac_debug_aac_parse_core_streams, or with sst_in (sbr_streams(S) rows, left alone) and hdr (SBR_HDR_DT
+    records) heaac_debug_heaac_parse_core_streams (include/heaac_debug.h): the chains of the device streams parsers on
+    the host.  aus: S * T access units, unit t of stream s at s * T + t (b"" stops its stream); streams: AAC_STREAM_DT
+    [S], updated in place.  Returns dict(coeffs, ics, tools, info, status [S * T], taken [S], hold [S * T], why [S * T])
+    plus sst [S][bytes], sbr, ps for HE.  `out`: a dict of pre-filled arrays to write into."""
+    T = int(frames_per_stream)
+    n = len(aus)
+    S = n // T
+    assert S * T == n and streams.dtype == AAC_STREAM_DT and streams.shape == (S,)
+    he = sst_in is not None
+    buf, off = pack_units(aus)
+    off = off.astype(np.uint32)
+    keep = np.concatenate([buf, np.zeros(1, np.uint8)])
+    out = dict(out) if out is not None else {}
+    out.setdefault("coeffs", np.zeros((n, coeff_channels, 1024), np.float32))
+    out.setdefault("ics", np.zeros((n, coeff_channels), ICS_DT))
+    out.setdefault("tools", np.zeros(n, TOOLS_FRAME_DT))
+    out.setdefault("info", np.zeros(n, AAC_INFO_DT))
+    out.setdefault("status", np.zeros(n, np.int32))
+    out.setdefault("taken", np.zeros(S, np.uint32))
+    out.setdefault("hold", np.zeros(n, np.uint8))
+    out.setdefault("why", np.zeros(n, np.int32))
+    p = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None
+    if not he:
+        rc = lib().heaac_debug_aac_parse_core_streams(C.byref(cfg), p(streams), p(keep), p(off), C.c_size_t(S), C.c_size_t(T),
+                                                      C.c_int(coeff_channels), p(out["coeffs"]), p(out["ics"]), p(out["tools"]),
+                                                      p(out["info"]), p(out["status"]), p(out["taken"]), p(out["hold"]), p(out["why"]))
+        _check(rc, "heaac_debug_aac_parse_core_streams")
+        return out
+    sst_in = np.ascontiguousarray(sst_in)
+    hdr = np.ascontiguousarray(hdr, dtype=SBR_HDR_DT).reshape(-1)
+    assert sst_in.dtype == np.uint8 and sst_in.shape[0] == S
+    out.setdefault("sst", np.zeros_like(sst_in))
+    out.setdefault("sbr", np.zeros(n, SBR_FRAME_DT))
+    out.setdefault("ps", np.zeros(n, PS_FRAME_DT) if with_ps else None)
+    rc = lib().heaac_debug_heaac_parse_core_streams(C.byref(cfg), p(streams), p(sst_in), p(out["sst"]), p(keep), p(off), C.c_size_t(S),
+                                                    C.c_size_t(T), C.c_int(coeff_channels), p(out["coeffs"]), p(out["ics"]),
+                                                    p(out["tools"]), p(out["info"]), p(hdr), C.c_size_t(hdr.shape[0]), p(out["sbr"]),
+                                                    p(out["ps"]), p(out["status"]), p(out["taken"]), p(out["hold"]), p(out["why"]))
+    _check(rc, "heaac_debug_heaac_parse_core_streams")
     return out
 
 

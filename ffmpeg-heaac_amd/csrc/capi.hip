@@ -342,6 +342,44 @@ extern "C" int heaac_heaac_parse_device(HeaacDevice *dev, const HeaacAacConfig *
                                   d_status, stream);
 }
 
+extern "C" int heaac_aac_parse_device_streams(HeaacDevice *dev, const HeaacAacConfig *cfg, HeaacAacStream *d_st, const uint8_t *d_au,
+                                              const uint32_t *d_au_offset, size_t n_streams, size_t frames_per_stream,
+                                              int coeff_channels, float *d_coeffs, HeaacIcs *d_ics, HeaacToolsFrame *d_tools,
+                                              HeaacAacFrameInfo *d_info, int32_t *d_status, uint32_t *d_taken, uint8_t *d_hold,
+                                              void *stream)
+{
+    if (!dev || !heaac_parse_args_ok(cfg, coeff_channels) || frames_per_stream == 0)
+        return HEAAC_ERR_ARG;
+    if (n_streams == 0)
+        return HEAAC_OK;
+    if (!heaac_parse_streams_args_ok(cfg, 0, d_st, NULL, NULL, d_au, d_au_offset, n_streams, frames_per_stream, d_coeffs, d_ics,
+                                     d_tools, d_info, NULL, 0, NULL, NULL, d_status, d_taken))
+        return HEAAC_ERR_ARG;
+    return heaac_launch_parse_streams(dev->d_ptab, NULL, cfg, d_st, NULL, NULL, d_au, d_au_offset, n_streams, frames_per_stream,
+                                      coeff_channels, d_coeffs, d_ics, d_tools, d_info, NULL, 0, NULL, NULL, d_status, d_taken, d_hold,
+                                      (hipStream_t)stream);
+}
+
+extern "C" int heaac_heaac_parse_device_streams(HeaacDevice *dev, const HeaacAacConfig *cfg, HeaacAacStream *d_st,
+                                                const HeaacSbrStream *d_sst_in, HeaacSbrStream *d_sst_out, const uint8_t *d_au,
+                                                const uint32_t *d_au_offset, size_t n_streams, size_t frames_per_stream,
+                                                int coeff_channels, float *d_coeffs, HeaacIcs *d_ics, HeaacToolsFrame *d_tools,
+                                                HeaacAacFrameInfo *d_info, const HeaacSbrHeader *d_hdr, size_t n_hdr,
+                                                HeaacSbrFrame *d_sbr, HeaacPsFrame *d_ps, int32_t *d_status, uint32_t *d_taken,
+                                                uint8_t *d_hold, void *stream)
+{
+    if (!dev || !heaac_parse_args_ok(cfg, coeff_channels) || frames_per_stream == 0)
+        return HEAAC_ERR_ARG;
+    if (n_streams == 0)
+        return HEAAC_OK;
+    if (!heaac_parse_streams_args_ok(cfg, 1, d_st, d_sst_in, d_sst_out, d_au, d_au_offset, n_streams, frames_per_stream, d_coeffs,
+                                     d_ics, d_tools, d_info, d_hdr, n_hdr, d_sbr, d_ps, d_status, d_taken))
+        return HEAAC_ERR_ARG;
+    return heaac_launch_parse_streams(dev->d_ptab, dev->d_stab, cfg, d_st, d_sst_in, d_sst_out, d_au, d_au_offset, n_streams,
+                                      frames_per_stream, coeff_channels, d_coeffs, d_ics, d_tools, d_info, d_hdr, n_hdr, d_sbr, d_ps,
+                                      d_status, d_taken, d_hold, (hipStream_t)stream);
+}
+
 extern "C" int heaac_spectral_tools_batch(HeaacDevice *dev, int channels, float *d_coeffs,
                                           const HeaacToolsFrame *d_tools,
                                           const int32_t *d_rng_in, int32_t *d_rng_out,

@@ -102,4 +102,17 @@ int heaac_launch_sbr_parse(const struct HeaacSbrParseTables *d_tab, const struct
                            const uint32_t *d_au_offset, const struct HeaacAacFrameInfo *d_info, const int32_t *d_aac_status,
                            size_t n, const HeaacSbrHeader *d_hdr, size_t n_hdr, HeaacSbrFrame *d_sbr, HeaacPsFrame *d_ps,
                            int32_t *d_status, hipStream_t s);
+
+/* k_parse.hip: heaac_aac_parse_device_streams / heaac_heaac_parse_device_streams (csrc/parse_streams.h): S streams x T
+ * units, one lane per stream behind one prep kernel; d_stab == NULL launches the walk without its SBR half */
+int heaac_parse_streams_args_ok(const struct HeaacAacConfig *cfg, int he, const void *st, const void *sst_in, const void *sst_out,
+                                const void *au, const void *au_offset, size_t S, size_t T, const void *coeffs, const void *ics,
+                                const void *tools, const void *info, const void *hdr, size_t n_hdr, const void *sbr, const void *ps,
+                                const void *status, const void *taken);
+int heaac_launch_parse_streams(const struct HeaacParseTables *d_tab, const struct HeaacSbrParseTables *d_stab,
+                               const struct HeaacAacConfig *cfg, struct HeaacAacStream *d_st, const struct HeaacSbrStream *d_sst_in,
+                               struct HeaacSbrStream *d_sst_out, const uint8_t *d_au, const uint32_t *d_au_offset, size_t S, size_t T,
+                               int coeff_channels, float *d_coeffs, HeaacIcs *d_ics, HeaacToolsFrame *d_tools,
+                               struct HeaacAacFrameInfo *d_info, const HeaacSbrHeader *d_hdr, size_t n_hdr, HeaacSbrFrame *d_sbr,
+                               HeaacPsFrame *d_ps, int32_t *d_status, uint32_t *d_taken, uint8_t *d_hold, hipStream_t s);
 }

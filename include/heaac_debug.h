@@ -49,6 +49,22 @@ int heaac_debug_sbr_parse_core(const HeaacAacConfig *cfg, const HeaacSbrStream *
                                const int32_t *aac_status, size_t n, const HeaacSbrHeader *hdr, size_t n_hdr,
                                HeaacSbrFrame *sbr, HeaacPsFrame *ps, int32_t *status, int32_t *why);
 
+/* The chains of heaac_aac_parse_device_streams and heaac_heaac_parse_device_streams (csrc/parse_streams.h) instantiated
+ * for the host: the same arguments with host pointers, the same argument checks, a plain loop over the streams, no
+ * device.  `why` [S][T] (may be NULL) receives 0 for a unit that was taken; for the unit a stream stopped at the AAC
+ * walk's reason (1, 2, 4 as above) or 256 times the SBR walk's reason (1 .. 8 as above); 1 << 20 for the units behind
+ * it, which were not looked at. */
+int heaac_debug_aac_parse_core_streams(const HeaacAacConfig *cfg, HeaacAacStream *st, const uint8_t *au,
+                                       const uint32_t *au_offset, size_t n_streams, size_t frames_per_stream,
+                                       int coeff_channels, float *coeffs, HeaacIcs *ics, HeaacToolsFrame *tools,
+                                       HeaacAacFrameInfo *info, int32_t *status, uint32_t *taken, uint8_t *hold, int32_t *why);
+int heaac_debug_heaac_parse_core_streams(const HeaacAacConfig *cfg, HeaacAacStream *st, const HeaacSbrStream *sst_in,
+                                         HeaacSbrStream *sst_out, const uint8_t *au, const uint32_t *au_offset,
+                                         size_t n_streams, size_t frames_per_stream, int coeff_channels, float *coeffs,
+                                         HeaacIcs *ics, HeaacToolsFrame *tools, HeaacAacFrameInfo *info,
+                                         const HeaacSbrHeader *hdr, size_t n_hdr, HeaacSbrFrame *sbr, HeaacPsFrame *ps,
+                                         int32_t *status, uint32_t *taken, uint8_t *hold, int32_t *why);
+
 #ifdef __cplusplus
 }
 #endif

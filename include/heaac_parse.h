@@ -548,6 +548,51 @@ int heaac_heaac_parse_device(HeaacDevice *dev, const HeaacAacConfig *cfg /* host
                              const HeaacSbrHeader *d_hdr, size_t n_hdr, HeaacSbrFrame *d_sbr, HeaacPsFrame *d_ps,
                              int32_t *d_status, void *stream);
 
+/* ---- T consecutive units per stream in one call (csrc/parse_streams.h, csrc/k_parse_streams.hip) ----
+ * The streams form of heaac_aac_parse_device: n_streams streams x frames_per_stream (T) consecutive access units, unit t
+ * of stream s at index i = s * T + t everywhere, as in the decode streams calls (heaac_dsp.h).  The per-unit arrays are
+ * laid out as the one-unit call lays them out with n = S * T (d_au_offset [S * T + 1], d_coeffs [S * T][coeff_channels]
+ * [1024], d_ics, d_tools, d_info, d_status [S * T]); the state is per stream, d_st [S].
+ *
+ * A stream's units are walked in order, each from the state the one before left, up to t0 = d_taken[s]: the first unit
+ * heaac_aac_parse_device would return HEAAC_PARSE_DEFERRED for from that state, or T.  A unit with offset[i + 1] ==
+ * offset[i] is such a unit: pad a stream that has fewer than T units with empty units at its end.
+ *   t <  t0   d_status is HEAAC_PARSE_OK, the unit's records are byte for byte those of the one-unit call
+ *   t >= t0   d_status is HEAAC_PARSE_DEFERRED, the unit's records are unspecified
+ * d_st[s] stands exactly as after unit t0 - 1 (t0 = 0: as it was), so the host parser resumes at unit t0 from it.
+ * d_hold [S * T] (may be NULL) receives 0 for t < t0 and 1 otherwise: the mask of the *_streams_ex decode calls, with
+ * which the taken head of every stream is decoded with no host step in between.  d_status, d_taken and d_hold are
+ * written for every unit, those of a stopped stream included.
+ * Returns HEAAC_OK (n_streams = 0 included), or HEAAC_ERR_ARG before anything is launched for what
+ * heaac_aac_parse_device refuses, frames_per_stream == 0, a NULL or misaligned d_status / d_taken, or an S * T that
+ * overflows or lies beyond the grid (2^31 - 1 blocks of 64 streams) or the 32-bit unit index.  No allocation, no
+ * synchronisation, capturable into a graph (two kernels, in line: one zeroes the tools records, one walks), no use of
+ * the context's workspace.  T = 1 gives the one-unit call's bytes plus d_taken / d_hold. */
+int heaac_aac_parse_device_streams(HeaacDevice *dev, const HeaacAacConfig *cfg /* host */,
+                                   HeaacAacStream *d_st,                            /* [S] in / out */
+                                   const uint8_t *d_au, const uint32_t *d_au_offset /* [S*T + 1] */,
+                                   size_t n_streams, size_t frames_per_stream, int coeff_channels,
+                                   float *d_coeffs, HeaacIcs *d_ics, HeaacToolsFrame *d_tools, HeaacAacFrameInfo *d_info,
+                                   int32_t *d_status /* [S][T] */, uint32_t *d_taken /* [S] */, uint8_t *d_hold /* [S][T] or NULL */,
+                                   void *stream);
+
+/* The same for whole HE-AAC units: per unit the AAC walk and then the SBR / PS walk of heaac_sbr_parse_device on what it
+ * left, d_sbr / d_ps [S * T], the states d_st, d_sst_in, d_sst_out [S] (the two SBR arrays must not overlap).  t0 is the
+ * first unit EITHER half gives up, and both halves of the state stand as after unit t0 - 1: d_st[s] and d_sst_out[s]
+ * (t0 = 0: d_st[s] as it was, d_sst_out[s] == d_sst_in[s]).  This is stricter than heaac_heaac_parse_device, whose AAC
+ * state has moved on where only the SBR half deferred: here heaac_heaac_parse_frame_ex resumes at unit t0 from the two
+ * states as they are.  (The SBR row is walked in place; where the SBR half gives unit t0 up, the lane copies the in row
+ * again and walks the payloads of units 0 .. t0 - 1 a second time, once per stream and call at most.)
+ * Refused with HEAAC_ERR_ARG before any launch: what the AAC streams call and what heaac_sbr_parse_device refuse.  Two
+ * kernels, in line: one zeroes the records and copies the S state rows, one walks. */
+int heaac_heaac_parse_device_streams(HeaacDevice *dev, const HeaacAacConfig *cfg, HeaacAacStream *d_st /* [S] in / out */,
+                                     const HeaacSbrStream *d_sst_in, HeaacSbrStream *d_sst_out /* [S] each, must not overlap */,
+                                     const uint8_t *d_au, const uint32_t *d_au_offset, size_t n_streams, size_t frames_per_stream,
+                                     int coeff_channels, float *d_coeffs, HeaacIcs *d_ics, HeaacToolsFrame *d_tools,
+                                     HeaacAacFrameInfo *d_info, const HeaacSbrHeader *d_hdr, size_t n_hdr, HeaacSbrFrame *d_sbr,
+                                     HeaacPsFrame *d_ps /* [S][T] */, int32_t *d_status, uint32_t *d_taken, uint8_t *d_hold,
+                                     void *stream);
+
 /* FNV-1a of the generated SBR / PS Huffman tables (sbr_iso_tables.h). */
 uint64_t heaac_sbr_tables_fingerprint(void);
 

@@ -18,7 +18,16 @@
       heaac_heaac_parse_batch on 16 host threads plus the upload of all its records, the HeaacSbrFrame / HeaacPsFrame
       among them, A/B alternating in one process.  Two corpora from tests/sbr_bitwriter.py, one after the other: stereo
       (coupled and not) and mono + PS HE units, each stream in steady state -- its first header parsed on the host
-      ahead of the timing, the timed unit without a header change -- tiled to --units.  Two JSON lines per corpus."""
+      ahead of the timing, the timed unit without a header change -- tiled to --units.  Two JSON lines per corpus.
+
+  python tools/parse_rate.py --device [--he] --frames-per-stream T [--units 32768] [--distinct 128] [--rounds 12] [--out FILE.jsonl]
+      the streams call (heaac_aac_parse_device_streams, with --he heaac_heaac_parse_device_streams on a mono + PS and a
+      stereo corpus) against T chained one-unit calls over the same S = units / T streams, A/B alternating in one
+      process, warmed up at the timed shape, the bytes on the device ahead of the timing.  Every stream is in steady
+      state and in scope, so both forms take every unit.  The chained form's per-position outputs stay where its calls
+      leave them: the re-layout to [S][T] a caller of it still owes is NOT in its time.  Records and final states of
+      the two forms are compared byte for byte.  Two JSON lines per corpus: ms per form over the rounds, launches,
+      state-row bytes moved by construction, the deferred count, records_equal."""
 import importlib, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -253,8 +262,138 @@ def he_mode(argv):
                 f.write(json.dumps(l) + "\n")
 
 
+def streams_mode(argv):
+    import argparse, json
+    import torch
+    import parse_device_common as PC
+    import sbr_device_common as SD
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--device", action="store_true")
+    ap.add_argument("--he", action="store_true")
+    ap.add_argument("--frames-per-stream", type=int, required=True)
+    ap.add_argument("--units", type=int, default=32768)
+    ap.add_argument("--distinct", type=int, default=128)
+    ap.add_argument("--rounds", type=int, default=12)
+    ap.add_argument("--out", default="")
+    a = ap.parse_args(argv)
+    assert torch.cuda.is_available(), "parse_rate --device needs a GPU"
+    dev = pkg.Device()
+    T = a.frames_per_stream
+    S = a.units // T
+    n = S * T
+    d = min(a.distinct, S)
+    sp = lambda v: dict(median=round(float(np.median(v)), 3), min=round(float(min(v)), 3), max=round(float(max(v)), 3))
+    row = int(pkg.sbr_streams(1).shape[1])
+    lines = []
+    for corpus in (("mono_ps", "stereo") if a.he else ("aac_lc_stereo",)):
+        cpe = corpus != "mono_ps"
+        rng = np.random.default_rng(2026 + cpe + 10 * T)
+        if a.he:
+            cfg, cc, with_ps = SD.he_cfg(pkg, cpe), 2 if cpe else 1, not cpe
+            writers = SD.make_writers(pkg, d, cpe)
+            tab = pkg.SbrHeaderTable(256)
+            st0, sst0 = np.zeros(d, pkg.AAC_STREAM_DT), pkg.sbr_streams(d)
+            for _ in range(2):                                 # the first headers: the host's
+                first = pkg.heaac_parse_batch(cfg, st0, sst0, tab, SD.he_units(rng, writers, cpe), with_ps=with_ps)
+                assert first["failed"] == 0
+            rows = [SD.he_units(rng, writers, cpe) for _ in range(T)]
+            d_hdr = pkg.to_device(tab.headers())
+        else:
+            cfg, cc, with_ps = TP._cfg(pkg, 2, 3, 2), 2, False
+            rows = PC.in_scope_steps(rng, 3, 2, True, d, T, adts=0.0, sbr=0.0)
+            st0, sst0 = np.zeros(d, pkg.AAC_STREAM_DT), None
+        tile = np.arange(S) % d
+        mean_size = float(np.mean([len(u) for r in rows for u in r]))
+        # the bytes of both layouts on the device ahead of the timing: [S][T] for the streams call, [S] per position
+        def up(aus):
+            b, o = pkg.pack_units(aus)
+            return torch.from_numpy(np.concatenate([b, np.zeros(4, np.uint8)])).cuda(), torch.from_numpy(o.astype(np.int32)).cuda()
+        d_buf, d_off = up([rows[t][i] for i in tile for t in range(T)])
+        pos = [up([rows[t][i] for i in tile]) for t in range(T)]
+        d_st0 = pkg.to_device(st0[tile])
+        d_st = [torch.empty_like(d_st0) for _ in range(2)]
+        sizes_of = dict(coeffs=cc * 1024, ics=cc * pkg.ICS_DT.itemsize, tools=pkg.TOOLS_FRAME_DT.itemsize, info=pkg.AAC_INFO_DT.itemsize, status=1)
+        if a.he:
+            sizes_of.update(sbr=pkg.SBR_FRAME_DT.itemsize)
+            if with_ps:
+                sizes_of.update(ps=pkg.PS_FRAME_DT.itemsize)
+            d_sst0 = pkg.to_device(sst0[tile])
+            d_sst = [torch.empty_like(d_sst0) for _ in range(3)]       # streams out; the chained form's ping and pong
+        dt_of = dict(coeffs=torch.float32, status=torch.int32)
+        mk = lambda units: {k: torch.empty(units * v, dtype=dt_of.get(k, torch.uint8), device="cuda") for k, v in sizes_of.items()}
+        s_out = mk(n)
+        s_out.update(taken=torch.empty(S, dtype=torch.int32, device="cuda"), hold=torch.empty(n, dtype=torch.uint8, device="cuda"))
+        c_out = [mk(S) for _ in range(T)]
+        for t in list(s_out.values()) + [v for o in c_out for v in o.values()]:       # one fill on both sides
+            t.view(torch.uint8).fill_(0xA5)
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+
+        def streams_round():
+            d_st[0].copy_(d_st0)
+            torch.cuda.synchronize()
+            ev[0].record()
+            if a.he:
+                dev.heaac_parse_device_streams(cfg, d_st[0], d_sst0, d_buf, d_off, d_hdr, T, coeff_channels=cc, sst_out=d_sst[0], **s_out)
+            else:
+                dev.aac_parse_streams(cfg, d_st[0], d_buf, d_off, T, coeff_channels=cc, **s_out)
+            ev[1].record()
+            torch.cuda.synchronize()
+            return ev[0].elapsed_time(ev[1])
+
+        def chained_round():
+            d_st[1].copy_(d_st0)
+            torch.cuda.synchronize()
+            ev[0].record()
+            for t in range(T):
+                if a.he:
+                    dev.heaac_parse_device(cfg, d_st[1], d_sst0 if t == 0 else d_sst[1 + (t - 1) % 2], pos[t][0], pos[t][1], d_hdr,
+                                           coeff_channels=cc, sst_out=d_sst[1 + t % 2], **c_out[t])
+                else:
+                    dev.aac_parse(cfg, d_st[1], pos[t][0], pos[t][1], coeff_channels=cc, **c_out[t])
+            ev[1].record()
+            torch.cuda.synchronize()
+            return ev[0].elapsed_time(ev[1])
+
+        for _ in range(3):                                     # warm-up of both forms at the timed shape
+            streams_round(); chained_round()
+        deferred_s = int((T - s_out["taken"].cpu().numpy().astype(np.int64)).sum())
+        deferred_c = int(sum(o["status"].cpu().numpy().astype(bool).sum() for o in c_out))
+        differ = []
+        for k, size in sizes_of.items():
+            x = s_out[k].view(S, T, size)
+            if any(not torch.equal(x[:, t], c_out[t][k].view(S, size)) for t in range(T)):
+                differ.append(k)
+        if not torch.equal(d_st[0], d_st[1]):
+            differ.append("st")
+        if a.he and not torch.equal(d_sst[0], d_sst[1 + (T - 1) % 2]):
+            differ.append("sst")
+        if s_out["hold"].any():
+            differ.append("hold")
+        same = deferred_s == 0 and deferred_c == 0 and not differ
+        s_ms, c_ms = [], []
+        for _ in range(a.rounds):
+            s_ms.append(streams_round()); c_ms.append(chained_round())
+        common = dict(corpus=corpus, streams=S, frames_per_stream=T, units=n, distinct_streams=d, mean_unit_bytes=round(mean_size, 1),
+                      rounds=a.rounds)
+        name = "heaac_heaac_parse_device" if a.he else "heaac_aac_parse_device"
+        lines += [
+            dict(form=name + "_streams", **common, call_ms=sp(s_ms), units_per_s=round(n / (np.median(s_ms) * 1e-3)),
+                 launches=2, state_row_bytes_moved=4 * row * S if a.he else 0, deferred=deferred_s, records_equal=bool(same),
+                 records_that_differ=differ),
+            dict(form="%d x %s" % (T, name), **common, call_ms=sp(c_ms), units_per_s=round(n / (np.median(c_ms) * 1e-3)),
+                 launches=(4 if a.he else 2) * T, state_row_bytes_moved=4 * row * n if a.he else 0, deferred=deferred_c,
+                 relayout_to_S_T_in_time=False),
+        ]
+    for l in lines:
+        print(json.dumps(l))
+    if a.out:
+        with open(a.out, "a") as f:
+            for l in lines:
+                f.write(json.dumps(l) + "\n")
+
+
 if "--device" in sys.argv:
-    (he_mode if "--he" in sys.argv else device_mode)(sys.argv[1:])
+    (streams_mode if "--frames-per-stream" in sys.argv else he_mode if "--he" in sys.argv else device_mode)(sys.argv[1:])
     sys.exit(0)
 
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 512

@@ -286,6 +286,25 @@ def _stream():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
+def _out(a, dtype, shape, name, device):
+    """An output tensor of the device parsers: a new one of `shape` when the caller gave none, else the caller's, checked
+    (a wrong-length tensor would be a silent device out-of-bounds access; the assertion names the argument)."""
+    import torch
+    if a is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    assert a.dtype == dtype and a.numel() == int(np.prod(shape)), name
+    return a
+
+
+def _aac_out(n, cc, coeffs, ics, tools, info, device):
+    """The four record arrays of the AAC half for n units: (coeffs, ics, tools, info)."""
+    import torch
+    return (_out(coeffs, torch.float32, (n, cc, 1024), "coeffs", device),
+            _out(ics, torch.uint8, n * cc * ICS_DT.itemsize, "ics", device),
+            _out(tools, torch.uint8, n * TOOLS_FRAME_DT.itemsize, "tools", device),
+            _out(info, torch.uint8, n * AAC_INFO_DT.itemsize, "info", device))
+
+
 def to_device(a, device="cuda"):
     """numpy (possibly structured) array -> uint8/float32 torch tensor on the GPU."""
     import torch
@@ -425,56 +444,27 @@ class Device:
         assert au_bytes.dtype == torch.uint8, "au_bytes"
         assert streams.dtype == torch.uint8 and streams.numel() == n * AAC_STREAM_DT.itemsize, "streams"
         dv = au_bytes.device
-        if coeffs is None:
-            coeffs = torch.empty((n, cc, 1024), dtype=torch.float32, device=dv)
-        else:
-            assert coeffs.dtype == torch.float32 and coeffs.numel() == n * cc * 1024, "coeffs"
-        if ics is None:
-            ics = torch.empty(n * cc * ICS_DT.itemsize, dtype=torch.uint8, device=dv)
-        else:
-            assert ics.dtype == torch.uint8 and ics.numel() == n * cc * ICS_DT.itemsize, "ics"
-        if tools is None:
-            tools = torch.empty(n * TOOLS_FRAME_DT.itemsize, dtype=torch.uint8, device=dv)
-        else:
-            assert tools.dtype == torch.uint8 and tools.numel() == n * TOOLS_FRAME_DT.itemsize, "tools"
-        if info is None:
-            info = torch.empty(n * AAC_INFO_DT.itemsize, dtype=torch.uint8, device=dv)
-        else:
-            assert info.dtype == torch.uint8 and info.numel() == n * AAC_INFO_DT.itemsize, "info"
-        if status is None:
-            status = torch.empty(n, dtype=torch.int32, device=dv)
-        else:
-            assert status.dtype == torch.int32 and status.numel() == n, "status"
+        coeffs, ics, tools, info = _aac_out(n, cc, coeffs, ics, tools, info, dv)
+        status = _out(status, torch.int32, n, "status", dv)
         _check(lib().heaac_aac_parse_device(self._h, C.byref(cfg), _ptr(streams), _ptr(au_bytes), _ptr(d_off),
                                             C.c_size_t(n), cc, _ptr(coeffs), _ptr(ics), _ptr(tools), _ptr(info),
                                             _ptr(status), _stream()), "heaac_aac_parse_device")
         return dict(coeffs=coeffs, ics=ics, tools=tools, info=info, status=status)
 
     # -- the SBR / PS payloads of the same units -> the records of he_decode, on the device --
-    def _sbr_parse_args(self, cfg, sst_in, sst_out, n, hdr, sbr, ps, status, dv):
+    def _sbr_parse_args(self, cfg, sst_in, sst_out, rows, n, hdr, sbr, ps, status, dv):
+        """rows: the number of HeaacSbrStream records (one per unit, or one per stream); n: the number of units."""
         import torch
         L = lib()
         L.heaac_sbr_stream_bytes.restype = C.c_size_t
         sb = int(L.heaac_sbr_stream_bytes())
-        assert sst_in.dtype == torch.uint8 and sst_in.numel() == n * sb, "sst_in"
-        if sst_out is None:
-            sst_out = torch.empty(n * sb, dtype=torch.uint8, device=dv)
-        else:
-            assert sst_out.dtype == torch.uint8 and sst_out.numel() == n * sb, "sst_out"
+        assert sst_in.dtype == torch.uint8 and sst_in.numel() == rows * sb, "sst_in"
+        sst_out = _out(sst_out, torch.uint8, rows * sb, "sst_out", dv)
         assert hdr.dtype == torch.uint8 and hdr.numel() >= SBR_HDR_DT.itemsize and hdr.numel() % SBR_HDR_DT.itemsize == 0, "hdr"
-        if sbr is None:
-            sbr = torch.empty(n * SBR_FRAME_DT.itemsize, dtype=torch.uint8, device=dv)
-        else:
-            assert sbr.dtype == torch.uint8 and sbr.numel() == n * SBR_FRAME_DT.itemsize, "sbr"
-        if ps is None:
-            if cfg.ps != 0 and cfg.chan_config == 1:
-                ps = torch.empty(n * PS_FRAME_DT.itemsize, dtype=torch.uint8, device=dv)
-        else:
-            assert ps.dtype == torch.uint8 and ps.numel() == n * PS_FRAME_DT.itemsize, "ps"
-        if status is None:
-            status = torch.empty(n, dtype=torch.int32, device=dv)
-        else:
-            assert status.dtype == torch.int32 and status.numel() == n, "status"
+        sbr = _out(sbr, torch.uint8, n * SBR_FRAME_DT.itemsize, "sbr", dv)
+        if ps is not None or (cfg.ps != 0 and cfg.chan_config == 1):
+            ps = _out(ps, torch.uint8, n * PS_FRAME_DT.itemsize, "ps", dv)
+        status = _out(status, torch.int32, n, "status", dv)
         return sst_out, sbr, ps, status
 
     def sbr_parse_device(self, cfg, sst_in, au_bytes, au_offset, info, hdr, aac_status=None, sst_out=None, sbr=None,
@@ -489,7 +479,7 @@ class Device:
         assert au_bytes.dtype == torch.uint8, "au_bytes"
         assert info.dtype == torch.uint8 and info.numel() == n * AAC_INFO_DT.itemsize, "info"
         assert aac_status is None or (aac_status.dtype == torch.int32 and aac_status.numel() == n), "aac_status"
-        sst_out, sbr, ps, status = self._sbr_parse_args(cfg, sst_in, sst_out, n, hdr, sbr, ps, status, au_bytes.device)
+        sst_out, sbr, ps, status = self._sbr_parse_args(cfg, sst_in, sst_out, n, n, hdr, sbr, ps, status, au_bytes.device)
         _check(lib().heaac_sbr_parse_device(self._h, C.byref(cfg), _ptr(sst_in), _ptr(sst_out), _ptr(au_bytes), _ptr(au_offset),
                                             _ptr(info), _ptr(aac_status), C.c_size_t(n), _ptr(hdr),
                                             C.c_size_t(hdr.numel() // SBR_HDR_DT.itemsize), _ptr(sbr), _ptr(ps), _ptr(status),
@@ -509,23 +499,8 @@ class Device:
         assert au_bytes.dtype == torch.uint8, "au_bytes"
         assert streams.dtype == torch.uint8 and streams.numel() == n * AAC_STREAM_DT.itemsize, "streams"
         dv = au_bytes.device
-        if coeffs is None:
-            coeffs = torch.empty((n, cc, 1024), dtype=torch.float32, device=dv)
-        else:
-            assert coeffs.dtype == torch.float32 and coeffs.numel() == n * cc * 1024, "coeffs"
-        if ics is None:
-            ics = torch.empty(n * cc * ICS_DT.itemsize, dtype=torch.uint8, device=dv)
-        else:
-            assert ics.dtype == torch.uint8 and ics.numel() == n * cc * ICS_DT.itemsize, "ics"
-        if tools is None:
-            tools = torch.empty(n * TOOLS_FRAME_DT.itemsize, dtype=torch.uint8, device=dv)
-        else:
-            assert tools.dtype == torch.uint8 and tools.numel() == n * TOOLS_FRAME_DT.itemsize, "tools"
-        if info is None:
-            info = torch.empty(n * AAC_INFO_DT.itemsize, dtype=torch.uint8, device=dv)
-        else:
-            assert info.dtype == torch.uint8 and info.numel() == n * AAC_INFO_DT.itemsize, "info"
-        sst_out, sbr, ps, status = self._sbr_parse_args(cfg, sst_in, sst_out, n, hdr, sbr, ps, status, dv)
+        coeffs, ics, tools, info = _aac_out(n, cc, coeffs, ics, tools, info, dv)
+        sst_out, sbr, ps, status = self._sbr_parse_args(cfg, sst_in, sst_out, n, n, hdr, sbr, ps, status, dv)
         _check(lib().heaac_heaac_parse_device(self._h, C.byref(cfg), _ptr(streams), _ptr(sst_in), _ptr(sst_out), _ptr(au_bytes),
                                               _ptr(au_offset), C.c_size_t(n), cc, _ptr(coeffs), _ptr(ics), _ptr(tools),
                                               _ptr(info), _ptr(hdr), C.c_size_t(hdr.numel() // SBR_HDR_DT.itemsize), _ptr(sbr),
@@ -545,19 +520,11 @@ class Device:
         assert au_bytes.dtype == torch.uint8, "au_bytes"
         assert streams.dtype == torch.uint8 and streams.numel() == S * AAC_STREAM_DT.itemsize, "streams"
         dv = au_bytes.device
-
-        def arr(a, dtype, count, name):
-            if a is None:
-                return torch.empty(count, dtype=dtype, device=dv)
-            assert a.dtype == dtype and a.numel() == count, name
-            return a
-        coeffs = arr(coeffs, torch.float32, n * cc * 1024, "coeffs").view(n, cc, 1024)
-        ics = arr(ics, torch.uint8, n * cc * ICS_DT.itemsize, "ics")
-        tools = arr(tools, torch.uint8, n * TOOLS_FRAME_DT.itemsize, "tools")
-        info = arr(info, torch.uint8, n * AAC_INFO_DT.itemsize, "info")
-        status = arr(status, torch.int32, n, "status")
-        taken = arr(taken, torch.int32, S, "taken")
-        hold = arr(hold, torch.uint8, n, "hold")
+        coeffs, ics, tools, info = _aac_out(n, cc, coeffs, ics, tools, info, dv)
+        coeffs = coeffs.view(n, cc, 1024)
+        status = _out(status, torch.int32, n, "status", dv)
+        taken = _out(taken, torch.int32, S, "taken", dv)
+        hold = _out(hold, torch.uint8, n, "hold", dv)
         return S, T, n, dict(coeffs=coeffs, ics=ics, tools=tools, info=info, status=status, taken=taken, hold=hold)
 
     def aac_parse_streams(self, cfg, streams, au_bytes, au_offset, frames_per_stream, coeff_channels=2, coeffs=None, ics=None,
@@ -586,30 +553,13 @@ class Device:
         cc = int(coeff_channels)
         S, T, n, out = self._parse_streams_args(streams, au_bytes, au_offset, frames_per_stream, cc, coeffs, ics, tools, info,
                                                 status, taken, hold)
-        L = lib()
-        L.heaac_sbr_stream_bytes.restype = C.c_size_t
-        sb = int(L.heaac_sbr_stream_bytes())
-        import torch
-        assert sst_in.dtype == torch.uint8 and sst_in.numel() == S * sb, "sst_in"
-        if sst_out is None:
-            sst_out = torch.empty(S * sb, dtype=torch.uint8, device=au_bytes.device)
-        else:
-            assert sst_out.dtype == torch.uint8 and sst_out.numel() == S * sb, "sst_out"
-        assert hdr.dtype == torch.uint8 and hdr.numel() >= SBR_HDR_DT.itemsize and hdr.numel() % SBR_HDR_DT.itemsize == 0, "hdr"
-        if sbr is None:
-            sbr = torch.empty(n * SBR_FRAME_DT.itemsize, dtype=torch.uint8, device=au_bytes.device)
-        else:
-            assert sbr.dtype == torch.uint8 and sbr.numel() == n * SBR_FRAME_DT.itemsize, "sbr"
-        if ps is None:
-            if cfg.ps != 0 and cfg.chan_config == 1:
-                ps = torch.empty(n * PS_FRAME_DT.itemsize, dtype=torch.uint8, device=au_bytes.device)
-        else:
-            assert ps.dtype == torch.uint8 and ps.numel() == n * PS_FRAME_DT.itemsize, "ps"
-        _check(L.heaac_heaac_parse_device_streams(self._h, C.byref(cfg), _ptr(streams), _ptr(sst_in), _ptr(sst_out), _ptr(au_bytes),
-                                                  _ptr(au_offset), C.c_size_t(S), C.c_size_t(T), cc, _ptr(out["coeffs"]),
-                                                  _ptr(out["ics"]), _ptr(out["tools"]), _ptr(out["info"]), _ptr(hdr),
-                                                  C.c_size_t(hdr.numel() // SBR_HDR_DT.itemsize), _ptr(sbr), _ptr(ps),
-                                                  _ptr(out["status"]), _ptr(out["taken"]), _ptr(out["hold"]), _stream()),
+        # (the status went through _parse_streams_args)
+        sst_out, sbr, ps, _ = self._sbr_parse_args(cfg, sst_in, sst_out, S, n, hdr, sbr, ps, out["status"], au_bytes.device)
+        _check(lib().heaac_heaac_parse_device_streams(self._h, C.byref(cfg), _ptr(streams), _ptr(sst_in), _ptr(sst_out),
+                                                      _ptr(au_bytes), _ptr(au_offset), C.c_size_t(S), C.c_size_t(T), cc,
+                                                      _ptr(out["coeffs"]), _ptr(out["ics"]), _ptr(out["tools"]), _ptr(out["info"]),
+                                                      _ptr(hdr), C.c_size_t(hdr.numel() // SBR_HDR_DT.itemsize), _ptr(sbr), _ptr(ps),
+                                                      _ptr(out["status"]), _ptr(out["taken"]), _ptr(out["hold"]), _stream()),
                "heaac_heaac_parse_device_streams")
         out.update(sst=sst_out, sbr=sbr, ps=ps)
         return out

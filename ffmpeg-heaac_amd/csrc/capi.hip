@@ -12,6 +12,7 @@
 #include "heaac_parse.h"
 #include "parse_core.h"
 #include "sbr_core.h"
+#include "parse_streams.h"
 #include "tables.h"
 #include "kernels.h"
 #include "host_common.h"
@@ -298,8 +299,6 @@ extern "C" int heaac_aac_parse_device(HeaacDevice *dev, const HeaacAacConfig *cf
     return heaac_launch_aac_parse(dev->d_ptab, cfg, d_st, d_au, d_au_offset, n, coeff_channels, d_coeffs, d_ics, d_tools,
                                   d_info, d_status, (hipStream_t)stream);
 }
-
-#define PARSE_GRID_MAX (0x7fffffffull * 64)     // units: one lane each, 64 per block (k_parse.hip)
 
 extern "C" int heaac_sbr_parse_device(HeaacDevice *dev, const HeaacAacConfig *cfg, const HeaacSbrStream *d_sst_in,
                                       HeaacSbrStream *d_sst_out, const uint8_t *d_au, const uint32_t *d_au_offset,

@@ -80,7 +80,8 @@ int heaac_launch_spectral_tools_streams(int channels, float *d_coeffs, const Hea
 int heaac_launch_fft_calc(const float *d_tab, int nbits, float *d_z, size_t n, hipStream_t s);
 int heaac_launch_imdct_mirror(float *d_out, int n, size_t count, hipStream_t s);
 
-/* k_parse.hip: heaac_aac_parse_device (include/heaac_parse.h); d_tab = the device copy of heaac_parse_tables() */
+/* k_parse_streams.hip: heaac_aac_parse_device (include/heaac_parse.h), the streams launcher below with S = n, T = 1;
+ * d_tab = the device copy of heaac_parse_tables() */
 struct HeaacParseTables;
 struct HeaacAacConfig;
 struct HeaacAacStream;
@@ -103,8 +104,9 @@ int heaac_launch_sbr_parse(const struct HeaacSbrParseTables *d_tab, const struct
                            size_t n, const HeaacSbrHeader *d_hdr, size_t n_hdr, HeaacSbrFrame *d_sbr, HeaacPsFrame *d_ps,
                            int32_t *d_status, hipStream_t s);
 
-/* k_parse.hip: heaac_aac_parse_device_streams / heaac_heaac_parse_device_streams (csrc/parse_streams.h): S streams x T
- * units, one lane per stream behind one prep kernel; d_stab == NULL launches the walk without its SBR half */
+/* k_parse_streams.hip: heaac_aac_parse_device_streams / heaac_heaac_parse_device_streams (csrc/parse_streams.h): S
+ * streams x T units, one lane per stream behind the prep kernel; d_stab == NULL launches the walk without its SBR half;
+ * d_taken, d_hold may be NULL */
 int heaac_parse_streams_args_ok(const struct HeaacAacConfig *cfg, int he, const void *st, const void *sst_in, const void *sst_out,
                                 const void *au, const void *au_offset, size_t S, size_t T, const void *coeffs, const void *ics,
                                 const void *tools, const void *info, const void *hdr, size_t n_hdr, const void *sbr, const void *ps,

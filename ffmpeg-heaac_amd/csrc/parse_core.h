@@ -10,7 +10,7 @@
  * stays there.
  *
  * pc_walk is the element loop of heaac_aac_parse_device: one SCE or one CPE per unit, AAC-LC / AAC-Main, data stream
- * and fill elements skipped, an ADTS header in front.  k_parse.hip instantiates it one lane per unit, and for the host
+ * and fill elements skipped, an ADTS header in front.  k_parse_streams.hip instantiates it one lane per unit, and for the host
  * as heaac_debug_aac_parse_core (include/heaac_debug.h), where it is tested, fuzzed and debugged.  It passes NULL for
  * the PcHost record and never decides a refusal: wherever the host parser would return anything but HEAAC_PARSE_OK it
  * gives the unit up (a PC_WHY_* reason, status HEAAC_PARSE_DEFERRED) and the caller hands it to the host parser; so

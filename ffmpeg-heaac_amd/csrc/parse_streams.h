@@ -3,7 +3,8 @@
  * sc_walk (sbr_core.h), each from the state the one before left, up to the first unit that is given up.  Written once
  * for the host and the device: k_parse_streams.hip instantiates pss_stream one lane per stream (k_parse_streams) and, through
  * pss_host, as heaac_debug_aac_parse_core_streams / heaac_debug_heaac_parse_core_streams (include/heaac_debug.h), where
- * it is tested, fuzzed (tests/c/fuzz_parse_streams.c) and debugged.  Nothing of the syntax stands here.
+ * it is tested, fuzzed (tests/c/fuzz_parse_streams.c) and debugged.  The one-unit call heaac_aac_parse_device and its
+ * host form heaac_debug_aac_parse_core are the AAC chain at T = 1, one stream per unit.  Nothing of the syntax stands here.
  *
  * Stop rule.  t0 = the first unit either walk gives up from the state units 0 .. t0 - 1 left (an empty unit is one), or
  * T.  Units below t0 are HEAAC_PARSE_OK with the records of the one-unit calls; from t0 on the status is
@@ -32,7 +33,11 @@
 #include "parse_core.h"
 #include "sbr_core.h"
 
-#define PSS_MAX_UNIT (1u << 27)       /* bytes: the walks count bits in an int */
+/* The geometry of every device parser (k_parse.hip, k_parse_streams.hip, the checks of capi.hip): one lane per unit or
+ * per stream, one wave per block */
+#define PARSE_BLOCK    64
+#define PARSE_GRID_MAX (0x7fffffffull * PARSE_BLOCK)   /* lanes of the largest grid */
+#define PARSE_MAX_UNIT (1u << 27)                      /* bytes: the walks count bits in an int */
 
 /* `why` of the host forms: 0 for a unit that was taken; for unit t0 the PC_WHY_* reason of the AAC half, or
  * PSS_WHY_SBR * the SC_WHY_* reason where the SBR half gave it up; PSS_WHY_STOPPED for the units behind t0, which were
@@ -42,7 +47,7 @@
 
 /* One stream.  he: 0 compiles the SBR half out (a constant at every call site).  st: the stream's AAC state; sst_in /
  * sst_out: its two SBR rows (he only; the OUT row holds the IN row); off: the stream's T + 1 offsets into au; the
- * record pointers are those of the stream's unit 0.  status [T], *taken; hold [T] and why [T] may be NULL. */
+ * record pointers are those of the stream's unit 0.  status [T]; taken, hold [T] and why [T] may be NULL. */
 SC_FN void pss_stream(const HeaacAacConfig *cfg, const HeaacParseTables *t, const uint32_t *lut, const HeaacSbrParseTables *stab,
                       const int he, HeaacAacStream *st, const HeaacSbrStream *sst_in, HeaacSbrStream *sst_out, const uint8_t *au,
                       const uint32_t *off, uint32_t T, int coeff_channels, float *coeffs, HeaacIcs *ics, HeaacToolsFrame *tools,
@@ -54,7 +59,7 @@ SC_FN void pss_stream(const HeaacAacConfig *cfg, const HeaacParseTables *t, cons
     while (u < end) {
         const uint32_t lo = off[u], hi = off[u + 1];
         int r = PC_WHY_REFUSED;
-        if (hi > lo && hi - lo < PSS_MAX_UNIT) {
+        if (hi > lo && hi - lo < PARSE_MAX_UNIT) {
             const uint8_t k0 = st->window_sequence[0], k1 = st->window_sequence[1], k2 = st->use_kb_window[0],
                           k3 = st->use_kb_window[1], k4 = st->mapped_tag, k5 = st->oc;
             r = again ? 0 : pc_walk(cfg, t, lut, st, au + lo, (int)(hi - lo), coeff_channels,
@@ -97,7 +102,7 @@ SC_FN void pss_stream(const HeaacAacConfig *cfg, const HeaacParseTables *t, cons
         if (hold) hold[u] = u >= t0;
         if (why) why[u] = u < t0 ? 0 : u == t0 ? reason : PSS_WHY_STOPPED;
     }
-    *taken = t0;
+    if (taken) *taken = t0;
 }
 
 /* The whole call on host memory: records zeroed, state rows copied, then stream by stream.  The arguments have passed
@@ -119,8 +124,18 @@ SC_FN void pss_host(const HeaacAacConfig *cfg, const HeaacParseTables *t, const 
         const size_t i = s * T;
         pss_stream(cfg, t, &t->lut[0][0], stab, he, st + s, he ? sst_in + s : NULL, he ? sst_out + s : NULL, au, off + i, T, coeff_channels,
                    coeffs + i * (size_t)coeff_channels * 1024, ics + i * (size_t)coeff_channels, tools + i, info + i, hdr, n_hdr,
-                   he ? sbr + i : NULL, he && ps ? ps + i : NULL, status + i, taken + s, hold ? hold + i : NULL, why ? why + i : NULL);
+                   he ? sbr + i : NULL, he && ps ? ps + i : NULL, status + i, taken ? taken + s : NULL, hold ? hold + i : NULL, why ? why + i : NULL);
     }
 }
+
+#ifdef __HIPCC__
+/* k_parse_streams.hip: the fill / copy kernel at the head of every device-parser call, on stream s.  tools, sbr and ps
+ * [0 .. their words) = 0, st_out [0 .. st_words) = st_in [..]; the arrays are 4-byte aligned, every count may be 0 (its
+ * pointers are then not looked at).  Internal to the library. */
+__attribute__((visibility("hidden"))) void heaac_launch_parse_prep(void *tools, unsigned long long tools_words, const void *st_in,
+                                                                   void *st_out, unsigned long long st_words, void *sbr,
+                                                                   unsigned long long sbr_words, void *ps,
+                                                                   unsigned long long ps_words, hipStream_t s);
+#endif
 
 #endif /* HEAAC_PARSE_STREAMS_H */

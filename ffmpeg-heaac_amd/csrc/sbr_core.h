@@ -22,7 +22,7 @@
  * works straight on the OUT row of the stream state, which the caller has filled with the IN row, and the caller copies
  * the row again when the unit is given up.  The records of such a unit are unspecified.
  *
- * The caller zeroes the unit's HeaacSbrFrame and HeaacPsFrame ahead of sc_emit_* (a memset on the host, k_sbr_prep on
+ * The caller zeroes the unit's HeaacSbrFrame and HeaacPsFrame ahead of sc_emit_* (a memset on the host, k_parse_prep on
  * the device).
  *
  * The code books are one flat table of tree nodes (HeaacSbrParseTables, 3.4 KB: on the device a copy in LDS), walked
@@ -76,7 +76,7 @@ enum { SC_T_ENV_15, SC_F_ENV_15, SC_T_ENV_BAL_15, SC_F_ENV_BAL_15, SC_T_ENV_30, 
 
 /* Rows are copied and cleared through the compiler's builtins, which it expands in line on the device and turns into
  * memcpy / memset on the host (byte loops cost the host parser a tenth of its time).  The functions of those names in
- * the HIP headers are not used: the compiler kept them as calls, and with them moved the code of k_aac_parse. */
+ * the HIP headers are not used: the compiler kept them as calls, and with them moved the code of the AAC walk kernel. */
 #define sc_copy(dst, src, n) __builtin_memcpy(dst, src, n)
 #define sc_zero(dst, n)      __builtin_memset(dst, 0, n)
 

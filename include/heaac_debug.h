@@ -30,11 +30,13 @@ int heaac_debug_workspace(HeaacDevice *dev, float **d_W, float **d_X, size_t *ch
 int heaac_debug_xbands(HeaacDevice *dev, unsigned char *host_out, size_t n_frames);
 
 /* The access-unit walk of heaac_aac_parse_device (csrc/parse_core.h) instantiated for the host: the same arguments
- * with host pointers, a plain loop over the n units, no device.  The host parser reads the element syntax through the
+ * with host pointers, no device.  It is the chain of the streams form below at T = 1, one stream per unit (its own
+ * argument checks, no `taken` / `hold`), as the device call is the streams kernel at T = 1.  The host parser reads the element syntax through the
  * same readers of csrc/parse_core.h; this is where the walk's deferrals and its commit-on-OK are compared with
  * heaac_aac_parse_frame_ex unit by unit, fuzzed and run under sanitizers, and where a kernel fault is debugged.
  * `why` (may be NULL) receives per unit 0 for HEAAC_PARSE_OK, or why the unit was deferred: 1 pulse data, 2 a CCE /
- * PCE / LFE or a second SCE / CPE, 4 a check of the host parser it does not pass. */
+ * PCE / LFE or a second SCE / CPE, 4 a check of the host parser it does not pass (at T = 1 the chain's reason is the
+ * walk's own; its "not looked at" value cannot occur). */
 int heaac_debug_aac_parse_core(const HeaacAacConfig *cfg, HeaacAacStream *st, const uint8_t *au,
                                const uint32_t *au_offset, size_t n, int coeff_channels, float *coeffs,
                                HeaacIcs *ics, HeaacToolsFrame *tools, HeaacAacFrameInfo *info, int32_t *status,

@@ -328,7 +328,7 @@ int heaac_aac_parse_batch(const HeaacAacConfig *cfg, HeaacAacStream *st,
                           float *coeffs, HeaacIcs *ics, HeaacToolsFrame *tools,
                           HeaacAacFrameInfo *info, int *status, int threads);
 
-/* ---- the same records from compressed units already in device memory (csrc/k_parse.hip, csrc/parse_core.h) ----
+/* ---- the same records from compressed units already in device memory (csrc/k_parse_streams.hip, csrc/parse_core.h) ----
  * n independent streams, one access unit each: unit i is d_au[d_au_offset[i] .. d_au_offset[i + 1]).  The outputs are
  * laid out as heaac_aac_parse_batch lays them out with coeff_channels (1 or 2, as heaac_aac_parse_frame_ex) as the
  * channel stride: d_coeffs [n][coeff_channels][1024], d_ics [n][coeff_channels], d_tools [n], d_info [n], d_status [n].
@@ -348,7 +348,8 @@ int heaac_aac_parse_batch(const HeaacAacConfig *cfg, HeaacAacStream *st,
  * Returns HEAAC_OK (0; n = 0 included), or HEAAC_ERR_ARG (heaac_dsp.h) before anything is launched for NULL pointers
  * with n > 0, coeff_channels outside 1 .. 2, cfg->sampling_index outside 0 .. 12 or an object type other than AAC-LC /
  * AAC-Main.  As the other batch calls: no allocation, no synchronisation, capturable into a graph (two kernels,
- * in line), no use of the context's workspace. */
+ * in line: one zeroes the tools records, one walks -- the kernels of heaac_aac_parse_device_streams at T = 1), no use of
+ * the context's workspace.  n may be anything up to the grid, 2^31 - 1 blocks of 64 units. */
 #define HEAAC_PARSE_DEFERRED 1      /* not parsed here: hand this unit to heaac_aac_parse_frame_ex on the host */
 int heaac_aac_parse_device(HeaacDevice *dev, const HeaacAacConfig *cfg /* host */,
                            HeaacAacStream *d_st,                 /* [n] in / out */
@@ -567,7 +568,8 @@ int heaac_heaac_parse_device(HeaacDevice *dev, const HeaacAacConfig *cfg /* host
  * heaac_aac_parse_device refuses, frames_per_stream == 0, a NULL or misaligned d_status / d_taken, or an S * T that
  * overflows or lies beyond the grid (2^31 - 1 blocks of 64 streams) or the 32-bit unit index.  No allocation, no
  * synchronisation, capturable into a graph (two kernels, in line: one zeroes the tools records, one walks), no use of
- * the context's workspace.  T = 1 gives the one-unit call's bytes plus d_taken / d_hold. */
+ * the context's workspace.  T = 1 gives the one-unit call's bytes plus d_taken / d_hold: the one-unit call is this
+ * call's walk kernel with T = 1 and neither array. */
 int heaac_aac_parse_device_streams(HeaacDevice *dev, const HeaacAacConfig *cfg /* host */,
                                    HeaacAacStream *d_st,                            /* [S] in / out */
                                    const uint8_t *d_au, const uint32_t *d_au_offset /* [S*T + 1] */,

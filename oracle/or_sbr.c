@@ -599,8 +599,12 @@ static void hf_assemble(const HeaacSbrHeader *h, const HeaacSbrFrame *fr, const 
             memcpy(q_temp[i + 2 * c->t_env[0]], s->q_m[0],  m_max * sizeof(s->q_m[0][0]));
         }
     } else if (h_SL) {
-        memcpy(g_temp[2 * c->t_env[0]], g_temp[2 * c->t_env_num_env_old], 4 * sizeof(g_temp[0]));
-        memcpy(q_temp[2 * c->t_env[0]], q_temp[2 * c->t_env_num_env_old], 4 * sizeof(q_temp[0]));
+        /* aacsbr.c:1638-1639 is a memcpy.  In a parsed stream the rows never overlap (t_env_num_env_old is 16..19, or 0
+         * on a frame that has reset set); a record may carry any t_env_num_env_old <= 19, and within one border of
+         * t_env[0] the reference's copy is undefined.  The rule here and in the kernels (k_hf.h seeds its ring from
+         * the four history rows as they arrived): the rows move as by memmove. */
+        memmove(g_temp[2 * c->t_env[0]], g_temp[2 * c->t_env_num_env_old], 4 * sizeof(g_temp[0]));
+        memmove(q_temp[2 * c->t_env[0]], q_temp[2 * c->t_env_num_env_old], 4 * sizeof(q_temp[0]));
     }
 
     for (e = 0; e < c->bs_num_env; e++)

@@ -16,6 +16,8 @@ import os
 
 import numpy as np
 
+from . import prototypes
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # HEAAC_LIB_PATH: measurement tooling (tools/abv.sh) points the binding at a variant build under ab/
 # without touching the product library; unset everywhere else.  Never silently: the override is announced on
@@ -108,42 +110,9 @@ assert CCE_LINK_DT.itemsize == 484 and CCE_FRAME_DT.itemsize == 2216
 assert SBR_HDR_DT.itemsize == 532 and SBR_CH_DT.itemsize == 336
 assert SBR_FRAME_DT.itemsize == 680 and PS_FRAME_DT.itemsize == 532
 
-# Every symbol include/*.h declares (checked by tests/test_abi.py).
-EXPORTED = [
-    # heaac_dsp.h
-    "heaac_device_create", "heaac_device_destroy", "heaac_device_workspace_bytes",
-    "heaac_strerror", "heaac_imdct_half_batch", "heaac_lc_decode_batch", "heaac_lc_decode_streams",
-    "heaac_lc_decode_streams_ex", "heaac_he_decode_streams_ex", "heaac_spectral_tools_streams_ex",
-    "heaac_he_decode_batch", "heaac_he_decode_batch_ex", "heaac_he_decode_streams", "heaac_qmf_analysis_batch", "heaac_qmf_synthesis_batch",
-    "heaac_qmf_synthesis_ds_batch",
-    "heaac_sbr_make_header", "heaac_build_info", "heaac_spectral_tools_batch", "heaac_spectral_tools_streams",
-    "heaac_validate_frame", "heaac_he_check_batch", "heaac_couple_after_imdct_batch",
-    # heaac_fft.h
-    "ff_fft_init", "ff_fft_end", "ff_fft_permute", "ff_fft_calc",
-    "ff_mdct_init", "ff_mdct_end", "ff_imdct_half", "ff_imdct_calc",
-    "ff_kbd_window_init", "ff_sine_window_init", "ff_init_ff_sine_windows", "ff_sine_windows",
-    "av_mdct_init", "av_imdct_half", "av_imdct_calc", "av_mdct_calc", "av_mdct_end",
-    "av_fft_init", "av_fft_permute", "av_fft_calc", "av_fft_end",
-    # heaac_codec.h
-    "heaac_aac_decoder", "heaac_codec_open", "heaac_codec_decode", "heaac_codec_close",
-    # heaac_parse.h
-    "heaac_asc_parse", "heaac_ga_specific_config", "heaac_aac_parse_frame_ex", "heaac_pcm_interleave_batch", "heaac_aac_layout_default", "heaac_aac_layout_from_pce", "heaac_aac_layout_from_au", "heaac_asc_layout", "heaac_aac_parse_frame_layout", "heaac_aac_parse_frame_layout_ex", "heaac_spectral_tools_batch_ex", "heaac_codec_get_context_defaults", "heaac_adts_parse_header", "heaac_adts_probe", "heaac_adts_split",
-    "heaac_heaac_parse_frame_ex", "heaac_pipeline_create", "heaac_pipeline_destroy", "heaac_pipeline_submit",
-    "heaac_pipeline_collect", "heaac_pipeline_timing", "heaac_pipeline_create_streams", "heaac_pipeline_frames_per_tick",
-    "heaac_layout_pipeline_create", "heaac_layout_pipeline_destroy", "heaac_layout_pipeline_submit",
-    "heaac_layout_pipeline_collect", "heaac_layout_pipeline_channels",
-    # heaac_debug.h
-    "heaac_debug_workspace", "heaac_debug_xbands", "heaac_debug_aac_parse_core",
-    "heaac_multi_shard", "heaac_multi_create", "heaac_multi_destroy", "heaac_multi_devices", "heaac_multi_device",
-    "heaac_multi_stream", "heaac_multi_he_decode", "heaac_aac_parse_frame", "heaac_aac_parse_batch", "heaac_aac_parse_device",
-    "heaac_aac_tables_fingerprint",
-    "heaac_sbr_table_create", "heaac_sbr_table_destroy", "heaac_sbr_table_count", "heaac_sbr_table_data",
-    "heaac_sbr_stream_init", "heaac_sbr_stream_bytes", "heaac_sbr_parse_payload", "heaac_sbr_no_payload",
-    "heaac_heaac_parse_frame", "heaac_heaac_parse_batch", "heaac_sbr_tables_fingerprint",
-    "heaac_sbr_parse_device", "heaac_heaac_parse_device", "heaac_debug_sbr_parse_core",
-    "heaac_aac_parse_device_streams", "heaac_heaac_parse_device_streams", "heaac_debug_aac_parse_core_streams",
-    "heaac_debug_heaac_parse_core_streams",
-]
+# Every symbol include/*.h declares (checked by tests/test_abi.py): the functions, whose prototypes lib() applies, and
+# two data symbols.
+EXPORTED = list(prototypes.PROTOTYPES) + ["heaac_aac_decoder", "ff_sine_windows"]
 
 
 # heaac_dsp.h: first rule a record breaks
@@ -161,12 +130,9 @@ def validate_frame(cfg, sbr, hdr, ps=None):
     "NONE" if the frame is valid."""
     sbr = np.ascontiguousarray(sbr, dtype=SBR_FRAME_DT).reshape(-1)[:1]
     hdr = np.ascontiguousarray(hdr, dtype=SBR_HDR_DT).reshape(-1)
-    p = None
     if ps is not None:
         ps = np.ascontiguousarray(ps, dtype=PS_FRAME_DT).reshape(-1)[:1]
-        p = ps.ctypes.data_as(C.c_void_p)
-    r = lib().heaac_validate_frame(C.c_int(cfg), sbr.ctypes.data_as(C.c_void_p), hdr.ctypes.data_as(C.c_void_p),
-                                   C.c_size_t(hdr.shape[0]), p)
+    r = lib().heaac_validate_frame(cfg, _np(sbr), _np(hdr), hdr.shape[0], _np(ps))
     if r < 0:
         raise HeaacError("heaac_validate_frame: bad call")
     return BAD_RULES[r]
@@ -232,10 +198,7 @@ def lib():
             print("ffmpeg-heaac_amd: HEAAC_LIB_PATH is set -- using %s instead of the product library" % LIB_PATH,
                   file=sys.stderr)
         _lib = C.CDLL(LIB_PATH)
-        _lib.heaac_strerror.restype = C.c_char_p
-        _lib.heaac_build_info.restype = C.c_char_p
-        _lib.heaac_device_workspace_bytes.restype = C.c_size_t
-        _lib.heaac_get_table.argtypes = [C.c_char_p, C.c_void_p, C.c_int]
+        prototypes.apply(_lib)
     return _lib
 
 
@@ -247,7 +210,7 @@ def _check(rc, what):
 def get_table(name, n=4096):
     """Host-built table by name (for table-parity tests; no GPU needed)."""
     buf = np.zeros(n, np.float32)
-    r = lib().heaac_get_table(name.encode(), buf.ctypes.data_as(C.c_void_p), n)
+    r = lib().heaac_get_table(name.encode(), _np(buf), n)
     if r < 0:
         raise KeyError(name)
     return buf[:r].copy()
@@ -258,12 +221,25 @@ def sbr_make_header(sample_rate=48000, start_freq=5, stop_freq=9, xover=0, freq_
                     interpol_freq=1, smoothing_mode=1, amp_res=1):
     """heaac_sbr_make_header(): SBR header -> band tables (host C, no GPU)."""
     h = np.zeros(1, SBR_HDR_DT)
-    rc = lib().heaac_sbr_make_header(h.ctypes.data_as(C.c_void_p), sample_rate, start_freq, stop_freq,
+    rc = lib().heaac_sbr_make_header(_np(h), sample_rate, start_freq, stop_freq,
                                      xover, freq_scale, alter_scale, noise_bands, limiter_bands,
                                      limiter_gains, interpol_freq, smoothing_mode, amp_res)
     if rc != 0:
         raise ValueError("invalid SBR header (%d)" % rc)
     return h
+
+
+def _np(a):
+    """Address of a numpy array (or None)."""
+    return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def _units(aus):
+    """A list of access units (bytes) -> (keep, ptrs, sizes): the buffers (to be held until the call has returned), the
+    c_char_p array of their addresses and the c_int array of their sizes."""
+    keep = [C.create_string_buffer(bytes(a), len(a)) for a in aus]
+    ptrs = (C.c_char_p * len(aus))(*[C.cast(k, C.c_char_p) for k in keep])
+    return keep, ptrs, (C.c_int * len(aus))(*[len(a) for a in aus])
 
 
 def _ptr(t):
@@ -296,6 +272,40 @@ def _out(a, dtype, shape, name, device):
     return a
 
 
+def _pcm(pcm, n, channels, length, pcm_format, device):
+    """The PCM tensor of a decode call over n frames: float32 [n][channels][length] for PCM_F32, else int16
+    [n][length][channels]; a new one when the caller gave none, else the caller's, checked."""
+    import torch
+    f32 = pcm_format == PCM_F32
+    dtype = torch.float32 if f32 else torch.int16
+    if pcm is None:
+        return torch.empty((n, channels, length) if f32 else (n, length, channels), dtype=dtype, device=device)
+    assert pcm.numel() == n * channels * length and pcm.dtype == dtype, "pcm"
+    return pcm
+
+
+def _state_out(state_out, state_in):
+    """The state_out tensor of a decode call: a new one like state_in when the caller gave none, else checked."""
+    import torch
+    if state_out is None:
+        return torch.empty_like(state_in)
+    assert state_out.dtype == torch.float32 and state_out.numel() == state_in.numel(), "state_out"
+    return state_out
+
+
+def _units_in(streams, au_bytes, au_offset, cc, T=1):
+    """The input checks of the device AAC parsers over S streams x T units (one unit per stream: T = 1): returns the
+    number of units, S * T."""
+    import torch
+    assert isinstance(au_offset, torch.Tensor) and au_offset.dtype == torch.int32 and au_offset.numel() >= 1, "au_offset"
+    n = au_offset.numel() - 1
+    assert n % T == 0, "au_offset: S * T + 1 offsets"
+    assert cc in (1, 2), "coeff_channels"
+    assert au_bytes.dtype == torch.uint8, "au_bytes"
+    assert streams.dtype == torch.uint8 and streams.numel() == n // T * AAC_STREAM_DT.itemsize, "streams"
+    return n
+
+
 def _aac_out(n, cc, coeffs, ics, tools, info, device):
     """The four record arrays of the AAC half for n units: (coeffs, ics, tools, info)."""
     import torch
@@ -322,7 +332,7 @@ class Device:
         if not torch.cuda.is_available():
             raise HeaacError("no HIP device visible: the HE-AAC DSP path has no CPU fallback")
         self._h = C.c_void_p()
-        _check(lib().heaac_device_create(C.byref(self._h), C.c_size_t(max_frames)), "heaac_device_create")
+        _check(lib().heaac_device_create(C.byref(self._h), max_frames), "heaac_device_create")
 
     def close(self):
         if self._h:
@@ -338,7 +348,7 @@ class Device:
     def x_bands(self, n):
         """include/heaac_debug.h: the X bands stored per (frame, channel) by the last HE decode call, uint8 [n][2]."""
         buf = np.zeros(2 * n, np.uint8)
-        _check(lib().heaac_debug_xbands(self._h, buf.ctypes.data_as(C.c_void_p), C.c_size_t(n)), "heaac_debug_xbands")
+        _check(lib().heaac_debug_xbands(self._h, _np(buf), n), "heaac_debug_xbands")
         return buf.reshape(n, 2)
 
     def x_bands_shares(self, n):
@@ -354,27 +364,28 @@ class Device:
         assert x.dtype == torch.float32 and x.shape[-1] == n_half
         x = x.contiguous()
         out = torch.empty_like(x)
-        _check(lib().heaac_imdct_half_batch(self._h, which, _ptr(out), _ptr(x),
-                                            C.c_size_t(x.numel() // n_half), _stream()),
+        _check(lib().heaac_imdct_half_batch(self._h, which, _ptr(out), _ptr(x), x.numel() // n_half, _stream()),
                "heaac_imdct_half_batch")
         return out
 
     # -- AAC-LC --
-    def lc_decode(self, channels, coeffs, ics, state_in, state_out=None, pcm=None, pcm_format=PCM_F32):
+    @staticmethod
+    def _lc_args(channels, coeffs, ics, state_in, S, T, state_out, pcm, pcm_format):
+        """The tensors of an LC decode call over S streams x T frames (lc_decode: S = n, T = 1), checked -- a
+        wrong-length tensor would be a silent device out-of-bounds access.  Returns (state_out, pcm), allocated where
+        the caller gave none."""
         import torch
+        n = S * T
+        assert state_in.dtype == torch.float32 and state_in.numel() == S * channels * 512, "state_in"
+        assert coeffs.dtype == torch.float32 and coeffs.numel() == n * channels * 1024, "coeffs"
+        assert ics.numel() * ics.element_size() == n * channels * ICS_DT.itemsize, "ics"
+        return _state_out(state_out, state_in), _pcm(pcm, n, channels, 1024, pcm_format, coeffs.device)
+
+    def lc_decode(self, channels, coeffs, ics, state_in, state_out=None, pcm=None, pcm_format=PCM_F32):
         n = coeffs.shape[0]
-        assert coeffs.dtype == torch.float32 and coeffs.numel() == n * channels * 1024
-        assert ics.numel() == n * channels * 4 and ics.dtype == torch.uint8
-        assert state_in.numel() == n * channels * 512
-        if state_out is None:
-            state_out = torch.empty_like(state_in)
-        if pcm is None:
-            if pcm_format == PCM_F32:
-                pcm = torch.empty((n, channels, 1024), dtype=torch.float32, device=coeffs.device)
-            else:
-                pcm = torch.empty((n, 1024, channels), dtype=torch.int16, device=coeffs.device)
+        state_out, pcm = self._lc_args(channels, coeffs, ics, state_in, n, 1, state_out, pcm, pcm_format)
         _check(lib().heaac_lc_decode_batch(self._h, channels, _ptr(coeffs), _ptr(ics), _ptr(state_in),
-                                           _ptr(state_out), _ptr(pcm), pcm_format, C.c_size_t(n), _stream()),
+                                           _ptr(state_out), _ptr(pcm), pcm_format, n, _stream()),
                "heaac_lc_decode_batch")
         return pcm, state_out
 
@@ -385,37 +396,17 @@ class Device:
         saved[] record of channels * 512 floats per stream (before frame 0 / after frame T - 1).  hold: None, or a
         uint8 tensor of S * T elements, non-zero = frame held (heaac_lc_decode_streams_ex: skipped, zero PCM, the
         stream's state passes over it).  Returns (pcm, state_out)."""
-        import torch
         T = int(frames_per_stream)
-        words = channels * 512
-        S = state_in.numel() // words
-        n = S * T
-        # a wrong-length tensor would be a silent device out-of-bounds access: check them all here
-        assert state_in.dtype == torch.float32 and state_in.numel() == S * words, "state_in"
-        assert coeffs.dtype == torch.float32 and coeffs.numel() == n * channels * 1024, "coeffs"
-        assert ics.numel() * ics.element_size() == n * channels * ICS_DT.itemsize, "ics"
-        if state_out is None:
-            state_out = torch.empty_like(state_in)
-        else:
-            assert state_out.dtype == torch.float32 and state_out.numel() == state_in.numel(), "state_out"
-        if pcm is None:
-            if pcm_format == PCM_F32:
-                pcm = torch.empty((n, channels, 1024), dtype=torch.float32, device=coeffs.device)
-            else:
-                pcm = torch.empty((n, 1024, channels), dtype=torch.int16, device=coeffs.device)
-        else:
-            assert pcm.numel() == n * channels * 1024 and \
-                pcm.dtype == (torch.float32 if pcm_format == PCM_F32 else torch.int16), "pcm"
+        S = state_in.numel() // (channels * 512)
+        state_out, pcm = self._lc_args(channels, coeffs, ics, state_in, S, T, state_out, pcm, pcm_format)
         if hold is None:
             _check(lib().heaac_lc_decode_streams(self._h, channels, _ptr(coeffs), _ptr(ics), _ptr(state_in),
-                                                 _ptr(state_out), _ptr(pcm), pcm_format, C.c_size_t(S), C.c_size_t(T),
-                                                 _stream()),
+                                                 _ptr(state_out), _ptr(pcm), pcm_format, S, T, _stream()),
                    "heaac_lc_decode_streams")
         else:
-            d_hold = _hold_ptr(hold, n)
+            d_hold = _hold_ptr(hold, S * T)
             _check(lib().heaac_lc_decode_streams_ex(self._h, channels, _ptr(coeffs), _ptr(ics), _ptr(state_in),
-                                                    _ptr(state_out), _ptr(pcm), pcm_format, C.c_size_t(S), C.c_size_t(T),
-                                                    d_hold, _stream()),
+                                                    _ptr(state_out), _ptr(pcm), pcm_format, S, T, d_hold, _stream()),
                    "heaac_lc_decode_streams_ex")
         return pcm, state_out
 
@@ -429,35 +420,28 @@ class Device:
         aac_parse_batch returns, as device tensors (coeffs float32 [n][coeff_channels][1024]; ics, tools, info as
         uint8 records), plus status int32 [n]: PARSE_OK or PARSE_DEFERRED (parse that unit on the host)."""
         import torch
-        if isinstance(au_offset, torch.Tensor):
-            assert au_offset.dtype == torch.int32 and au_offset.numel() >= 1, "au_offset"
-            d_off = au_offset
-        else:
+        d_off = au_offset
+        if not isinstance(au_offset, torch.Tensor):
             off = np.ascontiguousarray(au_offset, dtype=np.int64).reshape(-1)
             assert off.size >= 1 and off[0] >= 0 and (np.diff(off) >= 0).all() and off[-1] <= au_bytes.numel() and \
                 off[-1] < 2 ** 31, "au_offset"
             d_off = torch.from_numpy(off.astype(np.int32)).to(au_bytes.device)
-        n = d_off.numel() - 1
         cc = int(coeff_channels)
         # a wrong-length tensor would be a silent device out-of-bounds access: check them all here
-        assert cc in (1, 2), "coeff_channels"
-        assert au_bytes.dtype == torch.uint8, "au_bytes"
-        assert streams.dtype == torch.uint8 and streams.numel() == n * AAC_STREAM_DT.itemsize, "streams"
+        n = _units_in(streams, au_bytes, d_off, cc)
         dv = au_bytes.device
         coeffs, ics, tools, info = _aac_out(n, cc, coeffs, ics, tools, info, dv)
         status = _out(status, torch.int32, n, "status", dv)
-        _check(lib().heaac_aac_parse_device(self._h, C.byref(cfg), _ptr(streams), _ptr(au_bytes), _ptr(d_off),
-                                            C.c_size_t(n), cc, _ptr(coeffs), _ptr(ics), _ptr(tools), _ptr(info),
-                                            _ptr(status), _stream()), "heaac_aac_parse_device")
+        _check(lib().heaac_aac_parse_device(self._h, C.byref(cfg), _ptr(streams), _ptr(au_bytes), _ptr(d_off), n, cc,
+                                            _ptr(coeffs), _ptr(ics), _ptr(tools), _ptr(info), _ptr(status), _stream()),
+               "heaac_aac_parse_device")
         return dict(coeffs=coeffs, ics=ics, tools=tools, info=info, status=status)
 
     # -- the SBR / PS payloads of the same units -> the records of he_decode, on the device --
     def _sbr_parse_args(self, cfg, sst_in, sst_out, rows, n, hdr, sbr, ps, status, dv):
         """rows: the number of HeaacSbrStream records (one per unit, or one per stream); n: the number of units."""
         import torch
-        L = lib()
-        L.heaac_sbr_stream_bytes.restype = C.c_size_t
-        sb = int(L.heaac_sbr_stream_bytes())
+        sb = lib().heaac_sbr_stream_bytes()
         assert sst_in.dtype == torch.uint8 and sst_in.numel() == rows * sb, "sst_in"
         sst_out = _out(sst_out, torch.uint8, rows * sb, "sst_out", dv)
         assert hdr.dtype == torch.uint8 and hdr.numel() >= SBR_HDR_DT.itemsize and hdr.numel() % SBR_HDR_DT.itemsize == 0, "hdr"
@@ -481,9 +465,8 @@ class Device:
         assert aac_status is None or (aac_status.dtype == torch.int32 and aac_status.numel() == n), "aac_status"
         sst_out, sbr, ps, status = self._sbr_parse_args(cfg, sst_in, sst_out, n, n, hdr, sbr, ps, status, au_bytes.device)
         _check(lib().heaac_sbr_parse_device(self._h, C.byref(cfg), _ptr(sst_in), _ptr(sst_out), _ptr(au_bytes), _ptr(au_offset),
-                                            _ptr(info), _ptr(aac_status), C.c_size_t(n), _ptr(hdr),
-                                            C.c_size_t(hdr.numel() // SBR_HDR_DT.itemsize), _ptr(sbr), _ptr(ps), _ptr(status),
-                                            _stream()), "heaac_sbr_parse_device")
+                                            _ptr(info), _ptr(aac_status), n, _ptr(hdr), hdr.numel() // SBR_HDR_DT.itemsize,
+                                            _ptr(sbr), _ptr(ps), _ptr(status), _stream()), "heaac_sbr_parse_device")
         return dict(sst=sst_out, sbr=sbr, ps=ps, status=status)
 
     def heaac_parse_device(self, cfg, streams, sst_in, au_bytes, au_offset, hdr, coeff_channels=2, coeffs=None, ics=None,
@@ -491,19 +474,14 @@ class Device:
         """heaac_heaac_parse_device: aac_parse and sbr_parse_device as one call (one status per unit, PARSE_OK only
         where both halves took it).  au_offset: an int32 device tensor of n + 1 offsets the caller vouches for.
         Returns the dict of aac_parse plus sst, sbr, ps."""
-        import torch
-        assert isinstance(au_offset, torch.Tensor) and au_offset.dtype == torch.int32 and au_offset.numel() >= 1, "au_offset"
-        n = au_offset.numel() - 1
         cc = int(coeff_channels)
-        assert cc in (1, 2), "coeff_channels"
-        assert au_bytes.dtype == torch.uint8, "au_bytes"
-        assert streams.dtype == torch.uint8 and streams.numel() == n * AAC_STREAM_DT.itemsize, "streams"
+        n = _units_in(streams, au_bytes, au_offset, cc)
         dv = au_bytes.device
         coeffs, ics, tools, info = _aac_out(n, cc, coeffs, ics, tools, info, dv)
         sst_out, sbr, ps, status = self._sbr_parse_args(cfg, sst_in, sst_out, n, n, hdr, sbr, ps, status, dv)
         _check(lib().heaac_heaac_parse_device(self._h, C.byref(cfg), _ptr(streams), _ptr(sst_in), _ptr(sst_out), _ptr(au_bytes),
-                                              _ptr(au_offset), C.c_size_t(n), cc, _ptr(coeffs), _ptr(ics), _ptr(tools),
-                                              _ptr(info), _ptr(hdr), C.c_size_t(hdr.numel() // SBR_HDR_DT.itemsize), _ptr(sbr),
+                                              _ptr(au_offset), n, cc, _ptr(coeffs), _ptr(ics), _ptr(tools),
+                                              _ptr(info), _ptr(hdr), hdr.numel() // SBR_HDR_DT.itemsize, _ptr(sbr),
                                               _ptr(ps), _ptr(status), _stream()), "heaac_heaac_parse_device")
         return dict(coeffs=coeffs, ics=ics, tools=tools, info=info, status=status, sst=sst_out, sbr=sbr, ps=ps)
 
@@ -512,13 +490,8 @@ class Device:
         import torch
         T = int(T)
         assert T >= 1, "frames_per_stream"
-        assert isinstance(au_offset, torch.Tensor) and au_offset.dtype == torch.int32 and au_offset.numel() >= 1, "au_offset"
-        n = au_offset.numel() - 1
-        assert n % T == 0, "au_offset: S * T + 1 offsets"
+        n = _units_in(streams, au_bytes, au_offset, cc, T)
         S = n // T
-        assert cc in (1, 2), "coeff_channels"
-        assert au_bytes.dtype == torch.uint8, "au_bytes"
-        assert streams.dtype == torch.uint8 and streams.numel() == S * AAC_STREAM_DT.itemsize, "streams"
         dv = au_bytes.device
         coeffs, ics, tools, info = _aac_out(n, cc, coeffs, ics, tools, info, dv)
         coeffs = coeffs.view(n, cc, 1024)
@@ -538,9 +511,9 @@ class Device:
         S, T, n, out = self._parse_streams_args(streams, au_bytes, au_offset, frames_per_stream, cc, coeffs, ics, tools, info,
                                                 status, taken, hold)
         _check(lib().heaac_aac_parse_device_streams(self._h, C.byref(cfg), _ptr(streams), _ptr(au_bytes), _ptr(au_offset),
-                                                    C.c_size_t(S), C.c_size_t(T), cc, _ptr(out["coeffs"]), _ptr(out["ics"]),
-                                                    _ptr(out["tools"]), _ptr(out["info"]), _ptr(out["status"]), _ptr(out["taken"]),
-                                                    _ptr(out["hold"]), _stream()), "heaac_aac_parse_device_streams")
+                                                    S, T, cc, _ptr(out["coeffs"]), _ptr(out["ics"]), _ptr(out["tools"]),
+                                                    _ptr(out["info"]), _ptr(out["status"]), _ptr(out["taken"]), _ptr(out["hold"]),
+                                                    _stream()), "heaac_aac_parse_device_streams")
         return out
 
     def heaac_parse_device_streams(self, cfg, streams, sst_in, au_bytes, au_offset, hdr, frames_per_stream, coeff_channels=2,
@@ -556,9 +529,9 @@ class Device:
         # (the status went through _parse_streams_args)
         sst_out, sbr, ps, _ = self._sbr_parse_args(cfg, sst_in, sst_out, S, n, hdr, sbr, ps, out["status"], au_bytes.device)
         _check(lib().heaac_heaac_parse_device_streams(self._h, C.byref(cfg), _ptr(streams), _ptr(sst_in), _ptr(sst_out),
-                                                      _ptr(au_bytes), _ptr(au_offset), C.c_size_t(S), C.c_size_t(T), cc,
+                                                      _ptr(au_bytes), _ptr(au_offset), S, T, cc,
                                                       _ptr(out["coeffs"]), _ptr(out["ics"]), _ptr(out["tools"]), _ptr(out["info"]),
-                                                      _ptr(hdr), C.c_size_t(hdr.numel() // SBR_HDR_DT.itemsize), _ptr(sbr), _ptr(ps),
+                                                      _ptr(hdr), hdr.numel() // SBR_HDR_DT.itemsize, _ptr(sbr), _ptr(ps),
                                                       _ptr(out["status"]), _ptr(out["taken"]), _ptr(out["hold"]), _stream()),
                "heaac_heaac_parse_device_streams")
         out.update(sst=sst_out, sbr=sbr, ps=ps)
@@ -574,12 +547,8 @@ class Device:
         assert tools.dtype == torch.uint8 and tools.numel() == n * TOOLS_FRAME_DT.itemsize
         assert rng is None or (rng.dtype == torch.int32 and rng.numel() == n)
         assert pred is None or (pred.dtype == torch.float32 and pred.numel() == n * channels * MAX_PREDICTORS * 6)
-        _check(lib().heaac_spectral_tools_batch(self._h, channels, _ptr(coeffs), _ptr(tools),
-                                                _ptr(rng) if rng is not None else None,
-                                                _ptr(rng) if rng is not None else None,
-                                                _ptr(pred) if pred is not None else None,
-                                                _ptr(pred) if pred is not None else None,
-                                                C.c_size_t(n), _stream()), "heaac_spectral_tools_batch")
+        _check(lib().heaac_spectral_tools_batch(self._h, channels, _ptr(coeffs), _ptr(tools), _ptr(rng), _ptr(rng),
+                                                _ptr(pred), _ptr(pred), n, _stream()), "heaac_spectral_tools_batch")
         return coeffs
 
     def spectral_tools_streams(self, channels, coeffs, tools, frames_per_stream, rng=None, pred=None, rng_out=None,
@@ -610,17 +579,14 @@ class Device:
             rng_out = rng
         if pred is not None and pred_out is None:
             pred_out = pred
-        state = lambda: (_ptr(rng) if rng is not None else None, _ptr(rng_out) if rng is not None else None,
-                         _ptr(pred) if pred is not None else None, _ptr(pred_out) if pred is not None else None)
+        state = lambda: (_ptr(rng), _ptr(rng_out), _ptr(pred), _ptr(pred_out))     # (no rng / pred: no rng_out / pred_out)
         if hold is None:
-            _check(lib().heaac_spectral_tools_streams(self._h, channels, _ptr(coeffs), _ptr(tools), *state(),
-                                                      C.c_size_t(S), C.c_size_t(T), _stream()),
+            _check(lib().heaac_spectral_tools_streams(self._h, channels, _ptr(coeffs), _ptr(tools), *state(), S, T, _stream()),
                    "heaac_spectral_tools_streams")
         else:
             d_hold = _hold_ptr(hold, n)
-            _check(lib().heaac_spectral_tools_streams_ex(self._h, channels, _ptr(coeffs), _ptr(tools), *state(),
-                                                         C.c_size_t(S), C.c_size_t(T), d_hold, _stream()),
-                   "heaac_spectral_tools_streams_ex")
+            _check(lib().heaac_spectral_tools_streams_ex(self._h, channels, _ptr(coeffs), _ptr(tools), *state(), S, T, d_hold,
+                                                         _stream()), "heaac_spectral_tools_streams_ex")
         return coeffs
 
     def spectral_tools_ex(self, channels, stages, coeffs, tools, rng=None, pred=None, cce=None, cce_coeffs=None):
@@ -635,13 +601,10 @@ class Device:
             n_cce = cce.numel() // (n * CCE_FRAME_DT.itemsize)
             assert cce.dtype == torch.uint8 and cce.numel() == n * n_cce * CCE_FRAME_DT.itemsize
             assert cce_coeffs.dtype == torch.float32 and cce_coeffs.numel() == n * n_cce * 1024
-        _check(lib().heaac_spectral_tools_batch_ex(self._h, channels, stages, _ptr(coeffs), _ptr(tools),
-                                                   _ptr(rng) if rng is not None else None,
-                                                   _ptr(rng) if rng is not None else None,
-                                                   _ptr(pred) if pred is not None else None,
-                                                   _ptr(pred) if pred is not None else None,
+        _check(lib().heaac_spectral_tools_batch_ex(self._h, channels, stages, _ptr(coeffs), _ptr(tools), _ptr(rng), _ptr(rng),
+                                                   _ptr(pred), _ptr(pred),
                                                    _ptr(cce) if n_cce else None, _ptr(cce_coeffs) if n_cce else None,
-                                                   n_cce, C.c_size_t(n), _stream()), "heaac_spectral_tools_batch_ex")
+                                                   n_cce, n, _stream()), "heaac_spectral_tools_batch_ex")
         return coeffs
 
     # -- HE-AAC --
@@ -654,9 +617,8 @@ class Device:
         assert cce.dtype == torch.float32 and cce.numel() == n * 1024, "cce"
         assert coupling.numel() * coupling.element_size() == n * COUPLING_DT.itemsize, "coupling"
         out = torch.empty((n, 1024, channels), dtype=torch.int16, device=pcm.device) if s16 else None
-        _check(lib().heaac_couple_after_imdct_batch(self._h, channels, _ptr(pcm), _ptr(cce), _ptr(coupling),
-                                                    _ptr(out), C.c_size_t(n), _stream()),
-               "heaac_couple_after_imdct_batch")
+        _check(lib().heaac_couple_after_imdct_batch(self._h, channels, _ptr(pcm), _ptr(cce), _ptr(coupling), _ptr(out), n,
+                                                    _stream()), "heaac_couple_after_imdct_batch")
         return out
 
     def pcm_interleave(self, planes, length, pcm_format=None):
@@ -673,20 +635,17 @@ class Device:
             refs[c].d_base = t.data_ptr() + 4 * off
             refs[c].frame_stride = stride
         out = torch.empty((n, length, ch), dtype=torch.int16, device=t0.device)
-        _check(lib().heaac_pcm_interleave_batch(self._h, ch, refs, int(length), int(fmt), _ptr(out), C.c_size_t(n), _stream()),
+        _check(lib().heaac_pcm_interleave_batch(self._h, ch, refs, int(length), int(fmt), _ptr(out), n, _stream()),
                "heaac_pcm_interleave_batch")
         return out
 
     def he_check(self, cfg, sbr, hdr, ps=None):
         """heaac_he_check_batch on device-resident records (byte tensors as he_decode takes them):
         returns None if every frame is valid, else (first bad frame index, rule name)."""
-        import torch
         n = sbr.numel() // SBR_FRAME_DT.itemsize
         first, rule = C.c_size_t(0), C.c_int(0)
-        rc = lib().heaac_he_check_batch(self._h, C.c_int(cfg), C.c_void_p(sbr.data_ptr()), C.c_void_p(hdr.data_ptr()),
-                                        C.c_size_t(hdr.numel() // SBR_HDR_DT.itemsize),
-                                        C.c_void_p(ps.data_ptr()) if ps is not None else None, C.c_size_t(n),
-                                        C.c_void_p(torch.cuda.current_stream().cuda_stream), C.byref(first), C.byref(rule))
+        rc = lib().heaac_he_check_batch(self._h, cfg, sbr.data_ptr(), hdr.data_ptr(), hdr.numel() // SBR_HDR_DT.itemsize,
+                                        ps.data_ptr() if ps is not None else None, n, _stream(), C.byref(first), C.byref(rule))
         if rc == 0:
             return None
         if rc != -1:
@@ -695,36 +654,33 @@ class Device:
             raise HeaacError("heaac_he_check_batch: bad arguments")
         return int(first.value), BAD_RULES[rule.value] if 0 <= rule.value < len(BAD_RULES) else str(rule.value)
 
-    def he_decode(self, cfg, coeffs, ics, sbr, hdr, ps, state_in, state_out=None, pcm=None,
-                  pcm_format=PCM_F32, downsampled=False):
-        """downsampled: HEAAC_HE_DOWNSAMPLED -- output at the core rate, 1024 samples per channel."""
+    @staticmethod
+    def _he_args(cfg, coeffs, ics, sbr, hdr, ps, state_in, S, T, state_out, pcm, pcm_format, downsampled):
+        """The tensors of an HE decode call over S streams x T frames (he_decode: S = n, T = 1), checked -- a
+        wrong-length tensor would be a silent device out-of-bounds read.  Returns (n_hdr, state_out, pcm), the last two
+        allocated where the caller gave none."""
         import torch
-        n = coeffs.shape[0]
-        # a wrong-length tensor would be a silent device out-of-bounds read: check them all here
+        n = S * T
+        assert state_in.dtype == torch.float32 and state_in.numel() == S * STATE_WORDS[cfg], "state_in"
         assert coeffs.dtype == torch.float32 and coeffs.numel() == n * CORE_CH[cfg] * 1024, "coeffs"
-        assert state_in.dtype == torch.float32 and state_in.numel() == n * STATE_WORDS[cfg], "state_in"
         assert ics.numel() * ics.element_size() == n * CORE_CH[cfg] * ICS_DT.itemsize, "ics"
         assert sbr.numel() * sbr.element_size() == n * SBR_FRAME_DT.itemsize, "sbr"
         assert hdr.numel() * hdr.element_size() >= SBR_HDR_DT.itemsize and \
             (hdr.numel() * hdr.element_size()) % SBR_HDR_DT.itemsize == 0, "hdr"
         if cfg == CFG_HEV2:
             assert ps is not None and ps.numel() * ps.element_size() == n * PS_FRAME_DT.itemsize, "ps"
-        if state_out is None:
-            state_out = torch.empty_like(state_in)
-        else:
-            assert state_out.dtype == torch.float32 and state_out.numel() == state_in.numel(), "state_out"
-        length = 1024 if downsampled else 2048
-        if pcm is None:
-            if pcm_format == PCM_F32:
-                pcm = torch.empty((n, OUT_CH[cfg], length), dtype=torch.float32, device=coeffs.device)
-            else:
-                pcm = torch.empty((n, length, OUT_CH[cfg]), dtype=torch.int16, device=coeffs.device)
-        else:
-            assert pcm.numel() == n * OUT_CH[cfg] * length, "pcm"
-        n_hdr = hdr.numel() // SBR_HDR_DT.itemsize
+        pcm = _pcm(pcm, n, OUT_CH[cfg], 1024 if downsampled else 2048, pcm_format, coeffs.device)
+        return hdr.numel() // SBR_HDR_DT.itemsize, _state_out(state_out, state_in), pcm
+
+    def he_decode(self, cfg, coeffs, ics, sbr, hdr, ps, state_in, state_out=None, pcm=None,
+                  pcm_format=PCM_F32, downsampled=False):
+        """downsampled: HEAAC_HE_DOWNSAMPLED -- output at the core rate, 1024 samples per channel."""
+        n = coeffs.shape[0]
+        n_hdr, state_out, pcm = self._he_args(cfg, coeffs, ics, sbr, hdr, ps, state_in, n, 1, state_out, pcm, pcm_format,
+                                              downsampled)
         _check(lib().heaac_he_decode_batch_ex(self._h, cfg, 1 if downsampled else 0, _ptr(coeffs), _ptr(ics), _ptr(sbr),
-                                              _ptr(hdr), C.c_size_t(n_hdr), _ptr(ps), _ptr(state_in), _ptr(state_out),
-                                              _ptr(pcm), pcm_format, C.c_size_t(n), _stream()),
+                                              _ptr(hdr), n_hdr, _ptr(ps), _ptr(state_in), _ptr(state_out),
+                                              _ptr(pcm), pcm_format, n, _stream()),
                "heaac_he_decode_batch")
         return pcm, state_out
 
@@ -734,43 +690,20 @@ class Device:
         are laid out as for he_decode with n = S * T (frame t of stream s at s * T + t); state_in / state_out hold ONE
         record per stream (before frame 0 / after frame T - 1).  hold: None, or a uint8 tensor of S * T elements,
         non-zero = frame held (heaac_he_decode_streams_ex).  Returns (pcm, state_out)."""
-        import torch
         T = int(frames_per_stream)
         S = state_in.numel() // STATE_WORDS[cfg]
-        n = S * T
-        # a wrong-length tensor would be a silent device out-of-bounds read: check them all here
-        assert state_in.dtype == torch.float32 and state_in.numel() == S * STATE_WORDS[cfg], "state_in"
-        assert coeffs.dtype == torch.float32 and coeffs.numel() == n * CORE_CH[cfg] * 1024, "coeffs"
-        assert ics.numel() * ics.element_size() == n * CORE_CH[cfg] * ICS_DT.itemsize, "ics"
-        assert sbr.numel() * sbr.element_size() == n * SBR_FRAME_DT.itemsize, "sbr"
-        assert hdr.numel() * hdr.element_size() >= SBR_HDR_DT.itemsize and \
-            (hdr.numel() * hdr.element_size()) % SBR_HDR_DT.itemsize == 0, "hdr"
-        if cfg == CFG_HEV2:
-            assert ps is not None and ps.numel() * ps.element_size() == n * PS_FRAME_DT.itemsize, "ps"
-        if state_out is None:
-            state_out = torch.empty_like(state_in)
-        else:
-            assert state_out.dtype == torch.float32 and state_out.numel() == state_in.numel(), "state_out"
-        length = 1024 if downsampled else 2048
-        if pcm is None:
-            if pcm_format == PCM_F32:
-                pcm = torch.empty((n, OUT_CH[cfg], length), dtype=torch.float32, device=coeffs.device)
-            else:
-                pcm = torch.empty((n, length, OUT_CH[cfg]), dtype=torch.int16, device=coeffs.device)
-        else:
-            assert pcm.numel() == n * OUT_CH[cfg] * length and \
-                pcm.dtype == (torch.float32 if pcm_format == PCM_F32 else torch.int16), "pcm"
-        n_hdr = hdr.numel() // SBR_HDR_DT.itemsize
+        n_hdr, state_out, pcm = self._he_args(cfg, coeffs, ics, sbr, hdr, ps, state_in, S, T, state_out, pcm, pcm_format,
+                                              downsampled)
         if hold is None:
             _check(lib().heaac_he_decode_streams(self._h, cfg, 1 if downsampled else 0, _ptr(coeffs), _ptr(ics), _ptr(sbr),
-                                                 _ptr(hdr), C.c_size_t(n_hdr), _ptr(ps), _ptr(state_in), _ptr(state_out),
-                                                 _ptr(pcm), pcm_format, C.c_size_t(S), C.c_size_t(T), _stream()),
+                                                 _ptr(hdr), n_hdr, _ptr(ps), _ptr(state_in), _ptr(state_out),
+                                                 _ptr(pcm), pcm_format, S, T, _stream()),
                    "heaac_he_decode_streams")
         else:
-            d_hold = _hold_ptr(hold, n)
+            d_hold = _hold_ptr(hold, S * T)
             _check(lib().heaac_he_decode_streams_ex(self._h, cfg, 1 if downsampled else 0, _ptr(coeffs), _ptr(ics), _ptr(sbr),
-                                                    _ptr(hdr), C.c_size_t(n_hdr), _ptr(ps), _ptr(state_in), _ptr(state_out),
-                                                    _ptr(pcm), pcm_format, C.c_size_t(S), C.c_size_t(T), d_hold, _stream()),
+                                                    _ptr(hdr), n_hdr, _ptr(ps), _ptr(state_in), _ptr(state_out),
+                                                    _ptr(pcm), pcm_format, S, T, d_hold, _stream()),
                    "heaac_he_decode_streams_ex")
         return pcm, state_out
 
@@ -779,31 +712,24 @@ class Device:
         n = x.shape[0]
         W = torch.empty((n, 32, 32, 2), dtype=torch.float32, device=x.device)
         xh = torch.empty_like(xhist)
-        _check(lib().heaac_qmf_analysis_batch(self._h, _ptr(x), _ptr(xhist), _ptr(xh), _ptr(W),
-                                              C.c_float(scale), C.c_size_t(n), _stream()),
+        _check(lib().heaac_qmf_analysis_batch(self._h, _ptr(x), _ptr(xhist), _ptr(xh), _ptr(W), scale, n, _stream()),
                "heaac_qmf_analysis_batch")
         return W, xh
 
-    def qmf_synthesis(self, X, v, scale=2.0 ** -15, bias=385.0):
+    def _qmf_synthesis(self, entry, length, X, v, scale, bias):
         import torch
         n = X.shape[0]
-        out = torch.empty((n, 2048), dtype=torch.float32, device=X.device)
+        out = torch.empty((n, length), dtype=torch.float32, device=X.device)
         vo = torch.empty_like(v)
-        _check(lib().heaac_qmf_synthesis_batch(self._h, _ptr(X), _ptr(v), _ptr(vo), _ptr(out),
-                                               C.c_float(scale), C.c_float(bias), C.c_size_t(n), _stream()),
-               "heaac_qmf_synthesis_batch")
+        _check(getattr(lib(), entry)(self._h, _ptr(X), _ptr(v), _ptr(vo), _ptr(out), scale, bias, n, _stream()), entry)
         return out, vo
+
+    def qmf_synthesis(self, X, v, scale=2.0 ** -15, bias=385.0):
+        return self._qmf_synthesis("heaac_qmf_synthesis_batch", 2048, X, v, scale, bias)
 
     def qmf_synthesis_ds(self, X, v, scale=2.0 ** -15, bias=385.0):
         """Downsampled synthesis bank (div = 1): X [n][2][32][64], v [n][576] -> out [n][1024]."""
-        import torch
-        n = X.shape[0]
-        out = torch.empty((n, 1024), dtype=torch.float32, device=X.device)
-        vo = torch.empty_like(v)
-        _check(lib().heaac_qmf_synthesis_ds_batch(self._h, _ptr(X), _ptr(v), _ptr(vo), _ptr(out),
-                                                  C.c_float(scale), C.c_float(bias), C.c_size_t(n), _stream()),
-               "heaac_qmf_synthesis_ds_batch")
-        return out, vo
+        return self._qmf_synthesis("heaac_qmf_synthesis_ds_batch", 1024, X, v, scale, bias)
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -855,20 +781,18 @@ ADTS_FRAME, ADTS_JUNK, ADTS_TRUNCATED, ADTS_TAG = 0, 1, 2, 3
 
 def adts_probe(buf):
     """heaac_adts_probe: the demuxer's probe score of a raw ADTS buffer."""
-    return lib().heaac_adts_probe(bytes(buf), C.c_size_t(len(buf)))
+    return lib().heaac_adts_probe(bytes(buf), len(buf))
 
 
 def adts_split(buf):
     """heaac_adts_split: (packets [ADTS_PACKET_DT], header of the first frame or None)."""
     buf = bytes(buf)
-    L = lib()
-    L.heaac_adts_split.restype = C.c_long
-    n = L.heaac_adts_split(buf, C.c_size_t(len(buf)), None, C.c_size_t(0), None)
+    n = lib().heaac_adts_split(buf, len(buf), None, 0, None)
     if n < 0:
         raise HeaacError("heaac_adts_split -> %d" % n)
     out = np.zeros(n, ADTS_PACKET_DT)
     h = AdtsHeader()
-    m = L.heaac_adts_split(buf, C.c_size_t(len(buf)), out.ctypes.data_as(C.c_void_p), C.c_size_t(n), C.byref(h))
+    m = lib().heaac_adts_split(buf, len(buf), _np(out), n, C.byref(h))
     assert m == n
     return out, (h if (out["kind"] != ADTS_JUNK).any() and ((out["kind"] == ADTS_FRAME) | (out["kind"] == ADTS_TRUNCATED)).any() else None)
 
@@ -885,24 +809,19 @@ class Pipeline:
         if self.len == 2048 and aac_cfg.ext_sample_rate and aac_cfg.ext_sample_rate < 2 * aac_cfg.sample_rate:
             self.len = 1024                                # downsampled SBR: the output at the core rate
         if self.T == 1:
-            _check(lib().heaac_pipeline_create(C.byref(self._h), C.byref(aac_cfg), he_cfg, C.c_size_t(n_streams), threads),
+            _check(lib().heaac_pipeline_create(C.byref(self._h), C.byref(aac_cfg), he_cfg, n_streams, threads),
                    "heaac_pipeline_create")
         else:
-            _check(lib().heaac_pipeline_create_streams(C.byref(self._h), C.byref(aac_cfg), he_cfg, C.c_size_t(n_streams),
-                                                       C.c_size_t(max(self.T, 0)), threads),
-                   "heaac_pipeline_create_streams")
+            _check(lib().heaac_pipeline_create_streams(C.byref(self._h), C.byref(aac_cfg), he_cfg, n_streams, max(self.T, 0),
+                                                       threads), "heaac_pipeline_create_streams")
 
     def submit(self, aus, with_status=True):
         """aus: n_streams * frames_per_tick access units (bytes; an empty one where a stream has run out).  Returns the
         parse status per unit (None without a status array)."""
-        k = self.n * self.T
-        assert len(aus) == k
-        keep = [C.create_string_buffer(bytes(a), len(a)) for a in aus]
-        ptrs = (C.c_char_p * k)(*[C.cast(q, C.c_char_p) for q in keep])
-        sizes = (C.c_int * k)(*[len(a) for a in aus])
-        status = np.zeros(k, np.int32) if with_status else None
-        _check(lib().heaac_pipeline_submit(self._h, ptrs, sizes, status.ctypes.data_as(C.c_void_p) if with_status else None),
-               "heaac_pipeline_submit")
+        assert len(aus) == self.n * self.T
+        keep, ptrs, sizes = _units(aus)
+        status = np.zeros(len(aus), np.int32) if with_status else None
+        _check(lib().heaac_pipeline_submit(self._h, ptrs, sizes, _np(status)), "heaac_pipeline_submit")
         return status
 
     def submit_raw(self, ptrs, sizes):
@@ -937,25 +856,21 @@ class LayoutPipeline:
         he = aac_cfg.sbr == 1
         self.len = 2048 if he and not (aac_cfg.ext_sample_rate and aac_cfg.ext_sample_rate < 2 * aac_cfg.sample_rate) else 1024
         self._layout = np.ascontiguousarray(layout)
-        _check(lib().heaac_layout_pipeline_create(C.byref(self._h), C.byref(aac_cfg), self._layout.ctypes.data_as(C.c_void_p),
-                                                  C.c_size_t(n_streams), threads), "heaac_layout_pipeline_create")
+        _check(lib().heaac_layout_pipeline_create(C.byref(self._h), C.byref(aac_cfg), _np(self._layout), n_streams, threads),
+               "heaac_layout_pipeline_create")
         self.ch = int(lib().heaac_layout_pipeline_channels(self._h))
 
     def submit(self, aus):
         assert len(aus) == self.n
-        keep = [C.create_string_buffer(bytes(a), len(a)) for a in aus]
-        ptrs = (C.c_char_p * self.n)(*[C.cast(k, C.c_char_p) for k in keep])
-        sizes = (C.c_int * self.n)(*[len(a) for a in aus])
+        keep, ptrs, sizes = _units(aus)
         status = np.zeros(self.n, np.int32)
-        _check(lib().heaac_layout_pipeline_submit(self._h, ptrs, sizes, status.ctypes.data_as(C.c_void_p)),
-               "heaac_layout_pipeline_submit")
+        _check(lib().heaac_layout_pipeline_submit(self._h, ptrs, sizes, _np(status)), "heaac_layout_pipeline_submit")
         return status
 
     def submit_raw(self, ptrs, sizes, status=None):
         """ptrs, sizes: ctypes arrays of n_streams built once by the caller; status: an int32 array of n_streams to
         fill, or None."""
-        _check(lib().heaac_layout_pipeline_submit(self._h, ptrs, sizes, status.ctypes.data_as(C.c_void_p) if status is not None else None),
-               "heaac_layout_pipeline_submit")
+        _check(lib().heaac_layout_pipeline_submit(self._h, ptrs, sizes, _np(status)), "heaac_layout_pipeline_submit")
 
     def collect(self):
         p = C.POINTER(C.c_int16)()
@@ -982,10 +897,8 @@ def aac_parse_frame_ex(cfg, stream, au, coeff_channels=2, with_cce=True):
                cce_ics=np.zeros(MAX_CCE, ICS_DT), cce_tools=np.zeros(MAX_CCE, TOOLS_FRAME_DT))
     co = _CceOut(out["cce"].ctypes.data, out["cce_coeffs"].ctypes.data, out["cce_ics"].ctypes.data,
                  out["cce_tools"].ctypes.data)
-    r = lib().heaac_aac_parse_frame_ex(C.byref(cfg), stream.ctypes.data_as(C.c_void_p), au, len(au), coeff_channels,
-                                       out["coeffs"].ctypes.data_as(C.c_void_p), out["ics"].ctypes.data_as(C.c_void_p),
-                                       out["tools"].ctypes.data_as(C.c_void_p), C.byref(co) if with_cce else None,
-                                       out["info"].ctypes.data_as(C.c_void_p))
+    r = lib().heaac_aac_parse_frame_ex(C.byref(cfg), _np(stream), au, len(au), coeff_channels, _np(out["coeffs"]),
+                                       _np(out["ics"]), _np(out["tools"]), C.byref(co) if with_cce else None, _np(out["info"]))
     return r, out
 
 
@@ -1003,7 +916,7 @@ assert AAC_LAYOUT_DT.itemsize == 216 and AAC_ELEM_INFO_DT.itemsize == 16
 def aac_layout_default(chan_config):
     """heaac_aac_layout_default: (status, one AAC_LAYOUT_DT record)."""
     l = np.zeros(1, AAC_LAYOUT_DT)
-    return lib().heaac_aac_layout_default(l.ctypes.data_as(C.c_void_p), int(chan_config)), l
+    return lib().heaac_aac_layout_default(_np(l), int(chan_config)), l
 
 
 def aac_layout_from_pce(buf, bit_offset):
@@ -1011,7 +924,7 @@ def aac_layout_from_pce(buf, bit_offset):
     l = np.zeros(1, AAC_LAYOUT_DT)
     used = C.c_int(0)
     buf = bytes(buf)
-    r = lib().heaac_aac_layout_from_pce(l.ctypes.data_as(C.c_void_p), buf, len(buf), int(bit_offset), C.byref(used))
+    r = lib().heaac_aac_layout_from_pce(_np(l), buf, len(buf), int(bit_offset), C.byref(used))
     return r, l, used.value
 
 
@@ -1019,7 +932,7 @@ def aac_layout_from_au(au):
     """heaac_aac_layout_from_au: (status, layout)."""
     l = np.zeros(1, AAC_LAYOUT_DT)
     au = bytes(au)
-    return lib().heaac_aac_layout_from_au(l.ctypes.data_as(C.c_void_p), au, len(au)), l
+    return lib().heaac_aac_layout_from_au(_np(l), au, len(au)), l
 
 
 def asc_layout(buf):
@@ -1027,7 +940,7 @@ def asc_layout(buf):
     c = AacConfig()
     l = np.zeros(1, AAC_LAYOUT_DT)
     buf = bytes(buf)
-    return lib().heaac_asc_layout(C.byref(c), l.ctypes.data_as(C.c_void_p), buf, len(buf)), c, l
+    return lib().heaac_asc_layout(C.byref(c), _np(l), buf, len(buf)), c, l
 
 
 def aac_parse_frame_layout(cfg, layout, streams, au, with_cce=False):
@@ -1041,35 +954,28 @@ def aac_parse_frame_layout(cfg, layout, streams, au, with_cce=False):
     assert streams.dtype == AAC_STREAM_DT and streams.shape[0] >= ne
     out = dict(coeffs=np.zeros((ne, 2, 1024), np.float32), ics=np.zeros((ne, 2), ICS_DT), tools=np.zeros(ne, TOOLS_FRAME_DT),
                elem=np.zeros(ne, AAC_ELEM_INFO_DT), info=np.zeros(1, AAC_INFO_DT))
-    args = (C.byref(cfg), layout.ctypes.data_as(C.c_void_p), streams.ctypes.data_as(C.c_void_p),
-            au, len(au), out["coeffs"].ctypes.data_as(C.c_void_p),
-            out["ics"].ctypes.data_as(C.c_void_p), out["tools"].ctypes.data_as(C.c_void_p),
-            out["elem"].ctypes.data_as(C.c_void_p))
+    args = (C.byref(cfg), _np(layout), _np(streams), au, len(au), _np(out["coeffs"]), _np(out["ics"]), _np(out["tools"]),
+            _np(out["elem"]))
     if not with_cce:
-        return lib().heaac_aac_parse_frame_layout(*args, out["info"].ctypes.data_as(C.c_void_p)), out
+        return lib().heaac_aac_parse_frame_layout(*args, _np(out["info"])), out
     out.update(cce=np.zeros((ne, MAX_CCE), CCE_FRAME_DT), cce_coeffs=np.zeros((MAX_CCE, 1024), np.float32),
                cce_ics=np.zeros(MAX_CCE, ICS_DT), cce_tools=np.zeros(MAX_CCE, TOOLS_FRAME_DT),
                cce_elem=np.zeros(MAX_CCE, AAC_ELEM_INFO_DT))
     co = _CceOut(out["cce"].ctypes.data, out["cce_coeffs"].ctypes.data, out["cce_ics"].ctypes.data,
                  out["cce_tools"].ctypes.data, out["cce_elem"].ctypes.data if with_cce != "no_sbr" else None)
-    return lib().heaac_aac_parse_frame_layout_ex(*args, C.byref(co), out["info"].ctypes.data_as(C.c_void_p)), out
+    return lib().heaac_aac_parse_frame_layout_ex(*args, C.byref(co), _np(out["info"])), out
 
 
 def aac_parse_batch(cfg, streams, aus, threads=0):
     """heaac_aac_parse_batch over a list of access units (bytes), one per stream.  `streams`: AAC_STREAM_DT
     array updated in place.  Returns dict(coeffs [n][2][1024], ics [n][2], tools [n], info [n], status [n])."""
     n = len(aus)
-    keep = [C.create_string_buffer(bytes(a), len(a)) for a in aus]
-    ptrs = (C.c_char_p * n)(*[C.cast(k, C.c_char_p) for k in keep])
-    sizes = (C.c_int * n)(*[len(a) for a in aus])
+    keep, ptrs, sizes = _units(aus)
     out = dict(coeffs=np.zeros((n, 2, 1024), np.float32), ics=np.zeros((n, 2), ICS_DT),
                tools=np.zeros(n, TOOLS_FRAME_DT), info=np.zeros(n, AAC_INFO_DT), status=np.zeros(n, np.int32))
     assert streams.dtype == AAC_STREAM_DT and streams.shape == (n,)
-    failed = lib().heaac_aac_parse_batch(C.byref(cfg), streams.ctypes.data_as(C.c_void_p), ptrs, sizes, C.c_size_t(n),
-                                         out["coeffs"].ctypes.data_as(C.c_void_p), out["ics"].ctypes.data_as(C.c_void_p),
-                                         out["tools"].ctypes.data_as(C.c_void_p), out["info"].ctypes.data_as(C.c_void_p),
-                                         out["status"].ctypes.data_as(C.c_void_p), C.c_int(threads))
-    out["failed"] = failed
+    out["failed"] = lib().heaac_aac_parse_batch(C.byref(cfg), _np(streams), ptrs, sizes, n, _np(out["coeffs"]), _np(out["ics"]),
+                                                _np(out["tools"]), _np(out["info"]), _np(out["status"]), threads)
     return out
 
 
@@ -1084,26 +990,29 @@ def pack_units(aus):
     return np.frombuffer(b"".join(bytes(a) for a in aus), np.uint8).copy(), off
 
 
+def _packed(aus):
+    """pack_units for the host walks of the device parsers: (bytes, uint32 offsets), the bytes with one more behind them
+    (a pointer even when every unit is empty)."""
+    buf, off = pack_units(aus)
+    return np.concatenate([buf, np.zeros(1, np.uint8)]), off.astype(np.uint32)
+
+
 def aac_parse_core(cfg, streams, aus, coeff_channels=2, out=None):
     """heaac_debug_aac_parse_core (include/heaac_debug.h): the walk of heaac_aac_parse_device on the host, over a
     list of access units, one per stream.  `streams`: AAC_STREAM_DT array, updated in place for the units that come
     back PARSE_OK.  Returns the dict of aac_parse_batch (coeffs [n][coeff_channels][1024], ics [n][coeff_channels])
     plus why [n]: 0, or the PARSE_WHY_* reason a unit was deferred for.  `out`: a dict of pre-filled arrays to write into."""
     n = len(aus)
-    buf, off = pack_units(aus)
-    off = off.astype(np.uint32)
+    keep, off = _packed(aus)
     if out is None:
         out = dict(coeffs=np.zeros((n, coeff_channels, 1024), np.float32), ics=np.zeros((n, coeff_channels), ICS_DT),
                    tools=np.zeros(n, TOOLS_FRAME_DT), info=np.zeros(n, AAC_INFO_DT))
     out["status"] = np.zeros(n, np.int32)
     out["why"] = np.zeros(n, np.int32)
     assert streams.dtype == AAC_STREAM_DT and streams.shape == (n,)
-    keep = np.concatenate([buf, np.zeros(1, np.uint8)])          # (a pointer even when every unit is empty)
-    rc = lib().heaac_debug_aac_parse_core(C.byref(cfg), streams.ctypes.data_as(C.c_void_p), keep.ctypes.data_as(C.c_void_p),
-                                          off.ctypes.data_as(C.c_void_p), C.c_size_t(n), C.c_int(coeff_channels),
-                                          out["coeffs"].ctypes.data_as(C.c_void_p), out["ics"].ctypes.data_as(C.c_void_p),
-                                          out["tools"].ctypes.data_as(C.c_void_p), out["info"].ctypes.data_as(C.c_void_p),
-                                          out["status"].ctypes.data_as(C.c_void_p), out["why"].ctypes.data_as(C.c_void_p))
+    rc = lib().heaac_debug_aac_parse_core(C.byref(cfg), _np(streams), _np(keep), _np(off), n, coeff_channels,
+                                          _np(out["coeffs"]), _np(out["ics"]), _np(out["tools"]), _np(out["info"]),
+                                          _np(out["status"]), _np(out["why"]))
     _check(rc, "heaac_debug_aac_parse_core")
     return out
 
@@ -1117,9 +1026,7 @@ def sbr_parse_core(cfg, sst_in, aus, info, hdr, aac_status=None, with_ps=True, o
     SBR_HDR_DT records, aac_status: int32 [n] or None.  Returns dict(sst [n][bytes], sbr [n], ps [n] or None, status
     [n], why [n]: 0 or the SBR_WHY_* reason).  `out`: a dict of pre-filled sst / sbr / ps arrays to write into."""
     n = len(aus)
-    buf, off = pack_units(aus)
-    off = off.astype(np.uint32)
-    keep = np.concatenate([buf, np.zeros(1, np.uint8)])
+    keep, off = _packed(aus)
     sst_in = np.ascontiguousarray(sst_in)
     info = np.ascontiguousarray(info, dtype=AAC_INFO_DT)
     hdr = np.ascontiguousarray(hdr, dtype=SBR_HDR_DT).reshape(-1)
@@ -1130,10 +1037,9 @@ def sbr_parse_core(cfg, sst_in, aus, info, hdr, aac_status=None, with_ps=True, o
     out["why"] = np.zeros(n, np.int32)
     if aac_status is not None:
         aac_status = np.ascontiguousarray(aac_status, dtype=np.int32)
-    p = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None
-    rc = lib().heaac_debug_sbr_parse_core(C.byref(cfg), p(sst_in), p(out["sst"]), p(keep), p(off), p(info), p(aac_status),
-                                          C.c_size_t(n), p(hdr), C.c_size_t(hdr.shape[0]), p(out["sbr"]), p(out.get("ps")),
-                                          p(out["status"]), p(out["why"]))
+    rc = lib().heaac_debug_sbr_parse_core(C.byref(cfg), _np(sst_in), _np(out["sst"]), _np(keep), _np(off), _np(info),
+                                          _np(aac_status), n, _np(hdr), hdr.shape[0], _np(out["sbr"]), _np(out.get("ps")),
+                                          _np(out["status"]), _np(out["why"]))
     _check(rc, "heaac_debug_sbr_parse_core")
     return out
 
@@ -1152,9 +1058,7 @@ def parse_core_streams(cfg, streams, aus, frames_per_stream, coeff_channels=2, s
     S = n // T
     assert S * T == n and streams.dtype == AAC_STREAM_DT and streams.shape == (S,)
     he = sst_in is not None
-    buf, off = pack_units(aus)
-    off = off.astype(np.uint32)
-    keep = np.concatenate([buf, np.zeros(1, np.uint8)])
+    keep, off = _packed(aus)
     out = dict(out) if out is not None else {}
     out.setdefault("coeffs", np.zeros((n, coeff_channels, 1024), np.float32))
     out.setdefault("ics", np.zeros((n, coeff_channels), ICS_DT))
@@ -1164,11 +1068,11 @@ def parse_core_streams(cfg, streams, aus, frames_per_stream, coeff_channels=2, s
     out.setdefault("taken", np.zeros(S, np.uint32))
     out.setdefault("hold", np.zeros(n, np.uint8))
     out.setdefault("why", np.zeros(n, np.int32))
-    p = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None
+    aac = [_np(out[k]) for k in ("coeffs", "ics", "tools", "info")]
+    tail = [_np(out[k]) for k in ("status", "taken", "hold", "why")]
     if not he:
-        rc = lib().heaac_debug_aac_parse_core_streams(C.byref(cfg), p(streams), p(keep), p(off), C.c_size_t(S), C.c_size_t(T),
-                                                      C.c_int(coeff_channels), p(out["coeffs"]), p(out["ics"]), p(out["tools"]),
-                                                      p(out["info"]), p(out["status"]), p(out["taken"]), p(out["hold"]), p(out["why"]))
+        rc = lib().heaac_debug_aac_parse_core_streams(C.byref(cfg), _np(streams), _np(keep), _np(off), S, T, coeff_channels,
+                                                      *aac, *tail)
         _check(rc, "heaac_debug_aac_parse_core_streams")
         return out
     sst_in = np.ascontiguousarray(sst_in)
@@ -1177,10 +1081,9 @@ def parse_core_streams(cfg, streams, aus, frames_per_stream, coeff_channels=2, s
     out.setdefault("sst", np.zeros_like(sst_in))
     out.setdefault("sbr", np.zeros(n, SBR_FRAME_DT))
     out.setdefault("ps", np.zeros(n, PS_FRAME_DT) if with_ps else None)
-    rc = lib().heaac_debug_heaac_parse_core_streams(C.byref(cfg), p(streams), p(sst_in), p(out["sst"]), p(keep), p(off), C.c_size_t(S),
-                                                    C.c_size_t(T), C.c_int(coeff_channels), p(out["coeffs"]), p(out["ics"]),
-                                                    p(out["tools"]), p(out["info"]), p(hdr), C.c_size_t(hdr.shape[0]), p(out["sbr"]),
-                                                    p(out["ps"]), p(out["status"]), p(out["taken"]), p(out["hold"]), p(out["why"]))
+    rc = lib().heaac_debug_heaac_parse_core_streams(C.byref(cfg), _np(streams), _np(sst_in), _np(out["sst"]), _np(keep), _np(off),
+                                                    S, T, coeff_channels, *aac, _np(hdr), hdr.shape[0], _np(out["sbr"]),
+                                                    _np(out["ps"]), *tail)
     _check(rc, "heaac_debug_heaac_parse_core_streams")
     return out
 
@@ -1196,27 +1099,23 @@ class SbrHeaderTable:
     """heaac_sbr_table_*: the batch's table of derived SBR headers (entry 0 = the null header)."""
 
     def __init__(self, capacity=256):
-        L = lib()
-        L.heaac_sbr_table_create.restype = C.c_void_p
-        L.heaac_sbr_table_count.restype = C.c_size_t
-        L.heaac_sbr_table_data.restype = C.c_void_p
-        self._h = L.heaac_sbr_table_create(C.c_size_t(capacity))
+        self._h = lib().heaac_sbr_table_create(capacity)
         if not self._h:
             raise HeaacError("heaac_sbr_table_create failed")
 
     def __len__(self):
-        return int(lib().heaac_sbr_table_count(C.c_void_p(self._h)))
+        return lib().heaac_sbr_table_count(self._h)
 
     def headers(self):
         """Copy of the entries so far as an SBR_HDR_DT array (what he_decode takes as `hdr`)."""
         n = len(self)
-        addr = lib().heaac_sbr_table_data(C.c_void_p(self._h))
+        addr = lib().heaac_sbr_table_data(self._h)
         buf = (C.c_uint8 * (n * SBR_HDR_DT.itemsize)).from_address(addr)
         return np.frombuffer(bytes(buf), dtype=SBR_HDR_DT).copy()
 
     def close(self):
         if self._h:
-            lib().heaac_sbr_table_destroy(C.c_void_p(self._h))
+            lib().heaac_sbr_table_destroy(self._h)
             self._h = None
 
     def __del__(self):
@@ -1228,10 +1127,8 @@ class SbrHeaderTable:
 
 def sbr_streams(n):
     """n fresh HeaacSbrStream records (opaque bytes, heaac_sbr_stream_init)."""
-    L = lib()
-    L.heaac_sbr_stream_bytes.restype = C.c_size_t
-    st = np.zeros((n, int(L.heaac_sbr_stream_bytes())), np.uint8)
-    L.heaac_sbr_stream_init(st.ctypes.data_as(C.c_void_p), C.c_size_t(n))
+    st = np.zeros((n, lib().heaac_sbr_stream_bytes()), np.uint8)
+    lib().heaac_sbr_stream_init(_np(st), n)
     return st
 
 
@@ -1244,19 +1141,16 @@ def sbr_parse_payload(stream, table, sample_rate, payload, channels, allow_ps, c
     sbr = np.zeros(1, SBR_FRAME_DT)
     ps = np.zeros(1, PS_FRAME_DT)
     info = np.zeros(1, SBR_PARSE_INFO_DT)
-    r = lib().heaac_sbr_parse_payload(stream.ctypes.data_as(C.c_void_p), C.c_void_p(table._h), C.c_int(sample_rate),
-                                      payload, C.c_int(len(payload)), C.c_int(bit),
-                                      C.c_int(len(payload) if cnt is None else cnt), C.c_int(bool(crc)),
-                                      C.c_int(channels), C.c_int(int(bool(allow_ps)) | (2 if misplaced else 0)),
-                                      sbr.ctypes.data_as(C.c_void_p), ps.ctypes.data_as(C.c_void_p),
-                                      info.ctypes.data_as(C.c_void_p))
+    r = lib().heaac_sbr_parse_payload(_np(stream), table._h, sample_rate, payload, len(payload), bit,
+                                      len(payload) if cnt is None else cnt, bool(crc), channels,
+                                      int(bool(allow_ps)) | (2 if misplaced else 0), _np(sbr), _np(ps), _np(info))
     return r, sbr, ps, info[0]
 
 
 def sbr_no_payload(stream, channels):
     """heaac_sbr_no_payload: the record of an access unit without an SBR payload for ONE stream record."""
     sbr = np.zeros(1, SBR_FRAME_DT)
-    lib().heaac_sbr_no_payload(stream.ctypes.data_as(C.c_void_p), C.c_int(channels), sbr.ctypes.data_as(C.c_void_p), None)
+    lib().heaac_sbr_no_payload(_np(stream), channels, _np(sbr), None)
     return sbr
 
 
@@ -1264,19 +1158,12 @@ def heaac_parse_batch(cfg, streams, sbr_st, table, aus, threads=0, with_ps=False
     """heaac_heaac_parse_batch: whole HE-AAC access units, one per stream.  streams: AAC_STREAM_DT [n],
     sbr_st: sbr_streams(n); both updated in place.  Returns the dict of aac_parse_batch plus sbr [n], ps [n]."""
     n = len(aus)
-    keep = [C.create_string_buffer(bytes(a), len(a)) for a in aus]
-    ptrs = (C.c_char_p * n)(*[C.cast(k, C.c_char_p) for k in keep])
-    sizes = (C.c_int * n)(*[len(a) for a in aus])
+    keep, ptrs, sizes = _units(aus)
     out = dict(coeffs=np.zeros((n, 2, 1024), np.float32), ics=np.zeros((n, 2), ICS_DT),
                tools=np.zeros(n, TOOLS_FRAME_DT), info=np.zeros(n, AAC_INFO_DT), status=np.zeros(n, np.int32),
                sbr=np.zeros(n, SBR_FRAME_DT), ps=np.zeros(n, PS_FRAME_DT))
     assert streams.dtype == AAC_STREAM_DT and streams.shape == (n,) and sbr_st.shape[0] == n
-    failed = lib().heaac_heaac_parse_batch(
-        C.byref(cfg), streams.ctypes.data_as(C.c_void_p), sbr_st.ctypes.data_as(C.c_void_p), C.c_void_p(table._h),
-        ptrs, sizes, C.c_size_t(n),
-        out["coeffs"].ctypes.data_as(C.c_void_p), out["ics"].ctypes.data_as(C.c_void_p),
-        out["tools"].ctypes.data_as(C.c_void_p), out["sbr"].ctypes.data_as(C.c_void_p),
-        out["ps"].ctypes.data_as(C.c_void_p) if with_ps else None,
-        out["info"].ctypes.data_as(C.c_void_p), out["status"].ctypes.data_as(C.c_void_p), C.c_int(threads))
-    out["failed"] = failed
+    out["failed"] = lib().heaac_heaac_parse_batch(
+        C.byref(cfg), _np(streams), _np(sbr_st), table._h, ptrs, sizes, n, _np(out["coeffs"]), _np(out["ics"]),
+        _np(out["tools"]), _np(out["sbr"]), _np(out["ps"]) if with_ps else None, _np(out["info"]), _np(out["status"]), threads)
     return out

@@ -22,8 +22,6 @@ def test_lc_streams_entry_point_declared_and_exported(pkg):
 def test_lc_streams_null_device_is_refused(pkg):
     L = pkg.lib()
     f = L.heaac_lc_decode_streams
-    f.restype = C.c_int
-    f.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.c_int, C.c_size_t, C.c_size_t, C.c_void_p]
     dummy = C.c_void_p(16)
     for channels in (1, 2):
         for S, T in ((1, 1), (4, 8), (0, 1)):

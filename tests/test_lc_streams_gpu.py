@@ -191,8 +191,6 @@ def test_lc_streams_edges(pkg, oracle, dev, profile, channels, fmtname):
 def test_lc_streams_argument_errors(pkg, dev):
     import torch
     f = pkg.lib().heaac_lc_decode_streams
-    f.restype = C.c_int
-    f.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.c_int, C.c_size_t, C.c_size_t, C.c_void_p]
     buf = torch.zeros(4 * 2 * 1024, device="cuda")
     p = C.c_void_p(buf.data_ptr())
     ERR = -1

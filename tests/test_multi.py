@@ -17,7 +17,6 @@ class HeShard(C.Structure):
 def test_partition_is_the_python_harness_partition(pkg):
     shard = importlib.import_module("ffmpeg_heaac_amd.shard")
     f = pkg.lib().heaac_multi_shard
-    f.restype = None
     for n in (0, 1, 7, 8, 9, 1000, 262144, 2 * 1024 * 1024 + 5):
         for G in (1, 2, 3, 4, 8, 16):
             covered = 0
@@ -51,7 +50,6 @@ def test_two_slots_decode_and_gather_like_one_context(pkg, oracle, dev):
     import torch
     synth = importlib.import_module("ffmpeg_heaac_amd.synth")
     lib = pkg.lib()
-    lib.heaac_multi_stream.restype = C.c_void_p
     rng = np.random.default_rng(12)
     cfg, n = pkg.CFG_HEV2, 301                                          # an odd count: shards of 151 and 150
     hdr = synth.default_headers(pkg)

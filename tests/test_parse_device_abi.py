@@ -34,8 +34,6 @@ def test_parse_device_entry_points_declared_and_exported(pkg):
 
 def test_parse_device_null_device_and_null_arrays_are_refused(pkg):
     f = pkg.lib().heaac_aac_parse_device
-    f.restype = C.c_int
-    f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int] + [C.c_void_p] * 6
     cfg = _cfg(pkg)
     dummy = C.c_void_p(64)
     for n in (0, 1, 4096):
@@ -43,8 +41,6 @@ def test_parse_device_null_device_and_null_arrays_are_refused(pkg):
             assert f(None, C.byref(cfg), dummy, dummy, dummy, n, cc, dummy, dummy, dummy, dummy, dummy, None) == HEAAC_ERR_ARG
     # the host form of the same call takes the same arrays: each of them NULL in turn
     g = pkg.lib().heaac_debug_aac_parse_core
-    g.restype = C.c_int
-    g.argtypes = [C.c_void_p] * 4 + [C.c_size_t, C.c_int] + [C.c_void_p] * 6
     st = np.zeros(1, pkg.AAC_STREAM_DT)
     au = np.zeros(16, np.uint8)
     off = np.array([0, 3], np.uint32)

@@ -110,8 +110,6 @@ def test_device_entry_refuses_bad_arguments_before_any_launch(pkg, dev):
     import ctypes as C
     import torch
     f = pkg.lib().heaac_aac_parse_device
-    f.restype = C.c_int
-    f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int] + [C.c_void_p] * 6
     n = 4
     aus = PC.in_scope_steps(np.random.default_rng(5), 3, 2, True, n, 1)[0]
     buf, off = pkg.pack_units(aus)

@@ -51,11 +51,7 @@ def test_entry_points_declared_with_their_signatures_and_exported(pkg):
 
 def test_null_device_and_bad_arguments_are_refused_before_any_launch(pkg):
     f = pkg.lib().heaac_aac_parse_device_streams
-    f.restype = C.c_int
-    f.argtypes = [C.c_void_p] * 5 + [C.c_size_t, C.c_size_t, C.c_int] + [C.c_void_p] * 8
     g = pkg.lib().heaac_heaac_parse_device_streams
-    g.restype = C.c_int
-    g.argtypes = [C.c_void_p] * 7 + [C.c_size_t, C.c_size_t, C.c_int] + [C.c_void_p] * 5 + [C.c_size_t] + [C.c_void_p] * 6
     cfg = _cfg(pkg)
     d = C.c_void_p(64)
     for S in (0, 1, 4096):

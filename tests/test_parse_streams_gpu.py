@@ -381,11 +381,7 @@ def test_device_entries_refuse_bad_arguments_before_any_launch(pkg, dev):
     output; S == 0 is HEAAC_OK; and the same arguments as they should be parse."""
     import torch
     f = pkg.lib().heaac_aac_parse_device_streams
-    f.restype = C.c_int
-    f.argtypes = [C.c_void_p] * 5 + [C.c_size_t, C.c_size_t, C.c_int] + [C.c_void_p] * 8
     g = pkg.lib().heaac_heaac_parse_device_streams
-    g.restype = C.c_int
-    g.argtypes = [C.c_void_p] * 7 + [C.c_size_t, C.c_size_t, C.c_int] + [C.c_void_p] * 5 + [C.c_size_t] + [C.c_void_p] * 6
     rng = np.random.default_rng(6800)
     S, T = 4, 2
     h = HeStreams(pkg, rng, S, False, "any")

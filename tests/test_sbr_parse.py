@@ -299,7 +299,6 @@ def test_sbr_tables_fingerprint(pkg):
     want = open(os.path.join(ROOT, "tests", "golden", "sbr_iso_tables.sha256")).read().split()[0]
     assert h == want
     L = pkg.lib()
-    L.heaac_sbr_tables_fingerprint.restype = C.c_uint64
     want_fnv = int(open(os.path.join(ROOT, "tests", "golden", "sbr_iso_tables.fnv")).read().split()[0], 16)
     assert L.heaac_sbr_tables_fingerprint() == want_fnv
     # every table is a complete prefix code (Kraft sum exactly 1): no bit pattern is undecodable

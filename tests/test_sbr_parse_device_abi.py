@@ -40,8 +40,6 @@ def _host_args(pkg, n=2, cpe=False):
 
 def _call(pkg, a, n, n_hdr=1, **over):
     g = pkg.lib().heaac_debug_sbr_parse_core
-    g.restype = C.c_int
-    g.argtypes = [C.c_void_p] * 7 + [C.c_size_t, C.c_void_p, C.c_size_t] + [C.c_void_p] * 4
     p = {k: (C.addressof(v) if k == "cfg" else v.ctypes.data) for k, v in a.items()}
     p.update(over)
     return g(p["cfg"], p["sst_in"], p["sst_out"], p["au"], p["off"], p["info"], p["aac"], n, p["hdr"], n_hdr, p["sbr"], p["ps"],
@@ -81,11 +79,7 @@ def test_a_null_device_is_refused(pkg):
     cfg = SD.he_cfg(pkg, False)
     d = C.c_void_p(64)
     f = pkg.lib().heaac_sbr_parse_device
-    f.restype = C.c_int
-    f.argtypes = [C.c_void_p] * 8 + [C.c_size_t, C.c_void_p, C.c_size_t] + [C.c_void_p] * 4
     g = pkg.lib().heaac_heaac_parse_device
-    g.restype = C.c_int
-    g.argtypes = [C.c_void_p] * 7 + [C.c_size_t, C.c_int] + [C.c_void_p] * 5 + [C.c_size_t] + [C.c_void_p] * 4
     for n in (0, 1, 4096):
         assert f(None, C.byref(cfg), d, d, d, d, d, d, n, d, 1, d, d, d, None) == HEAAC_ERR_ARG
         assert g(None, C.byref(cfg), d, d, d, d, d, n, 1, d, d, d, d, d, 1, d, d, d, None) == HEAAC_ERR_ARG

@@ -238,8 +238,6 @@ def test_device_entry_refuses_bad_arguments_before_any_launch(pkg, dev):
     HEAAC_ERR_ARG and write nothing; n = 0 is HEAAC_OK whatever the arrays are."""
     import torch
     f = pkg.lib().heaac_sbr_parse_device
-    f.restype = C.c_int
-    f.argtypes = [C.c_void_p] * 8 + [C.c_size_t, C.c_void_p, C.c_size_t] + [C.c_void_p] * 4
     rng = np.random.default_rng(8500)
     n = 4
     ch = DeviceChain(pkg, dev, n, False)

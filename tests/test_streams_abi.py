@@ -23,9 +23,6 @@ def test_streams_entry_point_declared_and_exported(pkg):
 def test_streams_null_device_is_refused(pkg):
     L = pkg.lib()
     f = L.heaac_he_decode_streams
-    f.restype = C.c_int
-    f.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4 + [C.c_size_t] + [C.c_void_p] * 4 + \
-        [C.c_int, C.c_size_t, C.c_size_t, C.c_void_p]
     dummy = C.c_void_p(16)
     for cfg in (pkg.CFG_HEV1, pkg.CFG_HEV1_MONO, pkg.CFG_HEV2):
         for S, T in ((1, 1), (4, 8), (0, 1)):

@@ -37,15 +37,8 @@ def test_null_device_is_refused(pkg):
     L = pkg.lib()
     dummy = C.c_void_p(16)
     lc = L.heaac_lc_decode_streams_ex
-    lc.restype = C.c_int
-    lc.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.c_int, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p]
     he = L.heaac_he_decode_streams_ex
-    he.restype = C.c_int
-    he.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4 + [C.c_size_t] + [C.c_void_p] * 4 + \
-                  [C.c_int, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p]
     tl = L.heaac_spectral_tools_streams_ex
-    tl.restype = C.c_int
-    tl.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 6 + [C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p]
     for hold in (None, dummy):
         for S, T in ((1, 1), (4, 8), (0, 1)):
             for channels in (1, 2):
@@ -122,8 +115,6 @@ def test_tools_wrapper_rejects_a_wrong_hold(pkg, monkeypatch, channels, bad):
 
 def _create_streams(pkg):
     f = pkg.lib().heaac_pipeline_create_streams
-    f.restype = C.c_int
-    f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_size_t, C.c_int]
     return f
 
 
@@ -155,8 +146,6 @@ def test_pipeline_create_streams_device_or_not(pkg):
     import torch
     f = _create_streams(pkg)
     g = pkg.lib().heaac_pipeline_frames_per_tick
-    g.restype = C.c_size_t
-    g.argtypes = [C.c_void_p]
     assert g(None) == 0
     good = _cfg(pkg)
     for T in (1, 2, 8):

@@ -379,8 +379,6 @@ def test_tools_streams_golden_bitstreams(pkg, dev, name):
 def test_tools_streams_argument_errors(pkg, dev):
     import torch
     f = pkg.lib().heaac_spectral_tools_streams
-    f.restype = C.c_int
-    f.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 6 + [C.c_size_t, C.c_size_t, C.c_void_p]
     buf = torch.zeros(4 * 2 * 1024, device="cuda")
     p = C.c_void_p(buf.data_ptr())
     ERR = -1

@@ -175,6 +175,39 @@ def random_ics(rng, si, aot, allow_intensity, quiet=False):
     return d
 
 
+def planned_ics(si, eight, max_sfb, band_type, sf_delta=None, q=None, global_gain=120, grouping=None, noise_start=None,
+                noise_level=100, sections=None, window_sequence=None, window_shape=0):
+    """Side info of one channel from a PLAN instead of draws (the dict random_ics returns): band_type [groups][max_sfb],
+    sf_delta alike (written as they stand, also where an accumulator leaves 0 .. 255), q = {(group, band): lines
+    [group_len][width]} (bands left out: zeros), grouping = the 7 bits of an eight-short frame, noise_start = the 9 bits
+    of the first noise band as sent, sections = [(band type, run)] per group where the runs are not those of band_type.
+    No TNS, pulse or prediction data."""
+    off = swb(si, eight)
+    d = dict(window_sequence=(2 if eight else 0) if window_sequence is None else window_sequence, window_shape=window_shape,
+             max_sfb=max_sfb, eight=bool(eight), off=off, num_swb=len(off) - 1, predictor_present=0, pulse=None, tns=None,
+             planned=True, global_gain=global_gain, noise_level=noise_level, noise_start=noise_start, sections=sections)
+    d["group_len"] = [1]
+    if eight:
+        d["grouping"] = list(grouping if grouping is not None else [1] * 7)
+        lens, cur = [], 1
+        for gbit in d["grouping"]:
+            if gbit:
+                cur += 1
+            else:
+                lens.append(cur); cur = 1
+        d["group_len"] = lens + [cur]
+    ng = len(d["group_len"])
+    d["band_type"] = np.array(band_type, int).reshape(ng, max_sfb)
+    d["sf_delta"] = np.zeros((ng, max_sfb), int) if sf_delta is None else np.array(sf_delta, int).reshape(ng, max_sfb)
+    d["q"] = {}
+    for g in range(ng):
+        for i in range(max_sfb):
+            if 1 <= d["band_type"][g, i] <= 11:
+                v = (q or {}).get((g, i))
+                d["q"][(g, i)] = np.zeros((d["group_len"][g], off[i + 1] - off[i]), int) if v is None else np.array(v, int)
+    return d
+
+
 def put_ics_info(bw, d, si, aot):
     bw.put(0, 1)
     bw.put(d["window_sequence"], 2); bw.put(d["window_shape"], 1)
@@ -202,21 +235,27 @@ def put_ics(bw, d, si, aot, common_window):
     nb = 3 if eight else 5
     esc = (1 << nb) - 1
     for g in range(ng):                                    # section_data
+        runs = []
         k = 0
         while k < ms:
             b = d["band_type"][g, k]
             e = k
             while e < ms and d["band_type"][g, e] == b:
                 e += 1
+            runs.append((int(b), e - k))
+            k = e
+        if d.get("sections") is not None:                  # a plan's own runs: equal neighbours apart, a run too long
+            runs = d["sections"][g]
+        for b, ln in runs:
             bw.put(int(b), 4)
-            ln = e - k
             while ln >= esc:
                 bw.put(esc, nb); ln -= esc
             bw.put(ln, nb)
-            k = e
     # scale_factor_data: three differential chains
     gain, noise, pos = d["global_gain"], d["global_gain"] - 90, 100
     noise_flag = True
+    planned = bool(d.get("planned"))                       # a plan's deltas are written as they stand
+    landed = []                                            # every value an accumulator takes
     sf_offset = 12 if eight else 0
     exp_sf = np.zeros(128, np.float32)
     idx = 0
@@ -227,26 +266,34 @@ def put_ics(bw, d, si, aot, common_window):
             if b == 0:
                 pass
             elif b in (14, 15):
-                if not 0 <= pos + dl <= 255:
+                if not planned and not 0 <= pos + dl <= 255:
                     dl = 0
                 put_sf(bw, dl); pos += dl
+                landed.append(pos)
                 exp_sf[idx] = np.float32(2.0 ** ((-pos + 300 - 200) / 4.0))
             elif b == 13:
                 if noise_flag:
                     noise_flag = False
-                    bw.put(d["noise_level"] - noise + 256, 9)      # offset[1] += get_bits(9) - 256
-                    noise = d["noise_level"]
+                    if planned and d.get("noise_start") is not None:
+                        bw.put(d["noise_start"], 9)                # the 9 bits themselves, wherever they land
+                        noise += d["noise_start"] - 256
+                    else:
+                        bw.put(d["noise_level"] - noise + 256, 9)  # offset[1] += get_bits(9) - 256
+                        noise = d["noise_level"]
                 else:
-                    if not 0 <= noise + dl <= 255:
+                    if not planned and not 0 <= noise + dl <= 255:
                         dl = 0
                     put_sf(bw, dl); noise += dl
+                landed.append(noise)
                 exp_sf[idx] = -np.float32(2.0 ** ((noise + sf_offset + 100 - 200) / 4.0))
             else:
-                if not 0 <= gain + dl <= 255:
+                if not planned and not 0 <= gain + dl <= 255:
                     dl = 0
                 put_sf(bw, dl); gain += dl
+                landed.append(gain)
                 exp_sf[idx] = -np.float32(2.0 ** ((gain + sf_offset - 200) / 4.0))
             idx += 1
+    d["sf_in_range"] = all(0 <= v <= 255 for v in landed)  # decode_scalefactors refuses the unit otherwise
     p = d["pulse"]
     bw.put(1 if p else 0, 1)
     if p:

@@ -122,7 +122,9 @@ class Channel:
         self.pointer = 0
 
     # -- grid ---------------------------------------------------------------------------------
-    def draw_grid(self, rng, bw, amp_res_header, varfrac):
+    def draw_grid(self, rng, bw, amp_res_header, varfrac, plan=None):
+        """plan: dict(L = 1 | 2 | 4, freq_res = 0 | 1) for a FIXFIX grid instead of a drawn one (a planned stream never
+        leaves a border behind the frame, so that grid always fits)."""
         num_env_old = self.num_env
         carry = max(self.t_env[self.num_env] - 16, 0)
         self.freq_res[0] = self.freq_res[self.num_env]
@@ -130,11 +132,12 @@ class Channel:
         while True:
             amp = amp_res_header
             pointer = 0
-            if carry == 0 and rng.random() >= varfrac:
+            if plan is not None or (carry == 0 and rng.random() >= varfrac):
+                assert carry == 0
                 cls = 0
-                L = int(rng.choice([1, 2, 4]))
+                L = int(plan["L"] if plan is not None else rng.choice([1, 2, 4]))
                 t = [0] + [((16 + (L >> 1)) // L) * (i + 1) for i in range(L - 1)] + [16]
-                fr = [int(rng.integers(0, 2))] * L
+                fr = [int(plan["freq_res"] if plan is not None else rng.integers(0, 2))] * L
                 w = Bits(); w.put(0, 2); w.put({1: 0, 2: 1, 4: 2}[L], 2); w.put(fr[0], 1)
                 if L == 1:
                     amp = 0
@@ -234,7 +237,10 @@ class Channel:
         self.e_a[1] = src.e_a[1]
 
     # -- envelopes ----------------------------------------------------------------------------
-    def draw_dtdf(self, rng, bw):
+    def draw_dtdf(self, rng, bw, plan=None):
+        if plan is not None:                       # put_envelope / put_noise take the directions from the plan
+            self.df_env, self.df_noise = [0] * self.num_env, [0] * self.num_noise
+            return
         self.df_env = [int(rng.integers(0, 2)) for _ in range(self.num_env)]
         self.df_noise = [int(rng.integers(0, 2)) for _ in range(self.num_noise)]
 
@@ -242,10 +248,10 @@ class Channel:
         for f in self.df_env + self.df_noise:
             bw.put(f, 1)
 
-    def draw_invf(self, rng, bw, n_q):
+    def draw_invf(self, rng, bw, n_q, plan=None):
         self.invf[1] = list(self.invf[0])
         for i in range(n_q):
-            self.invf[0][i] = int(rng.integers(0, 4))
+            self.invf[0][i] = int(plan.get("invf", [0] * 5)[i] if plan is not None else rng.integers(0, 4))
             bw.put(self.invf[0][i], 2)
 
     @staticmethod
@@ -255,7 +261,9 @@ class Channel:
             v.append(int(np.clip(v[-1] + rng.integers(-step, step + 1), lo, hi)))
         return v
 
-    def put_envelope(self, rng, bw, n, balance):
+    def put_envelope(self, rng, bw, n, balance, plan=None):
+        """plan["env"](i, ref, nb, delta, tt, ft, start_bits) -> (direction flag, targets [nb]): the targets are written as
+        they stand, also where they leave the record's 0 .. 255 (ref: the values a time-direction delta starts from)."""
         delta = 2 if balance else 1
         odd = n[1] & 1
         if balance:
@@ -269,7 +277,6 @@ class Channel:
         for i in range(self.num_env):
             res = self.freq_res[i + 1]
             nb = n[res]
-            target = [delta * v for v in self._walk(rng, nb, lo, hi, step)]
             prev = self.env[i]
             if res == self.freq_res[i]:
                 ref = [prev[j] for j in range(nb)]
@@ -277,8 +284,14 @@ class Channel:
                 ref = [prev[(j + odd) >> 1] for j in range(nb)]
             else:
                 ref = [prev[2 * j - odd if j else 0] for j in range(nb)]
+            if plan is not None:
+                self.df_env[i], target = plan["env"](i, [int(x) for x in ref], nb, delta, tt, ft, start_bits)
+                assert len(target) == nb
+            else:
+                target = [delta * v for v in self._walk(rng, nb, lo, hi, step)]
             d = [(target[j] - int(ref[j])) for j in range(nb)]
             if self.df_env[i] and not all(x % delta == 0 and abs(x // delta) <= lav for x in d):
+                assert plan is None, "a planned envelope must be expressible in its direction"
                 self.df_env[i] = 0                                        # not expressible in the time direction
             self._pending_env.append((i, target, d, start_bits, tt, ft, delta))
             self.env[i + 1, :nb] = target          # beyond nb a row keeps what it held, as in a decoder
@@ -295,7 +308,8 @@ class Channel:
                     bw.sbr(ft, (target[j] - target[j - 1]) // delta)
         self._pending_env = []
 
-    def put_noise(self, rng, n_q, balance):
+    def put_noise(self, rng, n_q, balance, plan=None):
+        """plan["noise"](i, ref, n_q, delta, tt, ft, 5) -> (direction flag, targets [n_q]), as for put_envelope."""
         delta = 2 if balance else 1
         tt = "t_noise_bal_30" if balance else "t_noise_30"
         ft = "f_env_bal_30" if balance else "f_env_30"
@@ -303,9 +317,14 @@ class Channel:
         lav = T["sbr_lav"][tt]
         self._pending_noise = []
         for i in range(self.num_noise):
-            target = [delta * v for v in self._walk(rng, n_q, lo, hi, step)]
+            if plan is not None:
+                self.df_noise[i], target = plan["noise"](i, [int(x) for x in self.noise[i][:n_q]], n_q, delta, tt, ft, 5)
+                assert len(target) == n_q
+            else:
+                target = [delta * v for v in self._walk(rng, n_q, lo, hi, step)]
             d = [target[j] - int(self.noise[i][j]) for j in range(n_q)]
             if self.df_noise[i] and not all(x % delta == 0 and abs(x // delta) <= lav for x in d):
+                assert plan is None, "a planned noise floor must be expressible in its direction"
                 self.df_noise[i] = 0
             self._pending_noise.append((i, target, d, tt, ft, delta))
             self.noise[i + 1, :n_q] = target
@@ -322,8 +341,8 @@ class Channel:
                     bw.sbr(ft, (target[j] - target[j - 1]) // delta)
         self._pending_noise = []
 
-    def draw_harmonics(self, rng, bw, n_high):
-        self.harm_flag = int(rng.random() < 0.3)
+    def draw_harmonics(self, rng, bw, n_high, plan=None):
+        self.harm_flag = int(rng.random() < 0.3) if plan is None else 0
         bw.put(self.harm_flag, 1)
         if self.harm_flag:
             for i in range(n_high):
@@ -366,9 +385,22 @@ class PsModel:
         self.ipd = np.zeros((5, 34), int)
         self.opd = np.zeros((5, 34), int)
 
-    def _put_par(self, rng, bw, par, num, e, table_df, table_dt, lo, hi, mask=False):
-        dt = int(rng.integers(0, 2))
+    def _put_par(self, rng, bw, par, num, e, table_df, table_dt, lo, hi, mask=False, plan=None):
         e_prev = max(e - 1 if e else self.num_env_old - 1, 0)
+        if plan is not None:                      # (dt, targets) as the plan states them; they must be expressible
+            dt, target = plan["par"](table_df, table_dt, e, [int(v) for v in par[e_prev][:num]], num)
+            assert len(target) == num
+            bw.put(dt, 1)
+            table = table_dt if dt else table_df
+            off = 0 if mask else T["ps_offset"][table]
+            last = 0
+            for b in range(num):
+                d = target[b] - (int(par[e_prev][b]) if dt else last)
+                bw.huff(table, (d & 7) if mask else d + off)
+                last = target[b]
+            par[e, :num] = target
+            return
+        dt = int(rng.integers(0, 2))
         if dt:                                    # mostly small steps from the previous envelope: short codes
             target = [int(np.clip(int(par[e_prev][b]) + rng.integers(-1, 2) * (rng.random() < 0.4), lo, hi))
                       for b in range(num)]
@@ -390,13 +422,17 @@ class PsModel:
             last = target[b]
         par[e, :num] = target
 
-    def draw(self, rng, force_header=False, modes="any", explicit=0.3, ext_junk=True):
-        """Returns the bits of one ps_data()."""
+    def draw(self, rng, force_header=False, modes="any", explicit=0.3, ext_junk=True, plan=None):
+        """Returns the bits of one ps_data().  plan: nothing is drawn -- dict(header = (enable_iid, iid_mode, enable_icc,
+        icc_mode, enable_ext) or None, num_env = 0 | 1 | 2 | 4 (evenly cut) or borders = the transmitted ones, ipdopd =
+        the enable bit of the extension, par = the callable of _put_par)."""
         bw = Bits()
-        header = int(force_header or not self.start or rng.random() < 0.3)
+        header = int(force_header or not self.start or rng.random() < 0.3) if plan is None else int(plan.get("header") is not None)
         bw.put(header, 1)
         if header:
-            if modes == "20":
+            if plan is not None:
+                en_iid, iid_mode, en_icc, icc_mode, en_ext = plan["header"]
+            elif modes == "20":
                 en_iid, iid_mode, en_icc, icc_mode, en_ext = 1, int(rng.choice([0, 1])), 1, int(rng.choice([0, 1])), 0
             elif modes == "34":
                 en_iid, iid_mode, en_icc, icc_mode, en_ext = 1, int(rng.choice([2, 5])), 1, int(rng.choice([2, 5])), 1
@@ -416,18 +452,23 @@ class PsModel:
                 self.icc_mode, self.nr_icc = icc_mode, self.NR[icc_mode]
             self.enable_ext = en_ext
             bw.put(en_ext, 1)
-        cls = int(rng.random() < explicit)
+        if plan is not None:
+            cls = int(plan.get("borders") is not None)
+            idx = len(plan["borders"]) - 1 if cls else [0, 1, 2, 4].index(plan["num_env"])
+        else:
+            cls = int(rng.random() < explicit)
         bw.put(cls, 1)
         self.num_env_old = self.num_env
-        idx = int(rng.integers(0, 4))
-        if header and not cls and not idx and self.enable_iid and not self.iid_quant and np.abs(self.iid).max() > 7:
-            idx = 1          # an envelope borrowed from a frame of the finer quantiser would leave the coarse range
+        if plan is None:
+            idx = int(rng.integers(0, 4))
+            if header and not cls and not idx and self.enable_iid and not self.iid_quant and np.abs(self.iid).max() > 7:
+                idx = 1      # an envelope borrowed from a frame of the finer quantiser would leave the coarse range
         bw.put(idx, 2)
         self.num_env = [[0, 1, 2, 4], [1, 2, 3, 4]][cls][idx]
         E = self.num_env
         self.border[0] = -1
         if cls:
-            cuts = sorted(int(x) for x in rng.choice(np.arange(0, 32), size=E, replace=False))
+            cuts = list(plan["borders"]) if plan is not None else sorted(int(x) for x in rng.choice(np.arange(0, 32), size=E, replace=False))
             for e in range(1, E + 1):
                 self.border[e] = cuts[e - 1]
                 bw.put(cuts[e - 1], 5)
@@ -438,29 +479,31 @@ class PsModel:
             lim = 15 if self.iid_quant else 7
             for e in range(E):
                 self._put_par(rng, bw, self.iid, self.nr_iid, e, "iid_df1" if self.iid_quant else "iid_df0",
-                              "iid_dt1" if self.iid_quant else "iid_dt0", -lim, lim)
+                              "iid_dt1" if self.iid_quant else "iid_dt0", -lim, lim, plan=plan)
         else:
             self.iid[:] = 0
         if self.enable_icc:
             for e in range(E):
-                self._put_par(rng, bw, self.icc, self.nr_icc, e, "icc_df", "icc_dt", 0, 7)
+                self._put_par(rng, bw, self.icc, self.nr_icc, e, "icc_df", "icc_dt", 0, 7, plan=plan)
         else:
             self.icc[:] = 0
         if self.enable_ext:
             x = Bits()
             x.put(0, 2)                                                   # ps_extension_id 0: ipd / opd
-            en = int(rng.random() < 0.8)
+            en = int(rng.random() < 0.8) if plan is None else int(plan.get("ipdopd", 1))
             x.put(en, 1)
             self.enable_ipdopd = en
             if en:
                 for e in range(E):
-                    self._put_par(rng, x, self.ipd, self.nr_ipdopd, e, "ipd_df", "ipd_dt", 0, 7, mask=True)
-                    self._put_par(rng, x, self.opd, self.nr_ipdopd, e, "opd_df", "opd_dt", 0, 7, mask=True)
+                    self._put_par(rng, x, self.ipd, self.nr_ipdopd, e, "ipd_df", "ipd_dt", 0, 7, mask=True, plan=plan)
+                    self._put_par(rng, x, self.opd, self.nr_ipdopd, e, "opd_df", "opd_dt", 0, 7, mask=True, plan=plan)
             x.put(0, 1)                                                   # reserved_ps
-            if ext_junk and rng.random() < 0.5:
+            if plan is None and ext_junk and rng.random() < 0.5:
                 for _ in range(int(rng.integers(1, 9))):                  # reserved extension ids: stepped over
                     x.put(3, 2)
             cnt = (len(x) + 7) // 8
+            if plan is not None and cnt > 270:
+                raise OverflowError("a planned extension longer than its count field can say")
             if cnt >= 15:
                 bw.put(15, 4); bw.put(cnt - 15, 8)
             else:
@@ -468,7 +511,10 @@ class PsModel:
             pad = 8 * cnt - len(x)
             bw.bits.extend(x.bits)
             # the tail is < 8 bits and is skipped unread
-            bw.bits.extend(int(b) for b in rng.integers(0, 2, pad))
+            if plan is None:
+                bw.bits.extend(int(b) for b in rng.integers(0, 2, pad))
+            else:
+                bw.bits.extend([0] * pad)
         # envelope fix-up
         if not E or self.border[E] < 31:
             source = E - 1 if E else self.num_env_old - 1
@@ -527,19 +573,27 @@ class SbrStreamWriter:
         self.kx_m = (32, 0)
         self.coupling = 0
 
-    def frame(self, rng, new_header=None, crc=False, respec=False):
+    def frame(self, rng, new_header=None, crc=False, respec=False, plan=None):
         """new_header: None = only when needed (first frame); True = send one (same spectrum unless respec).
+        plan: nothing is drawn (rng may be None) -- dict(header = the header to send with new_header (all fields of
+        draw_header), coupling, ch = [channel plan] * channels (draw_grid, put_envelope, put_noise), ps = a plan of
+        PsModel.draw or None for a frame without PS data).
         Returns (bits, dict(sbr=HeaacSbrFrame record, ps=record or None, hdr=HeaacSbrHeader record, reset))."""
         pkg = self.pkg
         bw = Bits()
+        pc = plan["ch"] if plan is not None else [None, None]
         if crc:
-            bw.put(int(rng.integers(0, 1024)), 10)
+            bw.put(int(rng.integers(0, 1024)) if plan is None else 0x2a5, 10)
         kx_old, m_old = self.kx_m
         reset = 0
         send = self.header is None or bool(new_header)
         bw.put(int(send), 1)
         if send:
-            if self.header is None or respec:
+            if plan is not None:
+                h = dict(plan["header"])
+                reset = int(self.header is None or any(h[k] != self.header[k] for k in (
+                    "start_freq", "stop_freq", "xover", "freq_scale", "alter_scale", "noise_bands")))
+            elif self.header is None or respec:
                 while True:
                     h = draw_header(rng)
                     if self.header is None or any(h[k] != self.header[k] for k in ("start_freq", "stop_freq", "xover",
@@ -559,59 +613,62 @@ class SbrStreamWriter:
         amp_hdr = self.header["amp_res"]
         c0, c1 = self.ch
         if self.channels == 1:
-            extra = int(rng.random() < 0.2)
+            extra = int(rng.random() < 0.2) if plan is None else 0
             bw.put(extra, 1)
             if extra:
                 bw.put(int(rng.integers(0, 16)), 4)
-            c0.draw_grid(rng, bw, amp_hdr, self.varfrac)
-            c0.draw_dtdf(rng, bw)
+            c0.draw_grid(rng, bw, amp_hdr, self.varfrac, pc[0])
+            c0.draw_dtdf(rng, bw, pc[0])
             x = Bits()
-            c0.draw_invf(rng, x, n_q)
-            c0.put_envelope(rng, x, n, False)
-            c0.put_noise(rng, n_q, False)
+            c0.draw_invf(rng, x, n_q, pc[0])
+            c0.put_envelope(rng, x, n, False, pc[0])
+            c0.put_noise(rng, n_q, False, pc[0])
             c0.put_dtdf(bw)
             bw.bits.extend(x.bits)
             c0.flush_envelope(bw)
             c0.flush_noise(bw)
-            c0.draw_harmonics(rng, bw, n[1])
+            c0.draw_harmonics(rng, bw, n[1], pc[0])
         else:
-            extra = int(rng.random() < 0.2)
+            extra = int(rng.random() < 0.2) if plan is None else 0
             bw.put(extra, 1)
             if extra:
                 bw.put(int(rng.integers(0, 256)), 8)
-            self.coupling = int(rng.random() < self.coupling_p)
+            self.coupling = int(rng.random() < self.coupling_p) if plan is None else int(plan["coupling"])
             bw.put(self.coupling, 1)
             if self.coupling:
-                c0.draw_grid(rng, bw, amp_hdr, self.varfrac)
+                c0.draw_grid(rng, bw, amp_hdr, self.varfrac, pc[0])
                 c1.copy_grid(c0)
-                c0.draw_dtdf(rng, bw); c1.draw_dtdf(rng, bw)
+                c0.draw_dtdf(rng, bw, pc[0]); c1.draw_dtdf(rng, bw, pc[1])
                 x = Bits()
-                c0.draw_invf(rng, x, n_q)
+                c0.draw_invf(rng, x, n_q, pc[0])
                 c1.invf[1] = list(c1.invf[0])
                 c1.invf[0] = list(c0.invf[0])
-                c0.put_envelope(rng, x, n, False); c0.put_noise(rng, n_q, False)
-                c1.put_envelope(rng, x, n, True); c1.put_noise(rng, n_q, True)
+                c0.put_envelope(rng, x, n, False, pc[0]); c0.put_noise(rng, n_q, False, pc[0])
+                c1.put_envelope(rng, x, n, True, pc[1]); c1.put_noise(rng, n_q, True, pc[1])
                 c0.put_dtdf(bw); c1.put_dtdf(bw)
                 bw.bits.extend(x.bits)
                 c0.flush_envelope(bw); c0.flush_noise(bw)
                 c1.flush_envelope(bw); c1.flush_noise(bw)
             else:
-                c0.draw_grid(rng, bw, amp_hdr, self.varfrac)
-                c1.draw_grid(rng, bw, amp_hdr, self.varfrac)
-                c0.draw_dtdf(rng, bw); c1.draw_dtdf(rng, bw)
+                c0.draw_grid(rng, bw, amp_hdr, self.varfrac, pc[0])
+                c1.draw_grid(rng, bw, amp_hdr, self.varfrac, pc[1])
+                c0.draw_dtdf(rng, bw, pc[0]); c1.draw_dtdf(rng, bw, pc[1])
                 x = Bits()
-                c0.draw_invf(rng, x, n_q); c1.draw_invf(rng, x, n_q)
-                c0.put_envelope(rng, x, n, False); c1.put_envelope(rng, x, n, False)
-                c0.put_noise(rng, n_q, False); c1.put_noise(rng, n_q, False)
+                c0.draw_invf(rng, x, n_q, pc[0]); c1.draw_invf(rng, x, n_q, pc[1])
+                c0.put_envelope(rng, x, n, False, pc[0]); c1.put_envelope(rng, x, n, False, pc[1])
+                c0.put_noise(rng, n_q, False, pc[0]); c1.put_noise(rng, n_q, False, pc[1])
                 c0.put_dtdf(bw); c1.put_dtdf(bw)
                 bw.bits.extend(x.bits)
                 c0.flush_envelope(bw); c1.flush_envelope(bw)
                 c0.flush_noise(bw); c1.flush_noise(bw)
-            c0.draw_harmonics(rng, bw, n[1])
-            c1.draw_harmonics(rng, bw, n[1])
+            c0.draw_harmonics(rng, bw, n[1], pc[0])
+            c1.draw_harmonics(rng, bw, n[1], pc[1])
         # extended data
         ps_bits = None
-        if self.ps is not None and rng.random() < 0.9:
+        if plan is not None:
+            if self.ps is not None and plan.get("ps") is not None:
+                ps_bits = self.ps.draw(None, plan=plan["ps"])      # (the caller sees to it that the payload fits)
+        elif self.ps is not None and rng.random() < 0.9:
             import copy
             keep = copy.deepcopy(self.ps)
             while True:                                                    # bs_extension_size + bs_esc_count <= 270 bytes
@@ -619,7 +676,7 @@ class SbrStreamWriter:
                 if len(ps_bits) + 2 <= 8 * 270:
                     break
                 self.ps = copy.deepcopy(keep)
-        junk = rng.random() < 0.15
+        junk = plan is None and rng.random() < 0.15
         if ps_bits is None and not junk:
             bw.put(0, 1)
         else:
@@ -632,6 +689,8 @@ class SbrStreamWriter:
                 x.put(int(rng.choice([0, 1, 3])), 2)                       # reserved extension: skipped whole
                 x.bits.extend(int(b) for b in rng.integers(0, 2, int(rng.integers(6, 40))))
             cnt = (len(x) + 7) // 8
+            if plan is not None and cnt > 270:
+                raise OverflowError("a planned extension longer than its count field can say")
             if cnt >= 15:
                 bw.put(15, 4); bw.put(cnt - 15, 8)
             else:

@@ -797,18 +797,25 @@ def adts_split(buf):
     return out, (h if (out["kind"] != ADTS_JUNK).any() and ((out["kind"] == ADTS_FRAME) | (out["kind"] == ADTS_TRUNCATED)).any() else None)
 
 
+PIPELINE_DEVICE_PARSE = 1         # heaac_pipeline.h
+
+
 class Pipeline:
     """include/heaac_pipeline.h: access units in host memory -> int16 PCM in host memory, ticks overlapped."""
 
-    def __init__(self, aac_cfg, he_cfg, n_streams, threads=0, frames_per_tick=1):
+    def __init__(self, aac_cfg, he_cfg, n_streams, threads=0, frames_per_tick=1, device_parse=False):
         """frames_per_tick = T > 1: every tick carries T consecutive access units of each stream
-        (heaac_pipeline_create_streams), unit t of stream s at s * T + t."""
+        (heaac_pipeline_create_streams), unit t of stream s at s * T + t.  device_parse: the units are parsed on the GPU
+        (heaac_pipeline_create_ex with HEAAC_PIPELINE_DEVICE_PARSE); PCM and statuses are the same."""
         self._h = C.c_void_p()
         self.n, self.ch, self.len = n_streams, OUT_CH[he_cfg], OUT_LEN[he_cfg]
         self.T = int(frames_per_tick)
         if self.len == 2048 and aac_cfg.ext_sample_rate and aac_cfg.ext_sample_rate < 2 * aac_cfg.sample_rate:
             self.len = 1024                                # downsampled SBR: the output at the core rate
-        if self.T == 1:
+        if device_parse:
+            _check(lib().heaac_pipeline_create_ex(C.byref(self._h), C.byref(aac_cfg), he_cfg, n_streams, max(self.T, 0), threads,
+                                                  PIPELINE_DEVICE_PARSE), "heaac_pipeline_create_ex")
+        elif self.T == 1:
             _check(lib().heaac_pipeline_create(C.byref(self._h), C.byref(aac_cfg), he_cfg, n_streams, threads),
                    "heaac_pipeline_create")
         else:
@@ -840,6 +847,12 @@ class Pipeline:
         ms = (C.c_float * 4)()
         lib().heaac_pipeline_timing(self._h, ms)
         return dict(parse=ms[0], h2d=ms[1], gpu=ms[2], d2h=ms[3])
+
+    def parse_counts(self):
+        """(units the device walk took, units the host parser was handed), cumulative since create"""
+        c = (C.c_ulonglong * 2)()
+        lib().heaac_pipeline_parse_counts(self._h, c)
+        return int(c[0]), int(c[1])
 
     def close(self):
         if self._h:

@@ -72,6 +72,33 @@ int heaac_failed_lists(hipStream_t s, const unsigned char *failed, size_t n, uns
 // old area is in flight then, the caller frees it) and *rows = first, doubled until it holds them, at most n.
 int heaac_park_grow(hipStream_t s, size_t needed, size_t have, size_t first, size_t n, size_t *rows);
 
+// ---- the kernels of a device-parse tick (k_fix.hip; pipeline.hip) ----
+// The five record arrays of a tick, in the order coefficients, HeaacIcs, tools, SBR, PS: where the tick's rows and the
+// staged rows begin and the 32-bit words of one unit's row (0: the configuration has no such array).
+#define HEAAC_FIX_ARRAYS 5
+struct HeaacFixRows {
+    uint32_t *dst[HEAAC_FIX_ARRAYS];
+    const uint32_t *src[HEAAC_FIX_ARRAYS];
+    uint32_t words[HEAAC_FIX_ARRAYS];
+};
+// Behind the walk: host_status[i] (the device's view of mapped host memory; NULL: not wanted) = d_status[i], with
+// HEAAC_PARSE_OK -> HEAAC_PARSE_NO_SBR where an HE unit had no payload (sbr_off: the configuration has no SBR at all);
+// d_hold_tools[0 .. nf) = 0.
+__attribute__((visibility("hidden"))) int heaac_launch_parse_status(hipStream_t s, const int32_t *d_status,
+                                                                    const HeaacAacFrameInfo *d_info, int he, int sbr_off,
+                                                                    int32_t *host_status, uint8_t *d_hold_tools, size_t nf);
+// State rows d_list[j] of d_ast (and of d_sst unless NULL) -> row j of the compact buffers (device memory, or the
+// device's view of mapped host memory), j < m.
+__attribute__((visibility("hidden"))) int heaac_launch_fix_gather(hipStream_t s, const uint32_t *d_list, size_t m,
+                                                                  const HeaacAacStream *d_ast, void *d_g_ast,
+                                                                  const HeaacSbrStream *d_sst, void *d_g_sst);
+// Staged unit u < units: its rows to row d_dest[u] of the tick's arrays, d_staged_hold[u] and [units + u] to d_hold
+// [d_dest[u]] and [nf + d_dest[u]]; the compact state rows back to the rows d_list names.
+__attribute__((visibility("hidden"))) int heaac_launch_fix_scatter(hipStream_t s, const HeaacFixRows *rows, const uint32_t *d_dest,
+                                                                   size_t units, const uint8_t *d_staged_hold, uint8_t *d_hold,
+                                                                   size_t nf, const uint32_t *d_list, size_t m, const void *d_g_ast,
+                                                                   HeaacAacStream *d_ast, const void *d_g_sst, HeaacSbrStream *d_sst);
+
 // ---- the device (capi.hip) ----
 // The most frames per stream heaac_he_decode_streams(_ex) takes on this device: a stream's frames go through one
 // workspace set.  The call's own argument check and heaac_pipeline_create_streams both ask here.

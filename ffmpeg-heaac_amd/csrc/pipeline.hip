@@ -11,6 +11,12 @@
 // 32 k streams) while the slowest stage takes 7 ms, so four ticks must overlap to keep every stage busy.
 // Event order per set s:  in waits run_done[s] of the tick that used s last (its inputs are free again); run waits
 // in_done[s] and that tick's out_done[s] (its PCM buffer is free); out waits run_done[s].
+//
+// HEAAC_PIPELINE_DEVICE_PARSE (heaac_pipeline_create_ex) replaces the first two stages: the tick's units are packed into
+// one pinned byte buffer (pipeline_pack.h), uploaded, and parsed by the walk of k_parse_streams.hip on `in`, the parser
+// states on the device; submit waits for the walk's stop positions and finishes the streams it stopped on the host pool
+// from their gathered states, the records of those units scattered into the tick's rows (k_fix.hip) -- all on `in`, so
+// the next tick's walk reads the states the fix-up left.  The GPU stage is the streams calls for every T.
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
 #include <string.h>
@@ -18,6 +24,8 @@
 #include "heaac_pipeline.h"
 #include "codec_layout.h"        // heaac_sbr_output_mode
 #include "host_common.h"
+#include "heaac_debug.h"
+#include "pipeline_pack.h"
 
 #define PL_MAX_HDRS 4096
 #define PL_DEPTH HEAAC_PIPELINE_DEPTH
@@ -38,6 +46,21 @@ struct Set {
     // (failed == 1 of the one-unit tick; failed == 2 is hold_dsp alone)
     uint8_t *h_hold, *d_hold;
     int any_held;                   // some byte of hold_dsp is set (hold_tools is a subset): the masks are uploaded and passed
+    // device parse: the tick's units laid end to end (grown on demand) and their offsets [nf + 1], pinned / device
+    uint8_t *h_bytes, *d_bytes; size_t bytes_cap;
+    uint32_t *h_off, *d_off;
+};
+
+// Device parse: the records the host parser made of the units the walk deferred, compact (staged unit u belongs at row
+// dest[u] of the tick's arrays), pinned and device; grown on demand.  One area for all sets: `done` (recorded behind the
+// scatter) says when the pinned half may be written again.
+struct Staging {
+    size_t cap;                     // units
+    float *h_coeffs, *d_coeffs; HeaacIcs *h_ics, *d_ics; HeaacToolsFrame *h_tools, *d_tools;
+    HeaacSbrFrame *h_sbr, *d_sbr; HeaacPsFrame *h_ps, *d_ps;
+    uint8_t *h_hold, *d_hold;       // [2 units]: hold_dsp of every staged unit, then hold_tools
+    uint32_t *h_dest, *d_dest;
+    hipEvent_t done; int used;
 };
 
 struct HeaacPipeline {
@@ -63,6 +86,24 @@ struct HeaacPipeline {
     float last_ms[4];
     HeaacPool *pool; int threads;   // threads: the pool's, the slices of a tick
     const uint8_t *const *job_au; const int *job_size; int *job_status; Set *job_set;
+    unsigned long long n_device, n_host;    // heaac_pipeline_parse_counts
+    // ---- HEAAC_PIPELINE_DEVICE_PARSE ----
+    int dp;
+    HeaacAacStream *d_ast;          // [n] parser states on the device (zeroed, as the host's calloc does)
+    HeaacSbrStream *d_sst[2];       // HE: [n] each, ping-pong; d_sst[sst_cur] holds the streams' current rows
+    int sst_cur;
+    HeaacAacFrameInfo *d_info;      // [nf] what the AAC walk left per unit (the status kernel reads sbr_payload_bit)
+    // What submit waits for is stored by the kernels into pinned host memory (m_*: the device's view of h_*): no
+    // copy commands behind the kernels.
+    int32_t *d_status, *h_status, *m_status;   // [nf] the walk's statuses; the host parser's, for the caller
+    uint32_t *h_taken, *m_taken;    // [n] t0 of each stream
+    hipEvent_t parsed;
+    // the streams the walk stopped: their list and state rows, pinned / device ([n] rows: an HE stream's first header is
+    // always deferred, so a first tick stops every stream)
+    uint32_t *h_list, *d_list, *stop_base;
+    HeaacAacStream *h_g_ast, *m_g_ast, *d_g_ast; HeaacSbrStream *h_g_sst, *m_g_sst, *d_g_sst;
+    size_t m;                       // of the tick in submit
+    Staging stg;
 };
 
 // (out of line under this name: tests/test_pipeline.py looks the per-stream loop up in the library)
@@ -112,6 +153,24 @@ __attribute__((noinline)) static void parse_slice(HeaacPipeline *p, int w)
     }
 }
 
+// One unit of a streams tick on the stream's parser states: parse_slice's decision per unit, as the two hold bytes.
+// Returns the parser's status.  (The host-parse slices and the fix-up of a device-parse tick both come here.)
+static inline int pl_parse_unit(HeaacPipeline *p, HeaacAacStream *ast, HeaacSbrStream *sst, const uint8_t *au, int size,
+                                float *coeffs, HeaacIcs *ics, HeaacToolsFrame *tools, HeaacSbrFrame *sbr, HeaacPsFrame *ps,
+                                uint8_t *hold_dsp, uint8_t *hold_tools)
+{
+    HeaacAacFrameInfo fi;
+    memset(&fi, 0, sizeof(fi));
+    const int r = p->he
+        ? heaac_heaac_parse_frame_ex(&p->aac, ast, sst, p->tab, au, size, p->ncore, coeffs, ics, tools, sbr, ps, &fi)
+        : heaac_aac_parse_frame_ex(&p->aac, ast, au, size, p->ncore, coeffs, ics, tools, NULL, &fi);
+    const int core_failed = r < 0 && fi.channels == 0;
+    const int run_tools = core_failed && (fi.refused & HEAAC_REFUSED_RUN_TOOLS);
+    *hold_dsp = (uint8_t)core_failed;
+    *hold_tools = (uint8_t)(core_failed && !run_tools);
+    return r;
+}
+
 // The slice of a tick that carries T > 1 units per stream: each stream's units in order on the stream's parser state,
 // the records of unit t of stream i at i T + t.  Per unit the decision is parse_slice's; it goes into the two hold
 // masks, and since the streams calls never read a held frame's records nothing is rewritten to be "safe to decode"
@@ -124,29 +183,62 @@ static void parse_slice_streams(HeaacPipeline *p, int w)
         HeaacSbrStream *sst_i = (HeaacSbrStream *)((char *)p->sst + i * heaac_sbr_stream_bytes());
         for (size_t t = 0; t < p->T; t++) {
             const size_t f = i * p->T + t;
-            HeaacAacFrameInfo fi;
-            memset(&fi, 0, sizeof(fi));
-            const int r = p->he
-                ? heaac_heaac_parse_frame_ex(&p->aac, &p->ast[i], sst_i, p->tab, p->job_au[f], p->job_size[f],
-                                             p->ncore, s->h_coeffs + f * (size_t)p->ncore * 1024, s->h_ics + f * p->ncore,
-                                             &s->h_tools[f], &s->h_sbr[f], s->h_ps ? &s->h_ps[f] : NULL, &fi)
-                : heaac_aac_parse_frame_ex(&p->aac, &p->ast[i], p->job_au[f], p->job_size[f], p->ncore,
-                                           s->h_coeffs + f * (size_t)p->ncore * 1024, s->h_ics + f * p->ncore,
-                                           &s->h_tools[f], NULL, &fi);
+            const int r = pl_parse_unit(p, &p->ast[i], sst_i, p->job_au[f], p->job_size[f],
+                                        s->h_coeffs + f * (size_t)p->ncore * 1024, s->h_ics + f * p->ncore, &s->h_tools[f],
+                                        p->he ? &s->h_sbr[f] : NULL, s->h_ps ? &s->h_ps[f] : NULL, &s->h_hold[f],
+                                        &s->h_hold[p->nf + f]);
             if (p->job_status) p->job_status[f] = r;
-            const int core_failed = r < 0 && fi.channels == 0;
-            const int run_tools = core_failed && (fi.refused & HEAAC_REFUSED_RUN_TOOLS);
-            s->h_hold[f] = (uint8_t)core_failed;
-            s->h_hold[p->nf + f] = (uint8_t)(core_failed && !run_tools);
         }
     }
 }
 
-static void pl_slice(void *ctx, int w, int)
+// Device parse, phase 1: the slice's units to their places in the set's byte buffer
+static void pack_slice(HeaacPipeline *p, int w)
+{
+    const size_t lo = p->nf * (size_t)w / (size_t)p->threads, hi = p->nf * (size_t)(w + 1) / (size_t)p->threads;
+    heaac_pack_bytes(p->job_au, p->job_size, p->job_set->h_off, lo, hi, p->job_set->h_bytes);
+}
+
+// Device parse, phase 2: the slice's share of the m stopped streams, each from its gathered states over its units
+// t0 .. T - 1 into the staging rows stop_base says
+static void fix_slice(HeaacPipeline *p, int w)
+{
+    const size_t lo = p->m * (size_t)w / (size_t)p->threads, hi = p->m * (size_t)(w + 1) / (size_t)p->threads;
+    Staging *g = &p->stg;
+    const size_t units = p->stop_base[p->m];
+    for (size_t j = lo; j < hi; j++) {
+        const size_t i = p->h_list[j];
+        HeaacSbrStream *sst_j = p->he ? (HeaacSbrStream *)((char *)p->h_g_sst + j * heaac_sbr_stream_bytes()) : NULL;
+        for (size_t t = p->h_taken[i], u = p->stop_base[j]; t < p->T; t++, u++) {
+            const size_t f = i * p->T + t;
+            const int r = pl_parse_unit(p, &p->h_g_ast[j], sst_j, p->job_au[f], p->job_size[f],
+                                        g->h_coeffs + u * (size_t)p->ncore * 1024, g->h_ics + u * p->ncore, &g->h_tools[u],
+                                        p->he ? &g->h_sbr[u] : NULL, g->h_ps ? &g->h_ps[u] : NULL, &g->h_hold[u],
+                                        &g->h_hold[units + u]);
+            if (p->job_status) p->job_status[f] = r;
+            g->h_dest[u] = (uint32_t)f;
+        }
+    }
+}
+
+static void pl_slice(void *ctx, int w, int phase)
 {
     HeaacPipeline *p = (HeaacPipeline *)ctx;
-    if (p->T > 1) parse_slice_streams(p, w);
+    if (phase == 1) pack_slice(p, w);
+    else if (phase == 2) fix_slice(p, w);
+    else if (p->T > 1) parse_slice_streams(p, w);
     else parse_slice(p, w);
+}
+
+static void stg_free(Staging *g)
+{
+    void *h[] = { g->h_coeffs, g->h_ics, g->h_tools, g->h_sbr, g->h_ps, g->h_hold, g->h_dest };
+    void *d[] = { g->d_coeffs, g->d_ics, g->d_tools, g->d_sbr, g->d_ps, g->d_hold, g->d_dest };
+    for (void *q : h) if (q) (void)hipHostFree(q);
+    for (void *q : d) if (q) (void)hipFree(q);
+    g->h_coeffs = g->d_coeffs = NULL; g->h_ics = g->d_ics = NULL; g->h_tools = g->d_tools = NULL; g->h_sbr = g->d_sbr = NULL;
+    g->h_ps = g->d_ps = NULL; g->h_hold = g->d_hold = NULL; g->h_dest = g->d_dest = NULL;
+    g->cap = 0;
 }
 
 extern "C" void heaac_pipeline_destroy(HeaacPipeline *p)
@@ -160,7 +252,12 @@ extern "C" void heaac_pipeline_destroy(HeaacPipeline *p)
         Set *s = &p->set[k];
         hipEvent_t ev[] = { s->in_start, s->in_done, s->run_done, s->out_done };
         for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+        if (s->h_bytes) (void)hipHostFree(s->h_bytes);
+        if (s->d_bytes) (void)hipFree(s->d_bytes);
     }
+    stg_free(&p->stg);
+    if (p->stg.done) (void)hipEventDestroy(p->stg.done);
+    if (p->parsed) (void)hipEventDestroy(p->parsed);
     heaac_mem_release(&p->mem);
     if (p->d_park_state) (void)hipFree(p->d_park_state);
     if (p->d_park_rng) (void)hipFree(p->d_park_rng);
@@ -183,6 +280,18 @@ extern "C" size_t heaac_pipeline_frames_per_tick(const HeaacPipeline *p) { retur
 extern "C" int heaac_pipeline_create_streams(HeaacPipeline **out, const HeaacAacConfig *aac, int he_cfg, size_t n_streams,
                                              size_t frames_per_tick, int threads)
 {
+    return heaac_pipeline_create_ex(out, aac, he_cfg, n_streams, frames_per_tick, threads, 0);
+}
+
+extern "C" void heaac_pipeline_parse_counts(const HeaacPipeline *p, unsigned long long counts[2])
+{
+    counts[0] = p ? p->n_device : 0;
+    counts[1] = p ? p->n_host : 0;
+}
+
+extern "C" int heaac_pipeline_create_ex(HeaacPipeline **out, const HeaacAacConfig *aac, int he_cfg, size_t n_streams,
+                                        size_t frames_per_tick, int threads, int flags)
+{
     if (!out) return HEAAC_ERR_ARG;
     *out = NULL;
     const size_t n = n_streams, T = frames_per_tick;
@@ -191,8 +300,17 @@ extern "C" int heaac_pipeline_create_streams(HeaacPipeline **out, const HeaacAac
         (!lc && he_cfg != HEAAC_CFG_HEV2 && he_cfg != HEAAC_CFG_HEV1 && he_cfg != HEAAC_CFG_HEV1_MONO) ||
         aac->sampling_index < 0 || aac->sampling_index > 12)
         return HEAAC_ERR_ARG;
+    if ((unsigned)flags & ~(unsigned)HEAAC_PIPELINE_DEVICE_PARSE) return HEAAC_ERR_ARG;
+    const int dp = (flags & HEAAC_PIPELINE_DEVICE_PARSE) != 0;
+    // what the device walk refuses (heaac_parse_args_ok of k_parse_streams.hip); its unit index is 32 bits wide
+    if (dp && ((aac->object_type != HEAAC_AOT_AAC_LC && aac->object_type != HEAAC_AOT_AAC_MAIN) || n * T > 0xfffffffeull))
+        return HEAAC_ERR_ARG;
+    // (heaac_sbr_parse_args_ok: a mono configuration that signals Parametric Stereo takes PS records, which only
+    // HEAAC_CFG_HEV2 has)
+    if (dp && !lc && he_cfg != HEAAC_CFG_HEV2 && aac->ps != 0 && aac->chan_config == 1) return HEAAC_ERR_ARG;
     HeaacPipeline *p = (HeaacPipeline *)calloc(1, sizeof(*p));
     if (!p) return HEAAC_ERR_NOMEM;
+    p->dp = dp;
     p->aac = *aac;
     p->he_cfg = he_cfg;
     p->he = !lc;
@@ -221,16 +339,22 @@ extern "C" int heaac_pipeline_create_streams(HeaacPipeline **out, const HeaacAac
     for (int k = 0; k < PL_DEPTH && ok; k++) {
         Set *s = &p->set[k];
         const size_t nc = nf * (size_t)p->ncore;
-        ok = heaac_pair(m, &s->h_coeffs, &s->d_coeffs, nc * 4096) && heaac_pair(m, &s->h_ics, &s->d_ics, nc * sizeof(HeaacIcs)) &&
-             heaac_pair(m, &s->h_tools, &s->d_tools, nf * sizeof(HeaacToolsFrame)) &&
-             (!p->he || heaac_pair(m, &s->h_sbr, &s->d_sbr, nf * sizeof(HeaacSbrFrame))) &&
-             (!with_ps || heaac_pair(m, &s->h_ps, &s->d_ps, nf * sizeof(HeaacPsFrame))) &&
-             heaac_pair(m, &s->h_pcm, &s->d_pcm, nf * (size_t)p->nout * p->out_len * 2) &&
-             (T > 1 ? heaac_pair(m, &s->h_hold, &s->d_hold, 2 * nf)
-                    : heaac_host(m, &s->failed, n) && heaac_pair(m, &s->h_list, &s->d_list, 4 * n * sizeof(unsigned))) &&
+        // (device parse: the records are made on the device, and what the host parser makes goes through the staging area)
+        ok = dp ? heaac_dev(m, &s->d_coeffs, nc * 4096) && heaac_dev(m, &s->d_ics, nc * sizeof(HeaacIcs)) &&
+                  heaac_dev(m, &s->d_tools, nf * sizeof(HeaacToolsFrame)) &&
+                  (!p->he || heaac_dev(m, &s->d_sbr, nf * sizeof(HeaacSbrFrame))) &&
+                  (!with_ps || heaac_dev(m, &s->d_ps, nf * sizeof(HeaacPsFrame))) && heaac_dev(m, &s->d_hold, 2 * nf) &&
+                  heaac_pair(m, &s->h_off, &s->d_off, (nf + 1) * sizeof(uint32_t))
+                : heaac_pair(m, &s->h_coeffs, &s->d_coeffs, nc * 4096) && heaac_pair(m, &s->h_ics, &s->d_ics, nc * sizeof(HeaacIcs)) &&
+                  heaac_pair(m, &s->h_tools, &s->d_tools, nf * sizeof(HeaacToolsFrame)) &&
+                  (!p->he || heaac_pair(m, &s->h_sbr, &s->d_sbr, nf * sizeof(HeaacSbrFrame))) &&
+                  (!with_ps || heaac_pair(m, &s->h_ps, &s->d_ps, nf * sizeof(HeaacPsFrame))) &&
+                  (T > 1 ? heaac_pair(m, &s->h_hold, &s->d_hold, 2 * nf)
+                         : heaac_host(m, &s->failed, n) && heaac_pair(m, &s->h_list, &s->d_list, 4 * n * sizeof(unsigned)));
+        ok = ok && heaac_pair(m, &s->h_pcm, &s->d_pcm, nf * (size_t)p->nout * p->out_len * 2) &&
              hipEventCreate(&s->in_start) == hipSuccess && hipEventCreate(&s->in_done) == hipSuccess &&
              hipEventCreate(&s->run_done) == hipSuccess && hipEventCreate(&s->out_done) == hipSuccess;
-        if (ok) {
+        if (ok && !dp) {
             memset(s->h_coeffs, 0, nc * 4096); memset(s->h_ics, 0, nc * sizeof(HeaacIcs));
             memset(s->h_tools, 0, nf * sizeof(HeaacToolsFrame));
             if (p->he) memset(s->h_sbr, 0, nf * sizeof(HeaacSbrFrame));
@@ -248,9 +372,30 @@ extern "C" int heaac_pipeline_create_streams(HeaacPipeline **out, const HeaacAac
     }
     ok = ok && heaac_seed_generators(p->d_rng, n);
     p->tab = heaac_sbr_table_create(PL_MAX_HDRS);
-    ok = ok && p->tab && heaac_host(m, &p->ast, n * sizeof(HeaacAacStream)) && heaac_host(m, &p->sst, n * heaac_sbr_stream_bytes());
+    ok = ok && p->tab &&
+         (dp || (heaac_host(m, &p->ast, n * sizeof(HeaacAacStream)) && heaac_host(m, &p->sst, n * heaac_sbr_stream_bytes())));
+    if (ok && dp) {
+        ok = heaac_dev(m, &p->d_ast, n * sizeof(HeaacAacStream)) && heaac_dev(m, &p->d_info, nf * sizeof(HeaacAacFrameInfo)) &&
+             heaac_pair(m, &p->h_status, &p->d_status, nf * sizeof(int32_t)) &&
+             heaac_mem(m, HEAAC_MEM_PINNED, (void **)&p->h_taken, n * sizeof(uint32_t)) &&
+             heaac_pair(m, &p->h_list, &p->d_list, n * sizeof(uint32_t)) && heaac_host(m, &p->stop_base, (n + 1) * sizeof(uint32_t)) &&
+             heaac_pair(m, &p->h_g_ast, &p->d_g_ast, n * sizeof(HeaacAacStream)) &&
+             (!p->he || (heaac_pair(m, &p->h_g_sst, &p->d_g_sst, n * sizeof(HeaacSbrStream)) &&
+                         heaac_dev(m, &p->d_sst[0], n * sizeof(HeaacSbrStream)) && heaac_dev(m, &p->d_sst[1], n * sizeof(HeaacSbrStream)))) &&
+             hipEventCreate(&p->parsed) == hipSuccess && hipEventCreate(&p->stg.done) == hipSuccess &&
+             hipMemset(p->d_ast, 0, n * sizeof(HeaacAacStream)) == hipSuccess &&
+             hipHostGetDevicePointer((void **)&p->m_status, p->h_status, 0) == hipSuccess &&
+             hipHostGetDevicePointer((void **)&p->m_taken, p->h_taken, 0) == hipSuccess &&
+             hipHostGetDevicePointer((void **)&p->m_g_ast, p->h_g_ast, 0) == hipSuccess &&
+             (!p->he || hipHostGetDevicePointer((void **)&p->m_g_sst, p->h_g_sst, 0) == hipSuccess);
+        if (ok && p->he) {
+            // new streams, through the pinned rows the fix-up will use
+            heaac_sbr_stream_init(p->h_g_sst, n);
+            ok = hipMemcpy(p->d_sst[0], p->h_g_sst, n * sizeof(HeaacSbrStream), hipMemcpyHostToDevice) == hipSuccess;
+        }
+    }
     if (ok) {
-        heaac_sbr_stream_init(p->sst, n);
+        if (!dp) heaac_sbr_stream_init(p->sst, n);
         // the null header (table entry 0) is what frames before their stream's first header point at
         ok = hipMemcpy(p->d_hdr, heaac_sbr_table_data(p->tab), sizeof(HeaacSbrHeader), hipMemcpyHostToDevice) == hipSuccess;
         p->hdr_uploaded = 1;
@@ -262,12 +407,14 @@ extern "C" int heaac_pipeline_create_streams(HeaacPipeline **out, const HeaacAac
         if ((size_t)threads > n) threads = (int)n;
         ok = (p->pool = heaac_pool_create(threads, pl_slice, p)) != NULL;
         if (ok) p->threads = heaac_pool_threads(p->pool);
-        ok = ok && (!p->he || heaac_host(m, &p->sst_tmp, p->threads * heaac_sbr_stream_bytes()));
+        ok = ok && (!p->he || dp || heaac_host(m, &p->sst_tmp, p->threads * heaac_sbr_stream_bytes()));
     }
     if (!ok) { heaac_pipeline_destroy(p); return HEAAC_ERR_NOMEM; }
     *out = p;
     return HEAAC_OK;
 }
+
+static int pl_submit_rest(HeaacPipeline *p, Set *s);
 
 static double now_ms(void)
 {
@@ -355,6 +502,143 @@ static int pl_run_streams(HeaacPipeline *p, Set *s)
     return rc;
 }
 
+// A buffer pair of `have` bytes or units that must hold `needed`: the capacity to allocate, doubled from `first`
+static size_t pl_grown(size_t needed, size_t have, size_t first, size_t most)
+{
+    size_t cap = have ? have : first;
+    while (cap < needed) cap *= 2;
+    return cap > most ? most : cap;
+}
+
+// The staging area for `units` units.  Nothing of the old one is in flight: the caller has waited for stg.done.
+static int stg_grow(HeaacPipeline *p, size_t units)
+{
+    Staging *g = &p->stg;
+    if (units <= g->cap) return HEAAC_OK;
+    const size_t cap = pl_grown(units, g->cap, 64, p->nf), nc = cap * (size_t)p->ncore;
+    stg_free(g);
+    const bool ok =
+        pinned((void **)&g->h_coeffs, nc * 4096) && devmem((void **)&g->d_coeffs, nc * 4096) &&
+        pinned((void **)&g->h_ics, nc * sizeof(HeaacIcs)) && devmem((void **)&g->d_ics, nc * sizeof(HeaacIcs)) &&
+        pinned((void **)&g->h_tools, cap * sizeof(HeaacToolsFrame)) && devmem((void **)&g->d_tools, cap * sizeof(HeaacToolsFrame)) &&
+        (!p->he || (pinned((void **)&g->h_sbr, cap * sizeof(HeaacSbrFrame)) && devmem((void **)&g->d_sbr, cap * sizeof(HeaacSbrFrame)))) &&
+        (!p->set[0].d_ps || (pinned((void **)&g->h_ps, cap * sizeof(HeaacPsFrame)) && devmem((void **)&g->d_ps, cap * sizeof(HeaacPsFrame)))) &&
+        pinned((void **)&g->h_hold, 2 * cap) && devmem((void **)&g->d_hold, 2 * cap) &&
+        pinned((void **)&g->h_dest, cap * sizeof(uint32_t)) && devmem((void **)&g->d_dest, cap * sizeof(uint32_t));
+    if (!ok) { stg_free(g); return HEAAC_ERR_NOMEM; }
+    g->cap = cap;
+    return HEAAC_OK;
+}
+
+// The fix-up of a device-parse tick: the p->m streams the walk stopped (h_list, stop_base) are finished by the host
+// parser from their gathered states, and what it made is scattered into the tick's rows; all on `in`.
+// *held: some unit of the tick is held.
+static int pl_fix_up(HeaacPipeline *p, Set *s, int *held)
+{
+    Staging *g = &p->stg;
+    const size_t m = p->m, units = p->stop_base[m];
+    int rc = stg_grow(p, units);
+    if (rc != HEAAC_OK) return rc;
+    HeaacSbrStream *d_sst = p->he ? p->d_sst[p->sst_cur] : NULL;
+    // gather
+    HIP_OK(hipMemcpyAsync(p->d_list, p->h_list, m * sizeof(uint32_t), hipMemcpyHostToDevice, p->in));
+    rc = heaac_launch_fix_gather(p->in, p->d_list, m, p->d_ast, p->m_g_ast, d_sst, p->m_g_sst);
+    if (rc != HEAAC_OK) return rc;
+    HIP_OK(hipStreamSynchronize(p->in));
+    // host parse
+    heaac_pool_run(p->pool, 2);
+    *held = memchr(g->h_hold, 1, units) != NULL;
+    // new SBR headers of this tick (the table's storage never moves)
+    if (heaac_sbr_table_count(p->tab) > PL_MAX_HDRS) return HEAAC_ERR_ARG;
+    rc = heaac_upload_headers(p->tab, &p->hdr_uploaded, p->d_hdr, NULL, p->in);
+    if (rc != HEAAC_OK) return rc;
+    // scatter
+    const size_t nc = units * (size_t)p->ncore;
+    HIP_OK(hipMemcpyAsync(g->d_coeffs, g->h_coeffs, nc * 4096, hipMemcpyHostToDevice, p->in));
+    HIP_OK(hipMemcpyAsync(g->d_ics, g->h_ics, nc * sizeof(HeaacIcs), hipMemcpyHostToDevice, p->in));
+    HIP_OK(hipMemcpyAsync(g->d_tools, g->h_tools, units * sizeof(HeaacToolsFrame), hipMemcpyHostToDevice, p->in));
+    if (p->he) HIP_OK(hipMemcpyAsync(g->d_sbr, g->h_sbr, units * sizeof(HeaacSbrFrame), hipMemcpyHostToDevice, p->in));
+    if (g->d_ps) HIP_OK(hipMemcpyAsync(g->d_ps, g->h_ps, units * sizeof(HeaacPsFrame), hipMemcpyHostToDevice, p->in));
+    HIP_OK(hipMemcpyAsync(g->d_hold, g->h_hold, 2 * units, hipMemcpyHostToDevice, p->in));
+    HIP_OK(hipMemcpyAsync(g->d_dest, g->h_dest, units * sizeof(uint32_t), hipMemcpyHostToDevice, p->in));
+    HIP_OK(hipMemcpyAsync(p->d_g_ast, p->h_g_ast, m * sizeof(HeaacAacStream), hipMemcpyHostToDevice, p->in));
+    if (p->he) HIP_OK(hipMemcpyAsync(p->d_g_sst, p->h_g_sst, m * sizeof(HeaacSbrStream), hipMemcpyHostToDevice, p->in));
+    HeaacFixRows rows;
+    memset(&rows, 0, sizeof(rows));
+    void *dst[HEAAC_FIX_ARRAYS] = { s->d_coeffs, s->d_ics, s->d_tools, s->d_sbr, s->d_ps };
+    const void *src[HEAAC_FIX_ARRAYS] = { g->d_coeffs, g->d_ics, g->d_tools, g->d_sbr, g->d_ps };
+    const size_t bytes[HEAAC_FIX_ARRAYS] = { (size_t)p->ncore * 4096, p->ncore * sizeof(HeaacIcs), sizeof(HeaacToolsFrame),
+                                             sizeof(HeaacSbrFrame), sizeof(HeaacPsFrame) };
+    for (int k = 0; k < HEAAC_FIX_ARRAYS; k++) {
+        rows.dst[k] = (uint32_t *)dst[k]; rows.src[k] = (const uint32_t *)src[k];
+        rows.words[k] = dst[k] ? (uint32_t)(bytes[k] / 4) : 0;
+    }
+    rc = heaac_launch_fix_scatter(p->in, &rows, g->d_dest, units, g->d_hold, s->d_hold, p->nf, p->d_list, m, p->d_g_ast, p->d_ast,
+                                  p->d_g_sst, d_sst);
+    if (rc != HEAAC_OK) return rc;
+    HIP_OK(hipEventRecord(g->done, p->in));
+    g->used = 1;
+    return HEAAC_OK;
+}
+
+// The first two stages of a device-parse tick, up to in_done: pack, upload, the walk and the status kernel on `in`,
+// the wait for the stop positions, the fix-up.  (The set's pinned inputs are free: submit has waited for in_done.)
+static int pl_submit_device(HeaacPipeline *p, Set *s, const uint8_t *const *au, const int *size, int *status, double t0)
+{
+    const size_t n = p->n, nf = p->nf;
+    // pack
+    if (heaac_pack_offsets(size, nf, s->h_off) != 0) return HEAAC_ERR_ARG;
+    const size_t total = s->h_off[nf];
+    if (total > s->bytes_cap || !s->bytes_cap) {
+        // (the walk that read the old buffer has finished: every submit waits for its own)
+        const size_t cap = pl_grown(total, s->bytes_cap, 1 << 16, (size_t)1 << 32);
+        if (s->h_bytes) (void)hipHostFree(s->h_bytes);
+        if (s->d_bytes) (void)hipFree(s->d_bytes);
+        s->h_bytes = NULL; s->d_bytes = NULL; s->bytes_cap = 0;
+        if (!pinned((void **)&s->h_bytes, cap) || !devmem((void **)&s->d_bytes, cap)) return HEAAC_ERR_NOMEM;
+        s->bytes_cap = cap;
+    }
+    p->job_au = au; p->job_size = size; p->job_status = status; p->job_set = s;
+    heaac_pool_run(p->pool, 1);
+    // upload
+    if (s->used) HIP_OK(hipStreamWaitEvent(p->in, s->run_done, 0));
+    HIP_OK(hipEventRecord(s->in_start, p->in));
+    if (total) HIP_OK(hipMemcpyAsync(s->d_bytes, s->h_bytes, total, hipMemcpyHostToDevice, p->in));
+    HIP_OK(hipMemcpyAsync(s->d_off, s->h_off, (nf + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, p->in));
+    // parse: the walk, then the statuses of the host parser
+    int rc;
+    if (p->he) {
+        rc = heaac_heaac_parse_device_streams(p->dev, &p->aac, p->d_ast, p->d_sst[p->sst_cur], p->d_sst[p->sst_cur ^ 1], s->d_bytes,
+                                              s->d_off, n, p->T, p->ncore, s->d_coeffs, s->d_ics, s->d_tools, p->d_info, p->d_hdr,
+                                              p->hdr_uploaded, s->d_sbr, s->d_ps, p->d_status, p->m_taken, s->d_hold, (void *)p->in);
+        if (rc == HEAAC_OK) p->sst_cur ^= 1;
+    } else {
+        rc = heaac_aac_parse_device_streams(p->dev, &p->aac, p->d_ast, s->d_bytes, s->d_off, n, p->T, p->ncore, s->d_coeffs,
+                                            s->d_ics, s->d_tools, p->d_info, p->d_status, p->m_taken, s->d_hold, (void *)p->in);
+    }
+    if (rc == HEAAC_OK)
+        rc = heaac_launch_parse_status(p->in, p->d_status, p->d_info, p->he, p->aac.sbr == 0, status ? p->m_status : NULL,
+                                       s->d_hold + nf, nf);
+    if (rc != HEAAC_OK) return rc;
+    HIP_OK(hipEventRecord(p->parsed, p->in));
+    // the staging area and the stop list are free once the scatter of the tick that used them last has run
+    if (p->stg.used) HIP_OK(hipEventSynchronize(p->stg.done));
+    HIP_OK(hipEventSynchronize(p->parsed));
+    if (status) memcpy(status, p->h_status, nf * sizeof(int32_t));
+    p->m = heaac_stop_list(p->h_taken, n, (uint32_t)p->T, p->h_list, p->stop_base);
+    p->n_host += p->stop_base[p->m];
+    p->n_device += nf - p->stop_base[p->m];
+    int held = 0;
+    if (p->m) {
+        rc = pl_fix_up(p, s, &held);
+        if (rc != HEAAC_OK) return rc;
+    }
+    s->any_held = held;
+    HIP_OK(hipEventRecord(s->in_done, p->in));
+    s->parse_ms = (float)(now_ms() - t0);
+    return HEAAC_OK;
+}
+
 extern "C" int heaac_pipeline_submit(HeaacPipeline *p, const uint8_t *const *au, const int *size, int *status)
 {
     if (!p || !au || !size) return HEAAC_ERR_ARG;
@@ -363,6 +647,11 @@ extern "C" int heaac_pipeline_submit(HeaacPipeline *p, const uint8_t *const *au,
     // the pinned inputs of this set are free once the H2D of the tick that used it last has finished
     if (s->used) HIP_OK(hipEventSynchronize(s->in_done));
     const double t0 = now_ms();
+    if (p->dp) {
+        const int rc = pl_submit_device(p, s, au, size, status, t0);
+        if (rc != HEAAC_OK) return rc;
+        return pl_submit_rest(p, s);
+    }
     p->job_au = au; p->job_size = size; p->job_status = status; p->job_set = s;
     heaac_pool_run(p->pool, 0);
     s->parse_ms = (float)(now_ms() - t0);
@@ -391,10 +680,18 @@ extern "C" int heaac_pipeline_submit(HeaacPipeline *p, const uint8_t *const *au,
     s->any_held = s->h_hold && memchr(s->h_hold, 1, nf) != NULL;
     if (s->any_held) HIP_OK(hipMemcpyAsync(s->d_hold, s->h_hold, 2 * nf, hipMemcpyHostToDevice, p->in));
     HIP_OK(hipEventRecord(s->in_done, p->in));
+    p->n_host += nf;
+    return pl_submit_rest(p, s);
+}
+
+// GPU stage and D2H of the tick in set s, behind its in_done
+static int pl_submit_rest(HeaacPipeline *p, Set *s)
+{
+    const size_t nf = p->nf;
     // GPU
     HIP_OK(hipStreamWaitEvent(p->run, s->in_done, 0));
     if (s->used) HIP_OK(hipStreamWaitEvent(p->run, s->out_done, 0));
-    rc = p->T > 1 ? pl_run_streams(p, s) : pl_run_batch(p, s);
+    const int rc = p->T > 1 || p->dp ? pl_run_streams(p, s) : pl_run_batch(p, s);
     if (rc != HEAAC_OK) return rc;
     HIP_OK(hipEventRecord(s->run_done, p->run));
     // D2H
@@ -423,4 +720,24 @@ extern "C" int heaac_pipeline_collect(HeaacPipeline *p, const int16_t **pcm)
 extern "C" void heaac_pipeline_timing(const HeaacPipeline *p, float ms[4])
 {
     for (int k = 0; k < 4; k++) ms[k] = p ? p->last_ms[k] : 0.0f;
+}
+
+// ---- include/heaac_debug.h: the two plain-C steps of a device-parse tick (pipeline_pack.h) ----
+extern "C" int heaac_debug_pipeline_pack(const uint8_t *const *au, const int *size, size_t n_units, uint8_t *bytes,
+                                         uint32_t *offset)
+{
+    if (!size || !offset) return HEAAC_ERR_ARG;
+    if (heaac_pack_offsets(size, n_units, offset) != 0) return HEAAC_ERR_ARG;
+    if (bytes) {
+        if (!au) return HEAAC_ERR_ARG;
+        heaac_pack_bytes(au, size, offset, 0, n_units, bytes);
+    }
+    return HEAAC_OK;
+}
+
+extern "C" size_t heaac_debug_pipeline_stops(const uint32_t *taken, size_t n_streams, size_t frames_per_tick, uint32_t *list,
+                                             uint32_t *base)
+{
+    if (!taken || !list || !base || frames_per_tick > 0xffffffffull) return 0;
+    return heaac_stop_list(taken, n_streams, (uint32_t)frames_per_tick, list, base);
 }

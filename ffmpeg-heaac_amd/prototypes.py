@@ -100,6 +100,8 @@ PROTOTYPES = {
     "heaac_pipeline_submit": (I, [P, P, P, P]),
     "heaac_pipeline_create_streams": (I, [P, P, I, Z, Z, I]),
     "heaac_pipeline_frames_per_tick": (Z, [P]),
+    "heaac_pipeline_create_ex": (I, [P, P, I, Z, Z, I, I]),
+    "heaac_pipeline_parse_counts": (None, [P, P]),
     "heaac_pipeline_collect": (I, [P, P]),
     "heaac_pipeline_timing": (None, [P, P]),
     "heaac_layout_pipeline_create": (I, [P, P, P, Z, I]),
@@ -114,6 +116,8 @@ PROTOTYPES = {
     "heaac_debug_sbr_parse_core": (I, [P, P, P, P, P, P, P, Z, P, Z, P, P, P, P]),
     "heaac_debug_aac_parse_core_streams": (I, [P, P, P, P, Z, Z, I, P, P, P, P, P, P, P, P]),
     "heaac_debug_heaac_parse_core_streams": (I, [P, P, P, P, P, P, Z, Z, I, P, P, P, P, P, Z, P, P, P, P, P, P]),
+    "heaac_debug_pipeline_pack": (I, [P, P, Z, P, P]),
+    "heaac_debug_pipeline_stops": (Z, [P, Z, Z, P, P]),
     # heaac_multi.h
     "heaac_multi_shard": (None, [Z, I, I, P, P]),
     "heaac_multi_create": (I, [P, P, I, Z]),

@@ -67,6 +67,17 @@ int heaac_debug_heaac_parse_core_streams(const HeaacAacConfig *cfg, HeaacAacStre
                                          const HeaacSbrHeader *hdr, size_t n_hdr, HeaacSbrFrame *sbr, HeaacPsFrame *ps,
                                          int32_t *status, uint32_t *taken, uint8_t *hold, int32_t *why);
 
+/* The two host steps of a device-parse tick of heaac_pipeline_* that are plain C (csrc/pipeline_pack.h), as submit runs
+ * them.  pack: offset [n_units + 1] of the units laid end to end, a unit with size <= 0 an empty one (its pointer is not
+ * looked at), and -- unless bytes is NULL -- their bytes copied to bytes[offset[i] ...]; with bytes == NULL nothing but
+ * size[] is read and au may be NULL.  HEAAC_ERR_ARG where the tick's bytes do not fit 32-bit offsets, before a byte is
+ * copied.  stops: taken [n_streams] (t0 per stream, as the streams walk writes it) -> the streams with t0 < T in
+ * ascending order in list [n_streams], and in base [n_streams + 1] where each one's unit t0 stands among the units
+ * handed to the host parser (base[m] = their count); returns m. */
+int heaac_debug_pipeline_pack(const uint8_t *const *au, const int *size, size_t n_units, uint8_t *bytes, uint32_t *offset);
+size_t heaac_debug_pipeline_stops(const uint32_t *taken, size_t n_streams, size_t frames_per_tick, uint32_t *list,
+                                  uint32_t *base);
+
 #ifdef __cplusplus
 }
 #endif

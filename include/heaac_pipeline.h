@@ -73,6 +73,41 @@ int heaac_pipeline_create_streams(HeaacPipeline **out, const HeaacAacConfig *aac
                                   size_t n_streams, size_t frames_per_tick, int threads);
 size_t heaac_pipeline_frames_per_tick(const HeaacPipeline *p);     /* T of the create call (1: heaac_pipeline_create) */
 
+/* The general create call: heaac_pipeline_create_streams with `flags`; flags = 0 is that call, and the two create calls
+ * above are this one with flags = 0.  (flags is a bit set passed as an int.)
+ *
+ * HEAAC_PIPELINE_DEVICE_PARSE: the access units are parsed on the GPU.  A tick's units are packed into one pinned byte
+ * buffer and uploaded as they are (a few hundred bytes per unit instead of about 15 KB of parsed records);
+ * heaac_aac_parse_device_streams / heaac_heaac_parse_device_streams (heaac_parse.h) walk them on the copy-in stream, the
+ * parser state of every stream kept on the device.  The walk stops a stream at the first unit it defers -- a stream's
+ * first SBR header and every header that changes the band tables, pulse data, coupling / program config / LFE elements,
+ * an empty unit (size <= 0), and every unit the host parser would not return HEAAC_PARSE_OK / HEAAC_PARSE_NO_SBR for,
+ * an HE unit whose SBR payload alone fails included.  The streams it stopped are finished on the parser pool by
+ * heaac_heaac_parse_frame_ex / heaac_aac_parse_frame_ex from the states the walk left, and those units' records are
+ * put into the tick's rows before the decode; the next tick is walked on the device again from the states the host
+ * parser left.  PCM and status[] of every unit of every tick are bit for bit those of the pipeline created with the
+ * same arguments and flags = 0 and fed the same units.
+ *
+ * submit of a device-parse pipeline WAITS for its own tick's parse kernel before it returns: it needs the positions
+ * the streams stopped at to hand the rest to the host parser (and waits again for the host parser's part where there
+ * is one).  It does not wait for the decode or for earlier ticks' downloads.  The submit of a host-parse pipeline only
+ * enqueues.  collect, timing, destroy and the depth are the same; heaac_pipeline_timing's ms[0] is submit's host time up
+ * to the point the tick's records are complete (pack, the wait, the host parser's part) and ms[1] the copy-in stream's
+ * time for the same (upload, the parse kernels, the fix-up copies and kernels).  The GPU stage runs the *_streams_ex
+ * calls for every frames_per_tick, 1 included.
+ *
+ * HEAAC_ERR_ARG for an unknown flag bit; with HEAAC_PIPELINE_DEVICE_PARSE for what the device parsers refuse: an object
+ * type other than AAC-LC or AAC-Main, n_streams * frames_per_tick beyond their 32-bit unit index, and a mono
+ * configuration with Parametric Stereo signalled (aac->ps != 0, channel configuration 1) under HEAAC_CFG_HEV1_MONO /
+ * HEAAC_CFG_HEV1, which have no PS records.  A tick whose units together exceed 4 GiB - 1 bytes is refused by submit
+ * with HEAAC_ERR_ARG before anything is enqueued. */
+#define HEAAC_PIPELINE_DEVICE_PARSE 1
+int heaac_pipeline_create_ex(HeaacPipeline **out, const HeaacAacConfig *aac, int he_cfg,
+                             size_t n_streams, size_t frames_per_tick, int threads, int flags);
+/* cumulative since create: counts[0] the units the device walk took, counts[1] the units the host parser was handed
+ * (without HEAAC_PIPELINE_DEVICE_PARSE: 0 and every unit submitted) */
+void heaac_pipeline_parse_counts(const HeaacPipeline *p, unsigned long long counts[2]);
+
 /* Waits for the OLDEST tick in flight and hands out its PCM: [n_streams][2048 (LC, downsampled SBR: 1024)][channels] int16 in pinned memory
  * owned by the pipeline, valid until HEAAC_PIPELINE_DEPTH more ticks have been submitted. */
 int heaac_pipeline_collect(HeaacPipeline *p, const int16_t **pcm);

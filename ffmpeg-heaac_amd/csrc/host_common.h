@@ -58,7 +58,8 @@ void heaac_pool_destroy(HeaacPool *pool);
 int heaac_threads_by_cpu_quota(void);
 int heaac_threads_online_max32(void);
 
-// ---- rows of the streams whose unit failed ----
+// ---- rows of the streams whose unit failed (the layout pipeline, pipeline_layout.hip: its spectral tools call takes
+// coupling elements and has no streams form with hold masks, so it parks the failed streams' rows around its calls) ----
 // One block of `block` threads per (stream, parking row) pair of d_list, rows of row_words 32-bit words:
 //   mode 0: park[row] = rows[stream];  1: rows[stream] = park[row];  2: rows[stream] = 0 (park may be NULL)
 void heaac_rows(hipStream_t s, const unsigned *d_list, unsigned pairs, unsigned block, void *rows, void *park,

@@ -1,6 +1,6 @@
-// host_common.hip -- host_common.h: what an object owns, the worker pool, the parking of failed streams' rows,
-// per-stream device seeding, the SBR header upload and the configuration's shape, once for the pipelines, the codec
-// contexts and the C ABI.
+// host_common.hip -- host_common.h: what an object owns, the worker pool, the parking of failed streams' rows (the
+// layout pipeline's), per-stream device seeding, the SBR header upload and the configuration's shape, once for the
+// pipelines, the codec contexts and the C ABI.
 #include <pthread.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -171,7 +171,8 @@ int heaac_threads_online_max32(void)
 // rows of the failed streams
 // ---------------------------------------------------------------------------
 // Rows of the listed streams to the parking area and back (or zeroed): one block per (stream, parking row) pair.  A
-// tick with thousands of damaged units costs a handful of launches, not six copies per stream (tools/damage_rate.py).
+// tick of the layout pipeline with thousands of damaged units costs a handful of launches, not six copies per stream
+// (tools/layout_rate.py --damaged).
 __global__ void k_rows(const unsigned *__restrict__ list, unsigned *rows, unsigned *park, unsigned long long row_words, int mode)
 {
     const unsigned stream = list[2 * blockIdx.x], slot = list[2 * blockIdx.x + 1];

@@ -3,9 +3,10 @@
 //
 //   host parse   the worker pool of host_common.h, one slice of the streams per thread
 //   H2D          stream `in`:  parsed records of the tick's buffer set, pinned -> device
-//   GPU          stream `run`: heaac_spectral_tools_batch + heaac_he_decode_batch, DSP state in place
-//                (frames_per_tick = T > 1: heaac_spectral_tools_streams_ex + heaac_he_decode_streams_ex over the T units
-//                of each stream, a unit that did not parse held by the calls' masks instead of parked around them)
+//   GPU          stream `run`: heaac_spectral_tools_streams_ex + heaac_he_decode_streams_ex (AAC-LC:
+//                heaac_lc_decode_streams_ex) over the T units of each stream, DSP state in place; a unit that did not
+//                parse is held by the calls' masks.  A tick without one passes no mask, and with T = 1 the calls then
+//                launch the batch kernels.
 //   D2H          stream `out`: int16 PCM of the tick's buffer set, device -> pinned
 // PL_DEPTH buffer sets rotate (set = tick % PL_DEPTH): a tick spends parse + H2D + GPU + D2H in flight (about 24 ms for
 // 32 k streams) while the slowest stage takes 7 ms, so four ticks must overlap to keep every stage busy.
@@ -16,7 +17,7 @@
 // one pinned byte buffer (pipeline_pack.h), uploaded, and parsed by the walk of k_parse_streams.hip on `in`, the parser
 // states on the device; submit waits for the walk's stop positions and finishes the streams it stopped on the host pool
 // from their gathered states, the records of those units scattered into the tick's rows (k_fix.hip) -- all on `in`, so
-// the next tick's walk reads the states the fix-up left.  The GPU stage is the streams calls for every T.
+// the next tick's walk reads the states the fix-up left.  The GPU stage and the D2H are the same.
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
 #include <string.h>
@@ -30,20 +31,22 @@
 #define PL_MAX_HDRS 4096
 #define PL_DEPTH HEAAC_PIPELINE_DEPTH
 
+// The five record arrays of a tick or of the staging area, in the order of HeaacFixRows; sbr / ps are NULL where the
+// configuration has none (HeaacPipeline::row_bytes says how long a unit's row is in each)
+union Records {
+    struct { float *coeffs; HeaacIcs *ics; HeaacToolsFrame *tools; HeaacSbrFrame *sbr; HeaacPsFrame *ps; };
+    void *row[HEAAC_FIX_ARRAYS];
+};
+enum { REC_TOOLS = 2 };
+
 struct Set {
-    // pinned host
-    float *h_coeffs; HeaacIcs *h_ics; HeaacToolsFrame *h_tools; HeaacSbrFrame *h_sbr; HeaacPsFrame *h_ps; int16_t *h_pcm;
-    // device
-    float *d_coeffs; HeaacIcs *d_ics; HeaacToolsFrame *d_tools; HeaacSbrFrame *d_sbr; HeaacPsFrame *d_ps; int16_t *d_pcm;
+    Records h, d;                   // pinned host (host parse only), device
+    int16_t *h_pcm, *d_pcm;
     hipEvent_t in_start, in_done, run_done, out_done;
     int used;                       // a tick has gone through this set
     float parse_ms;
-    unsigned char *failed;          // [n] the stream's access unit of this tick did not parse (core element): 1, or 2 where
-                                    // the spectral tools still have to move its noise generator / predictors
-    unsigned *h_list, *d_list;      // [2 n] (stream, parking row) pairs of the failed streams, pinned / device
-    // frames_per_tick > 1 instead of failed / the lists: the hold masks of the streams calls, pinned / device.
-    // [0, n T): hold_dsp, the unit did not parse; [n T, 2 n T): hold_tools, it did not and the tools do not run either
-    // (failed == 1 of the one-unit tick; failed == 2 is hold_dsp alone)
+    // The hold masks of the streams calls, pinned (host parse only) / device.  [0, n T): hold_dsp, the unit's core
+    // element did not parse; [n T, 2 n T): hold_tools, it did not and the spectral tools do not run either
     uint8_t *h_hold, *d_hold;
     int any_held;                   // some byte of hold_dsp is set (hold_tools is a subset): the masks are uploaded and passed
     // device parse: the tick's units laid end to end (grown on demand) and their offsets [nf + 1], pinned / device
@@ -56,32 +59,29 @@ struct Set {
 // scatter) says when the pinned half may be written again.
 struct Staging {
     size_t cap;                     // units
-    float *h_coeffs, *d_coeffs; HeaacIcs *h_ics, *d_ics; HeaacToolsFrame *h_tools, *d_tools;
-    HeaacSbrFrame *h_sbr, *d_sbr; HeaacPsFrame *h_ps, *d_ps;
+    HeaacMem *mem;                  // every block of the area
+    Records h, d;
     uint8_t *h_hold, *d_hold;       // [2 units]: hold_dsp of every staged unit, then hold_tools
     uint32_t *h_dest, *d_dest;
     hipEvent_t done; int used;
 };
 
 struct HeaacPipeline {
-    HeaacMem *mem;                  // every block but the parking areas
+    HeaacMem *mem;                  // every block but the ones grown on demand (the sets' byte buffers, the staging area)
     HeaacAacConfig aac;
     int he_cfg, ncore, nout, he, out_len;
     size_t n, words;
+    size_t row_bytes[HEAAC_FIX_ARRAYS];   // of one unit's row in each record array; 0: no such array
     size_t T, nf;                   // access units per stream and tick; n * T, the frames of a tick
     HeaacDevice *dev;
     hipStream_t in, run, out;
     Set set[PL_DEPTH];
     float *d_state; int32_t *d_rng;
-    // A stream whose access unit fails keeps its decoder state and gets silence for the tick: its state
-    // rows are parked here around the decode launches.  Grown on demand -- damaged units are the exception.
-    float *d_park_state; int32_t *d_park_rng; HeaacPredictorState *d_park_pred; size_t park_rows;
     HeaacPredictorState *d_pred;  // AAC-Main streams: [n][ncore][672] (aacdec.c:1271-1322), else NULL
     int downsampled;              // SBR with the output at the core rate (aacsbr.c:1719)
     HeaacSbrHeader *d_hdr; size_t hdr_uploaded;
     HeaacSbrHeaderTable *tab;
     HeaacAacStream *ast; HeaacSbrStream *sst;
-    HeaacSbrStream *sst_tmp;      // HE: [threads] scratch SBR reader states, one per parse slice
     unsigned long submitted, collected;
     float last_ms[4];
     HeaacPool *pool; int threads;   // threads: the pool's, the slices of a tick
@@ -106,76 +106,36 @@ struct HeaacPipeline {
     Staging stg;
 };
 
-// (out of line under this name: tests/test_pipeline.py looks the per-stream loop up in the library)
-__attribute__((noinline)) static void parse_slice(HeaacPipeline *p, int w)
-{
-    const size_t lo = p->n * (size_t)w / (size_t)p->threads, hi = p->n * (size_t)(w + 1) / (size_t)p->threads;
-    Set *s = p->job_set;
-    // the slice's scratch copy of one stream's SBR reader state (a copy on the stack inside the loop would only be
-    // released at return: one reader per failed stream, and thousands of them overflow a thread's stack)
-    void *tmp = p->sst_tmp ? (char *)p->sst_tmp + (size_t)w * heaac_sbr_stream_bytes() : NULL;
-    for (size_t i = lo; i < hi; i++) {
-        HeaacAacFrameInfo fi;
-        memset(&fi, 0, sizeof(fi));
-        HeaacSbrStream *sst_i = (HeaacSbrStream *)((char *)p->sst + i * heaac_sbr_stream_bytes());
-        const int r = p->he
-            ? heaac_heaac_parse_frame_ex(&p->aac, &p->ast[i], sst_i, p->tab, p->job_au[i], p->job_size[i],
-                                         p->ncore, s->h_coeffs + i * (size_t)p->ncore * 1024, s->h_ics + i * p->ncore,
-                                         &s->h_tools[i], &s->h_sbr[i], s->h_ps ? &s->h_ps[i] : NULL, &fi)
-            : heaac_aac_parse_frame_ex(&p->aac, &p->ast[i], p->job_au[i], p->job_size[i], p->ncore,
-                                       s->h_coeffs + i * (size_t)p->ncore * 1024, s->h_ics + i * p->ncore, &s->h_tools[i],
-                                       NULL, &fi);
-        if (p->job_status) p->job_status[i] = r;
-        // The core element did not parse (an SBR payload that fails leaves valid "SBR off" records and the unit decodes,
-        // as in the reference).  The reference returns an error and writes no samples, aac_decode_frame :2065-2068; here
-        // the stream's slot in the batch still runs, so it gets records that are safe to decode -- silence, no tools,
-        // no SBR payload -- and submit() parks its state rows around the launches: the stream is left as it was before
-        // the unit and its PCM of this tick is zero.  (What was half written by the failed parse, and the SBR / PS
-        // records of the tick that used this buffer set last, must not reach the kernels.)
-        // One thing does move, as in the reference: where its element decoders had drawn noise or stepped predictors
-        // before they refused the unit, the parser has left tools records that do exactly that much
-        // (HEAAC_REFUSED_RUN_TOOLS, heaac_parse.h) -- they run, and only the decoder's state rows are parked.
-        const int core_failed = r < 0 && fi.channels == 0;
-        const int run_tools = core_failed && (fi.refused & HEAAC_REFUSED_RUN_TOOLS);
-        s->failed[i] = (unsigned char)(core_failed ? 1 + run_tools : 0);
-        if (core_failed) {
-            memset(s->h_ics + i * p->ncore, 0, p->ncore * sizeof(HeaacIcs));
-            if (!run_tools) {
-                memset(s->h_coeffs + i * (size_t)p->ncore * 1024, 0, (size_t)p->ncore * 4096);
-                memset(&s->h_tools[i], 0, sizeof(HeaacToolsFrame));
-            }
-            if (p->he) {
-                // the record of "no payload" from a COPY of the stream's SBR state (the call moves kx / m along)
-                memcpy(tmp, sst_i, heaac_sbr_stream_bytes());
-                heaac_sbr_no_payload((HeaacSbrStream *)tmp, p->ncore, &s->h_sbr[i], s->h_ps ? &s->h_ps[i] : NULL);
-            }
-        }
-    }
-}
-
-// One unit of a streams tick on the stream's parser states: parse_slice's decision per unit, as the two hold bytes.
-// Returns the parser's status.  (The host-parse slices and the fix-up of a device-parse tick both come here.)
+// One unit on its stream's parser states, its records into row f of r.  The core element did not parse (an SBR
+// payload that fails leaves valid "SBR off" records and the unit decodes, as in the reference): the reference returns an
+// error and writes no samples, aac_decode_frame :2065-2068; here *hold_dsp = 1 and the streams calls leave the stream's
+// DSP state as it was and write silence, without reading the unit's records.  One thing does move, as in the
+// reference: where its element decoders had drawn noise or stepped predictors before they refused the unit, the parser
+// has left tools records that do exactly that much (HEAAC_REFUSED_RUN_TOOLS, heaac_parse.h) -- *hold_tools = 0 and the
+// spectral tools run on them.  Returns the parser's status.  (The host-parse slices and the fix-up of a device-parse
+// tick both come here.)
 static inline int pl_parse_unit(HeaacPipeline *p, HeaacAacStream *ast, HeaacSbrStream *sst, const uint8_t *au, int size,
-                                float *coeffs, HeaacIcs *ics, HeaacToolsFrame *tools, HeaacSbrFrame *sbr, HeaacPsFrame *ps,
-                                uint8_t *hold_dsp, uint8_t *hold_tools)
+                                const Records *r, size_t f, uint8_t *hold_dsp, uint8_t *hold_tools)
 {
+    float *coeffs = r->coeffs + f * (size_t)p->ncore * 1024;
+    HeaacIcs *ics = r->ics + f * p->ncore;
     HeaacAacFrameInfo fi;
     memset(&fi, 0, sizeof(fi));
-    const int r = p->he
-        ? heaac_heaac_parse_frame_ex(&p->aac, ast, sst, p->tab, au, size, p->ncore, coeffs, ics, tools, sbr, ps, &fi)
-        : heaac_aac_parse_frame_ex(&p->aac, ast, au, size, p->ncore, coeffs, ics, tools, NULL, &fi);
-    const int core_failed = r < 0 && fi.channels == 0;
+    const int st = p->he
+        ? heaac_heaac_parse_frame_ex(&p->aac, ast, sst, p->tab, au, size, p->ncore, coeffs, ics, &r->tools[f], &r->sbr[f],
+                                     r->ps ? &r->ps[f] : NULL, &fi)
+        : heaac_aac_parse_frame_ex(&p->aac, ast, au, size, p->ncore, coeffs, ics, &r->tools[f], NULL, &fi);
+    const int core_failed = st < 0 && fi.channels == 0;
     const int run_tools = core_failed && (fi.refused & HEAAC_REFUSED_RUN_TOOLS);
     *hold_dsp = (uint8_t)core_failed;
     *hold_tools = (uint8_t)(core_failed && !run_tools);
-    return r;
+    return st;
 }
 
-// The slice of a tick that carries T > 1 units per stream: each stream's units in order on the stream's parser state,
-// the records of unit t of stream i at i T + t.  Per unit the decision is parse_slice's; it goes into the two hold
-// masks, and since the streams calls never read a held frame's records nothing is rewritten to be "safe to decode"
-// (a unit whose tools still run keeps the parser's tools record and coefficients, as there).
-static void parse_slice_streams(HeaacPipeline *p, int w)
+// The host-parse slice of a tick: each stream's T units in order on the stream's parser state, the records of unit t
+// of stream i at i T + t.
+// (out of line under this name, as fix_slice is: tests/test_pipeline.py looks the per-stream loops up in the library)
+__attribute__((noinline)) static void parse_slice(HeaacPipeline *p, int w)
 {
     const size_t lo = p->n * (size_t)w / (size_t)p->threads, hi = p->n * (size_t)(w + 1) / (size_t)p->threads;
     Set *s = p->job_set;
@@ -183,9 +143,7 @@ static void parse_slice_streams(HeaacPipeline *p, int w)
         HeaacSbrStream *sst_i = (HeaacSbrStream *)((char *)p->sst + i * heaac_sbr_stream_bytes());
         for (size_t t = 0; t < p->T; t++) {
             const size_t f = i * p->T + t;
-            const int r = pl_parse_unit(p, &p->ast[i], sst_i, p->job_au[f], p->job_size[f],
-                                        s->h_coeffs + f * (size_t)p->ncore * 1024, s->h_ics + f * p->ncore, &s->h_tools[f],
-                                        p->he ? &s->h_sbr[f] : NULL, s->h_ps ? &s->h_ps[f] : NULL, &s->h_hold[f],
+            const int r = pl_parse_unit(p, &p->ast[i], sst_i, p->job_au[f], p->job_size[f], &s->h, f, &s->h_hold[f],
                                         &s->h_hold[p->nf + f]);
             if (p->job_status) p->job_status[f] = r;
         }
@@ -201,7 +159,7 @@ static void pack_slice(HeaacPipeline *p, int w)
 
 // Device parse, phase 2: the slice's share of the m stopped streams, each from its gathered states over its units
 // t0 .. T - 1 into the staging rows stop_base says
-static void fix_slice(HeaacPipeline *p, int w)
+__attribute__((noinline)) static void fix_slice(HeaacPipeline *p, int w)
 {
     const size_t lo = p->m * (size_t)w / (size_t)p->threads, hi = p->m * (size_t)(w + 1) / (size_t)p->threads;
     Staging *g = &p->stg;
@@ -211,9 +169,7 @@ static void fix_slice(HeaacPipeline *p, int w)
         HeaacSbrStream *sst_j = p->he ? (HeaacSbrStream *)((char *)p->h_g_sst + j * heaac_sbr_stream_bytes()) : NULL;
         for (size_t t = p->h_taken[i], u = p->stop_base[j]; t < p->T; t++, u++) {
             const size_t f = i * p->T + t;
-            const int r = pl_parse_unit(p, &p->h_g_ast[j], sst_j, p->job_au[f], p->job_size[f],
-                                        g->h_coeffs + u * (size_t)p->ncore * 1024, g->h_ics + u * p->ncore, &g->h_tools[u],
-                                        p->he ? &g->h_sbr[u] : NULL, g->h_ps ? &g->h_ps[u] : NULL, &g->h_hold[u],
+            const int r = pl_parse_unit(p, &p->h_g_ast[j], sst_j, p->job_au[f], p->job_size[f], &g->h, u, &g->h_hold[u],
                                         &g->h_hold[units + u]);
             if (p->job_status) p->job_status[f] = r;
             g->h_dest[u] = (uint32_t)f;
@@ -226,18 +182,40 @@ static void pl_slice(void *ctx, int w, int phase)
     HeaacPipeline *p = (HeaacPipeline *)ctx;
     if (phase == 1) pack_slice(p, w);
     else if (phase == 2) fix_slice(p, w);
-    else if (p->T > 1) parse_slice_streams(p, w);
     else parse_slice(p, w);
+}
+
+// The configuration's record arrays for `units` units: device memory in *d, with pinned twins in *h unless NULL
+static bool rec_alloc(const HeaacPipeline *p, HeaacMem **m, Records *h, Records *d, size_t units)
+{
+    for (int k = 0; k < HEAAC_FIX_ARRAYS; k++) {
+        const size_t bytes = units * p->row_bytes[k];
+        if (bytes && !(heaac_mem(m, HEAAC_MEM_DEVICE, &d->row[k], bytes) && (!h || heaac_mem(m, HEAAC_MEM_PINNED, &h->row[k], bytes))))
+            return false;
+    }
+    return true;
+}
+
+// `units` rows of every record array, pinned -> device, on `in`
+static int rec_upload(HeaacPipeline *p, const Records *h, const Records *d, size_t units, bool mono_tools)
+{
+    for (int k = 0; k < HEAAC_FIX_ARRAYS; k++) {
+        if (!p->row_bytes[k]) continue;
+        if (k == REC_TOOLS && mono_tools) {
+            // a mono stream uses channel 0 of the tools record only: the second channel's 3.5 KB stay on the host
+            // (the device copies were zeroed once and the kernel never reads them for one channel)
+            HIP_OK(hipMemcpy2DAsync(d->tools, sizeof(HeaacToolsFrame), h->tools, sizeof(HeaacToolsFrame),
+                                    offsetof(HeaacToolsFrame, ch) + sizeof(HeaacToolsChannel), units, hipMemcpyHostToDevice, p->in));
+        } else {
+            HIP_OK(hipMemcpyAsync(d->row[k], h->row[k], units * p->row_bytes[k], hipMemcpyHostToDevice, p->in));
+        }
+    }
+    return HEAAC_OK;
 }
 
 static void stg_free(Staging *g)
 {
-    void *h[] = { g->h_coeffs, g->h_ics, g->h_tools, g->h_sbr, g->h_ps, g->h_hold, g->h_dest };
-    void *d[] = { g->d_coeffs, g->d_ics, g->d_tools, g->d_sbr, g->d_ps, g->d_hold, g->d_dest };
-    for (void *q : h) if (q) (void)hipHostFree(q);
-    for (void *q : d) if (q) (void)hipFree(q);
-    g->h_coeffs = g->d_coeffs = NULL; g->h_ics = g->d_ics = NULL; g->h_tools = g->d_tools = NULL; g->h_sbr = g->d_sbr = NULL;
-    g->h_ps = g->d_ps = NULL; g->h_hold = g->d_hold = NULL; g->h_dest = g->d_dest = NULL;
+    heaac_mem_release(&g->mem);
     g->cap = 0;
 }
 
@@ -259,9 +237,6 @@ extern "C" void heaac_pipeline_destroy(HeaacPipeline *p)
     if (p->stg.done) (void)hipEventDestroy(p->stg.done);
     if (p->parsed) (void)hipEventDestroy(p->parsed);
     heaac_mem_release(&p->mem);
-    if (p->d_park_state) (void)hipFree(p->d_park_state);
-    if (p->d_park_rng) (void)hipFree(p->d_park_rng);
-    if (p->d_park_pred) (void)hipFree(p->d_park_pred);
     if (p->in) (void)hipStreamDestroy(p->in);
     if (p->run) (void)hipStreamDestroy(p->run);
     if (p->out) (void)hipStreamDestroy(p->out);
@@ -335,31 +310,22 @@ extern "C" int heaac_pipeline_create_ex(HeaacPipeline **out, const HeaacAacConfi
     bool ok = hipStreamCreateWithFlags(&p->in, hipStreamNonBlocking) == hipSuccess &&
               hipStreamCreateWithFlags(&p->run, hipStreamNonBlocking) == hipSuccess &&
               hipStreamCreateWithFlags(&p->out, hipStreamNonBlocking) == hipSuccess;
-    const int with_ps = he_cfg == HEAAC_CFG_HEV2;
+    const size_t row_bytes[HEAAC_FIX_ARRAYS] = { (size_t)p->ncore * 4096, p->ncore * sizeof(HeaacIcs), sizeof(HeaacToolsFrame),
+                                                 p->he ? sizeof(HeaacSbrFrame) : 0,
+                                                 he_cfg == HEAAC_CFG_HEV2 ? sizeof(HeaacPsFrame) : 0 };
+    memcpy(p->row_bytes, row_bytes, sizeof(row_bytes));
     for (int k = 0; k < PL_DEPTH && ok; k++) {
         Set *s = &p->set[k];
-        const size_t nc = nf * (size_t)p->ncore;
         // (device parse: the records are made on the device, and what the host parser makes goes through the staging area)
-        ok = dp ? heaac_dev(m, &s->d_coeffs, nc * 4096) && heaac_dev(m, &s->d_ics, nc * sizeof(HeaacIcs)) &&
-                  heaac_dev(m, &s->d_tools, nf * sizeof(HeaacToolsFrame)) &&
-                  (!p->he || heaac_dev(m, &s->d_sbr, nf * sizeof(HeaacSbrFrame))) &&
-                  (!with_ps || heaac_dev(m, &s->d_ps, nf * sizeof(HeaacPsFrame))) && heaac_dev(m, &s->d_hold, 2 * nf) &&
-                  heaac_pair(m, &s->h_off, &s->d_off, (nf + 1) * sizeof(uint32_t))
-                : heaac_pair(m, &s->h_coeffs, &s->d_coeffs, nc * 4096) && heaac_pair(m, &s->h_ics, &s->d_ics, nc * sizeof(HeaacIcs)) &&
-                  heaac_pair(m, &s->h_tools, &s->d_tools, nf * sizeof(HeaacToolsFrame)) &&
-                  (!p->he || heaac_pair(m, &s->h_sbr, &s->d_sbr, nf * sizeof(HeaacSbrFrame))) &&
-                  (!with_ps || heaac_pair(m, &s->h_ps, &s->d_ps, nf * sizeof(HeaacPsFrame))) &&
-                  (T > 1 ? heaac_pair(m, &s->h_hold, &s->d_hold, 2 * nf)
-                         : heaac_host(m, &s->failed, n) && heaac_pair(m, &s->h_list, &s->d_list, 4 * n * sizeof(unsigned)));
-        ok = ok && heaac_pair(m, &s->h_pcm, &s->d_pcm, nf * (size_t)p->nout * p->out_len * 2) &&
+        ok = rec_alloc(p, m, dp ? NULL : &s->h, &s->d, nf) &&
+             (dp ? heaac_dev(m, &s->d_hold, 2 * nf) && heaac_pair(m, &s->h_off, &s->d_off, (nf + 1) * sizeof(uint32_t))
+                 : heaac_pair(m, &s->h_hold, &s->d_hold, 2 * nf)) &&
+             heaac_pair(m, &s->h_pcm, &s->d_pcm, nf * (size_t)p->nout * p->out_len * 2) &&
              hipEventCreate(&s->in_start) == hipSuccess && hipEventCreate(&s->in_done) == hipSuccess &&
              hipEventCreate(&s->run_done) == hipSuccess && hipEventCreate(&s->out_done) == hipSuccess;
         if (ok && !dp) {
-            memset(s->h_coeffs, 0, nc * 4096); memset(s->h_ics, 0, nc * sizeof(HeaacIcs));
-            memset(s->h_tools, 0, nf * sizeof(HeaacToolsFrame));
-            if (p->he) memset(s->h_sbr, 0, nf * sizeof(HeaacSbrFrame));
-            if (with_ps) memset(s->h_ps, 0, nf * sizeof(HeaacPsFrame));
-            ok = hipMemset(s->d_tools, 0, nf * sizeof(HeaacToolsFrame)) == hipSuccess;
+            for (int a = 0; a < HEAAC_FIX_ARRAYS; a++) if (s->h.row[a]) memset(s->h.row[a], 0, nf * p->row_bytes[a]);
+            ok = hipMemset(s->d.tools, 0, nf * sizeof(HeaacToolsFrame)) == hipSuccess;
         }
     }
     ok = ok && heaac_dev(m, &p->d_state, n * p->words * 4) && heaac_dev(m, &p->d_rng, n * 4) &&
@@ -407,14 +373,11 @@ extern "C" int heaac_pipeline_create_ex(HeaacPipeline **out, const HeaacAacConfi
         if ((size_t)threads > n) threads = (int)n;
         ok = (p->pool = heaac_pool_create(threads, pl_slice, p)) != NULL;
         if (ok) p->threads = heaac_pool_threads(p->pool);
-        ok = ok && (!p->he || dp || heaac_host(m, &p->sst_tmp, p->threads * heaac_sbr_stream_bytes()));
     }
     if (!ok) { heaac_pipeline_destroy(p); return HEAAC_ERR_NOMEM; }
     *out = p;
     return HEAAC_OK;
 }
-
-static int pl_submit_rest(HeaacPipeline *p, Set *s);
 
 static double now_ms(void)
 {
@@ -423,83 +386,32 @@ static double now_ms(void)
     return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6;
 }
 
-static size_t pl_pred_row_bytes(const HeaacPipeline *p)
+// GPU stage and D2H of the tick in set s, behind its in_done
+static int pl_submit_rest(HeaacPipeline *p, Set *s)
 {
-    return (size_t)p->ncore * HEAAC_MAX_PREDICTORS * sizeof(HeaacPredictorState);
-}
-
-// The state rows of every failed stream, the generator and predictor rows of those that keep them too (the set's
-// two lists, heaac_failed_lists): to the parking area (mode 0) or back (1)
-static void pl_park(HeaacPipeline *p, const Set *s, unsigned n_all, unsigned n_full, int mode)
-{
-    const unsigned *full = s->d_list + 2 * p->n;
-    heaac_rows(p->run, s->d_list, n_all, 256, p->d_state, p->d_park_state, p->words, mode);
-    if (!n_full) return;
-    heaac_rows(p->run, full, n_full, 64, p->d_rng, p->d_park_rng, 1, mode);
-    if (p->d_pred) heaac_rows(p->run, full, n_full, 256, p->d_pred, p->d_park_pred, pl_pred_row_bytes(p) / 4, mode);
-}
-
-// The GPU stage of a one-unit tick: the batch calls, the failed streams' state rows parked around them
-static int pl_run_batch(HeaacPipeline *p, Set *s)
-{
-    const size_t n = p->n;
-    int rc;
-    // streams whose unit failed: park their state rows (state, noise generator, predictors) before the launches ...
-    unsigned n_all = 0, n_full = 0;
-    rc = heaac_failed_lists(p->run, s->failed, n, s->h_list, s->d_list, &n_all, &n_full);
-    if (rc != HEAAC_OK) return rc;
-    size_t rows;
-    rc = heaac_park_grow(p->run, n_all, p->park_rows, 64, n, &rows);
-    if (rc != HEAAC_OK) return rc;
-    if (rows != p->park_rows) {
-        if (p->d_park_state) (void)hipFree(p->d_park_state);
-        if (p->d_park_rng) (void)hipFree(p->d_park_rng);
-        if (p->d_park_pred) (void)hipFree(p->d_park_pred);
-        p->d_park_state = NULL; p->d_park_rng = NULL; p->d_park_pred = NULL; p->park_rows = 0;
-        if (!devmem((void **)&p->d_park_state, rows * p->words * 4) || !devmem((void **)&p->d_park_rng, rows * 4) ||
-            (p->d_pred && !devmem((void **)&p->d_park_pred, rows * pl_pred_row_bytes(p))))
-            return HEAAC_ERR_NOMEM;
-        p->park_rows = rows;
-    }
-    if (n_all) {
-        pl_park(p, s, n_all, n_full, 0);
-        HIP_OK(hipGetLastError());
-    }
-    rc = heaac_spectral_tools_batch(p->dev, p->ncore, s->d_coeffs, s->d_tools, p->d_rng, p->d_rng, p->d_pred, p->d_pred, n,
-                                    (void *)p->run);
-    if (rc == HEAAC_OK)
-        rc = p->he ? heaac_he_decode_batch_ex(p->dev, p->he_cfg, p->downsampled ? HEAAC_HE_DOWNSAMPLED : 0, s->d_coeffs, s->d_ics,
-                                              s->d_sbr, p->d_hdr, PL_MAX_HDRS, s->d_ps,
-                                              p->d_state, p->d_state, s->d_pcm, HEAAC_PCM_S16_INTERLEAVED, n, (void *)p->run)
-                   : heaac_lc_decode_batch(p->dev, p->ncore, s->d_coeffs, s->d_ics, p->d_state, p->d_state, s->d_pcm,
-                                           HEAAC_PCM_S16_INTERLEAVED, n, (void *)p->run);
-    if (rc != HEAAC_OK) return rc;
-    // ... and put them back, with silence where the decode wrote
-    if (n_all) {
-        const size_t pcm_row = (size_t)p->nout * p->out_len;           // int16: an even count, so whole 32-bit words
-        pl_park(p, s, n_all, n_full, 1);
-        heaac_rows(p->run, s->d_list, n_all, 256, s->d_pcm, NULL, pcm_row / 2, 2);
-        HIP_OK(hipGetLastError());
-    }
-    return HEAAC_OK;
-}
-
-// The GPU stage of a tick of T > 1 units per stream: the streams calls, a unit that did not parse held by their masks
-// (no parking area, no row launches)
-static int pl_run_streams(HeaacPipeline *p, Set *s)
-{
-    const size_t n = p->n;
-    // a tick without a failed unit -- the usual one -- runs the plain streams kernels (NULL: no mask)
-    const uint8_t *hold_dsp = s->any_held ? s->d_hold : NULL, *hold_tools = s->any_held ? s->d_hold + p->nf : NULL;
-    int rc = heaac_spectral_tools_streams_ex(p->dev, p->ncore, s->d_coeffs, s->d_tools, p->d_rng, p->d_rng, p->d_pred,
+    const size_t n = p->n, nf = p->nf;
+    // GPU
+    HIP_OK(hipStreamWaitEvent(p->run, s->in_done, 0));
+    if (s->used) HIP_OK(hipStreamWaitEvent(p->run, s->out_done, 0));
+    // a tick without a failed unit -- the usual one -- runs the plain kernels (NULL: no mask)
+    const uint8_t *hold_dsp = s->any_held ? s->d_hold : NULL, *hold_tools = s->any_held ? s->d_hold + nf : NULL;
+    int rc = heaac_spectral_tools_streams_ex(p->dev, p->ncore, s->d.coeffs, s->d.tools, p->d_rng, p->d_rng, p->d_pred,
                                              p->d_pred, n, p->T, hold_tools, (void *)p->run);
     if (rc == HEAAC_OK)
-        rc = p->he ? heaac_he_decode_streams_ex(p->dev, p->he_cfg, p->downsampled ? HEAAC_HE_DOWNSAMPLED : 0, s->d_coeffs,
-                                                s->d_ics, s->d_sbr, p->d_hdr, PL_MAX_HDRS, s->d_ps, p->d_state, p->d_state,
+        rc = p->he ? heaac_he_decode_streams_ex(p->dev, p->he_cfg, p->downsampled ? HEAAC_HE_DOWNSAMPLED : 0, s->d.coeffs,
+                                                s->d.ics, s->d.sbr, p->d_hdr, PL_MAX_HDRS, s->d.ps, p->d_state, p->d_state,
                                                 s->d_pcm, HEAAC_PCM_S16_INTERLEAVED, n, p->T, hold_dsp, (void *)p->run)
-                   : heaac_lc_decode_streams_ex(p->dev, p->ncore, s->d_coeffs, s->d_ics, p->d_state, p->d_state, s->d_pcm,
+                   : heaac_lc_decode_streams_ex(p->dev, p->ncore, s->d.coeffs, s->d.ics, p->d_state, p->d_state, s->d_pcm,
                                                 HEAAC_PCM_S16_INTERLEAVED, n, p->T, hold_dsp, (void *)p->run);
-    return rc;
+    if (rc != HEAAC_OK) return rc;
+    HIP_OK(hipEventRecord(s->run_done, p->run));
+    // D2H
+    HIP_OK(hipStreamWaitEvent(p->out, s->run_done, 0));
+    HIP_OK(hipMemcpyAsync(s->h_pcm, s->d_pcm, nf * (size_t)p->nout * p->out_len * 2, hipMemcpyDeviceToHost, p->out));
+    HIP_OK(hipEventRecord(s->out_done, p->out));
+    s->used = 1;
+    p->submitted++;
+    return HEAAC_OK;
 }
 
 // A buffer pair of `have` bytes or units that must hold `needed`: the capacity to allocate, doubled from `first`
@@ -515,17 +427,13 @@ static int stg_grow(HeaacPipeline *p, size_t units)
 {
     Staging *g = &p->stg;
     if (units <= g->cap) return HEAAC_OK;
-    const size_t cap = pl_grown(units, g->cap, 64, p->nf), nc = cap * (size_t)p->ncore;
+    const size_t cap = pl_grown(units, g->cap, 64, p->nf);
     stg_free(g);
-    const bool ok =
-        pinned((void **)&g->h_coeffs, nc * 4096) && devmem((void **)&g->d_coeffs, nc * 4096) &&
-        pinned((void **)&g->h_ics, nc * sizeof(HeaacIcs)) && devmem((void **)&g->d_ics, nc * sizeof(HeaacIcs)) &&
-        pinned((void **)&g->h_tools, cap * sizeof(HeaacToolsFrame)) && devmem((void **)&g->d_tools, cap * sizeof(HeaacToolsFrame)) &&
-        (!p->he || (pinned((void **)&g->h_sbr, cap * sizeof(HeaacSbrFrame)) && devmem((void **)&g->d_sbr, cap * sizeof(HeaacSbrFrame)))) &&
-        (!p->set[0].d_ps || (pinned((void **)&g->h_ps, cap * sizeof(HeaacPsFrame)) && devmem((void **)&g->d_ps, cap * sizeof(HeaacPsFrame)))) &&
-        pinned((void **)&g->h_hold, 2 * cap) && devmem((void **)&g->d_hold, 2 * cap) &&
-        pinned((void **)&g->h_dest, cap * sizeof(uint32_t)) && devmem((void **)&g->d_dest, cap * sizeof(uint32_t));
-    if (!ok) { stg_free(g); return HEAAC_ERR_NOMEM; }
+    if (!(rec_alloc(p, &g->mem, &g->h, &g->d, cap) && heaac_pair(&g->mem, &g->h_hold, &g->d_hold, 2 * cap) &&
+          heaac_pair(&g->mem, &g->h_dest, &g->d_dest, cap * sizeof(uint32_t)))) {
+        stg_free(g);
+        return HEAAC_ERR_NOMEM;
+    }
     g->cap = cap;
     return HEAAC_OK;
 }
@@ -553,25 +461,17 @@ static int pl_fix_up(HeaacPipeline *p, Set *s, int *held)
     rc = heaac_upload_headers(p->tab, &p->hdr_uploaded, p->d_hdr, NULL, p->in);
     if (rc != HEAAC_OK) return rc;
     // scatter
-    const size_t nc = units * (size_t)p->ncore;
-    HIP_OK(hipMemcpyAsync(g->d_coeffs, g->h_coeffs, nc * 4096, hipMemcpyHostToDevice, p->in));
-    HIP_OK(hipMemcpyAsync(g->d_ics, g->h_ics, nc * sizeof(HeaacIcs), hipMemcpyHostToDevice, p->in));
-    HIP_OK(hipMemcpyAsync(g->d_tools, g->h_tools, units * sizeof(HeaacToolsFrame), hipMemcpyHostToDevice, p->in));
-    if (p->he) HIP_OK(hipMemcpyAsync(g->d_sbr, g->h_sbr, units * sizeof(HeaacSbrFrame), hipMemcpyHostToDevice, p->in));
-    if (g->d_ps) HIP_OK(hipMemcpyAsync(g->d_ps, g->h_ps, units * sizeof(HeaacPsFrame), hipMemcpyHostToDevice, p->in));
+    rc = rec_upload(p, &g->h, &g->d, units, false);
+    if (rc != HEAAC_OK) return rc;
     HIP_OK(hipMemcpyAsync(g->d_hold, g->h_hold, 2 * units, hipMemcpyHostToDevice, p->in));
     HIP_OK(hipMemcpyAsync(g->d_dest, g->h_dest, units * sizeof(uint32_t), hipMemcpyHostToDevice, p->in));
     HIP_OK(hipMemcpyAsync(p->d_g_ast, p->h_g_ast, m * sizeof(HeaacAacStream), hipMemcpyHostToDevice, p->in));
     if (p->he) HIP_OK(hipMemcpyAsync(p->d_g_sst, p->h_g_sst, m * sizeof(HeaacSbrStream), hipMemcpyHostToDevice, p->in));
     HeaacFixRows rows;
     memset(&rows, 0, sizeof(rows));
-    void *dst[HEAAC_FIX_ARRAYS] = { s->d_coeffs, s->d_ics, s->d_tools, s->d_sbr, s->d_ps };
-    const void *src[HEAAC_FIX_ARRAYS] = { g->d_coeffs, g->d_ics, g->d_tools, g->d_sbr, g->d_ps };
-    const size_t bytes[HEAAC_FIX_ARRAYS] = { (size_t)p->ncore * 4096, p->ncore * sizeof(HeaacIcs), sizeof(HeaacToolsFrame),
-                                             sizeof(HeaacSbrFrame), sizeof(HeaacPsFrame) };
     for (int k = 0; k < HEAAC_FIX_ARRAYS; k++) {
-        rows.dst[k] = (uint32_t *)dst[k]; rows.src[k] = (const uint32_t *)src[k];
-        rows.words[k] = dst[k] ? (uint32_t)(bytes[k] / 4) : 0;
+        rows.dst[k] = (uint32_t *)s->d.row[k]; rows.src[k] = (const uint32_t *)g->d.row[k];
+        rows.words[k] = (uint32_t)(p->row_bytes[k] / 4);
     }
     rc = heaac_launch_fix_scatter(p->in, &rows, g->d_dest, units, g->d_hold, s->d_hold, p->nf, p->d_list, m, p->d_g_ast, p->d_ast,
                                   p->d_g_sst, d_sst);
@@ -609,12 +509,12 @@ static int pl_submit_device(HeaacPipeline *p, Set *s, const uint8_t *const *au, 
     int rc;
     if (p->he) {
         rc = heaac_heaac_parse_device_streams(p->dev, &p->aac, p->d_ast, p->d_sst[p->sst_cur], p->d_sst[p->sst_cur ^ 1], s->d_bytes,
-                                              s->d_off, n, p->T, p->ncore, s->d_coeffs, s->d_ics, s->d_tools, p->d_info, p->d_hdr,
-                                              p->hdr_uploaded, s->d_sbr, s->d_ps, p->d_status, p->m_taken, s->d_hold, (void *)p->in);
+                                              s->d_off, n, p->T, p->ncore, s->d.coeffs, s->d.ics, s->d.tools, p->d_info, p->d_hdr,
+                                              p->hdr_uploaded, s->d.sbr, s->d.ps, p->d_status, p->m_taken, s->d_hold, (void *)p->in);
         if (rc == HEAAC_OK) p->sst_cur ^= 1;
     } else {
-        rc = heaac_aac_parse_device_streams(p->dev, &p->aac, p->d_ast, s->d_bytes, s->d_off, n, p->T, p->ncore, s->d_coeffs,
-                                            s->d_ics, s->d_tools, p->d_info, p->d_status, p->m_taken, s->d_hold, (void *)p->in);
+        rc = heaac_aac_parse_device_streams(p->dev, &p->aac, p->d_ast, s->d_bytes, s->d_off, n, p->T, p->ncore, s->d.coeffs,
+                                            s->d.ics, s->d.tools, p->d_info, p->d_status, p->m_taken, s->d_hold, (void *)p->in);
     }
     if (rc == HEAAC_OK)
         rc = heaac_launch_parse_status(p->in, p->d_status, p->d_info, p->he, p->aac.sbr == 0, status ? p->m_status : NULL,
@@ -639,6 +539,28 @@ static int pl_submit_device(HeaacPipeline *p, Set *s, const uint8_t *const *au, 
     return HEAAC_OK;
 }
 
+// The first two stages of a host-parse tick, up to in_done: the parser pool, then the records and the masks on `in`
+static int pl_submit_host(HeaacPipeline *p, Set *s, const uint8_t *const *au, const int *size, int *status, double t0)
+{
+    const size_t nf = p->nf;
+    p->job_au = au; p->job_size = size; p->job_status = status; p->job_set = s;
+    heaac_pool_run(p->pool, 0);
+    s->parse_ms = (float)(now_ms() - t0);
+    // new SBR headers of this tick (the table's storage never moves)
+    if (heaac_sbr_table_count(p->tab) > PL_MAX_HDRS) return HEAAC_ERR_ARG;
+    // H2D
+    if (s->used) HIP_OK(hipStreamWaitEvent(p->in, s->run_done, 0));
+    HIP_OK(hipEventRecord(s->in_start, p->in));
+    int rc = heaac_upload_headers(p->tab, &p->hdr_uploaded, p->d_hdr, NULL, p->in);
+    if (rc == HEAAC_OK) rc = rec_upload(p, &s->h, &s->d, nf, p->ncore == 1);
+    if (rc != HEAAC_OK) return rc;
+    s->any_held = memchr(s->h_hold, 1, nf) != NULL;
+    if (s->any_held) HIP_OK(hipMemcpyAsync(s->d_hold, s->h_hold, 2 * nf, hipMemcpyHostToDevice, p->in));
+    HIP_OK(hipEventRecord(s->in_done, p->in));
+    p->n_host += nf;
+    return HEAAC_OK;
+}
+
 extern "C" int heaac_pipeline_submit(HeaacPipeline *p, const uint8_t *const *au, const int *size, int *status)
 {
     if (!p || !au || !size) return HEAAC_ERR_ARG;
@@ -647,60 +569,8 @@ extern "C" int heaac_pipeline_submit(HeaacPipeline *p, const uint8_t *const *au,
     // the pinned inputs of this set are free once the H2D of the tick that used it last has finished
     if (s->used) HIP_OK(hipEventSynchronize(s->in_done));
     const double t0 = now_ms();
-    if (p->dp) {
-        const int rc = pl_submit_device(p, s, au, size, status, t0);
-        if (rc != HEAAC_OK) return rc;
-        return pl_submit_rest(p, s);
-    }
-    p->job_au = au; p->job_size = size; p->job_status = status; p->job_set = s;
-    heaac_pool_run(p->pool, 0);
-    s->parse_ms = (float)(now_ms() - t0);
-
-    // (nf: the frames of a tick, one per stream or T)
-    const size_t nf = p->nf, nc = nf * (size_t)p->ncore;
-    // new SBR headers of this tick (the table's storage never moves)
-    if (heaac_sbr_table_count(p->tab) > PL_MAX_HDRS) return HEAAC_ERR_ARG;
-    // H2D
-    if (s->used) HIP_OK(hipStreamWaitEvent(p->in, s->run_done, 0));
-    HIP_OK(hipEventRecord(s->in_start, p->in));
-    int rc = heaac_upload_headers(p->tab, &p->hdr_uploaded, p->d_hdr, NULL, p->in);
-    if (rc != HEAAC_OK) return rc;
-    HIP_OK(hipMemcpyAsync(s->d_coeffs, s->h_coeffs, nc * 4096, hipMemcpyHostToDevice, p->in));
-    HIP_OK(hipMemcpyAsync(s->d_ics, s->h_ics, nc * sizeof(HeaacIcs), hipMemcpyHostToDevice, p->in));
-    if (p->ncore == 1) {
-        // a mono stream uses channel 0 of the tools record only: the second channel's 3.5 KB stay on the host
-        // (the device copies were zeroed once and the kernel never reads them for one channel)
-        HIP_OK(hipMemcpy2DAsync(s->d_tools, sizeof(HeaacToolsFrame), s->h_tools, sizeof(HeaacToolsFrame),
-                                offsetof(HeaacToolsFrame, ch) + sizeof(HeaacToolsChannel), nf, hipMemcpyHostToDevice, p->in));
-    } else {
-        HIP_OK(hipMemcpyAsync(s->d_tools, s->h_tools, nf * sizeof(HeaacToolsFrame), hipMemcpyHostToDevice, p->in));
-    }
-    if (p->he) HIP_OK(hipMemcpyAsync(s->d_sbr, s->h_sbr, nf * sizeof(HeaacSbrFrame), hipMemcpyHostToDevice, p->in));
-    if (s->d_ps) HIP_OK(hipMemcpyAsync(s->d_ps, s->h_ps, nf * sizeof(HeaacPsFrame), hipMemcpyHostToDevice, p->in));
-    s->any_held = s->h_hold && memchr(s->h_hold, 1, nf) != NULL;
-    if (s->any_held) HIP_OK(hipMemcpyAsync(s->d_hold, s->h_hold, 2 * nf, hipMemcpyHostToDevice, p->in));
-    HIP_OK(hipEventRecord(s->in_done, p->in));
-    p->n_host += nf;
-    return pl_submit_rest(p, s);
-}
-
-// GPU stage and D2H of the tick in set s, behind its in_done
-static int pl_submit_rest(HeaacPipeline *p, Set *s)
-{
-    const size_t nf = p->nf;
-    // GPU
-    HIP_OK(hipStreamWaitEvent(p->run, s->in_done, 0));
-    if (s->used) HIP_OK(hipStreamWaitEvent(p->run, s->out_done, 0));
-    const int rc = p->T > 1 || p->dp ? pl_run_streams(p, s) : pl_run_batch(p, s);
-    if (rc != HEAAC_OK) return rc;
-    HIP_OK(hipEventRecord(s->run_done, p->run));
-    // D2H
-    HIP_OK(hipStreamWaitEvent(p->out, s->run_done, 0));
-    HIP_OK(hipMemcpyAsync(s->h_pcm, s->d_pcm, nf * (size_t)p->nout * p->out_len * 2, hipMemcpyDeviceToHost, p->out));
-    HIP_OK(hipEventRecord(s->out_done, p->out));
-    s->used = 1;
-    p->submitted++;
-    return HEAAC_OK;
+    const int rc = p->dp ? pl_submit_device(p, s, au, size, status, t0) : pl_submit_host(p, s, au, size, status, t0);
+    return rc != HEAAC_OK ? rc : pl_submit_rest(p, s);
 }
 
 extern "C" int heaac_pipeline_collect(HeaacPipeline *p, const int16_t **pcm)

@@ -59,14 +59,16 @@ int heaac_pipeline_submit(HeaacPipeline *p, const uint8_t *const *au, const int 
  * heaac_lc_decode_streams_ex), the stream's state on chip across the T frames.
  *   submit:  au[n_streams * T] / size[...] / status[...], unit t of stream s at s * T + t.
  *   collect: [n_streams][T][len][channels] int16.
- * Depth, event order and heaac_pipeline_timing are those of the one-unit tick.  Every unit is treated as the one-unit
- * tick treats it: one that does not parse gives silence for its frame and leaves the stream as heaac_pipeline_submit
- * describes -- here through the hold masks of the streams calls instead of parking the state around the batch calls
- * (the two must agree, and tests/test_pipeline_streams_gpu.py compares them).
+ * Depth, event order and heaac_pipeline_timing are those of the one-unit tick, which is this tick with T = 1: one code
+ * path for every T.  A unit that does not parse gives silence for its frame and leaves the stream as
+ * heaac_pipeline_submit describes, through the hold masks of the streams calls (DESIGN.md s7;
+ * tests/test_pipeline_streams_gpu.py holds "T units in one tick = T ticks of one unit" and compares the one-unit tick
+ * with one codec context per stream).
  * A stream that has run out of units passes size = 0 for the rest of its tick: the parser answers size <= 0 with
  * HEAAC_PARSE_ERR_ARG before it looks at the buffer, which is a unit that does not parse -- status
  * HEAAC_PARSE_ERR_ARG, silence, the stream untouched -- with T = 1 and with T > 1 alike.
- * frames_per_tick = 1 is heaac_pipeline_create (the batch calls).  HEAAC_ERR_ARG for frames_per_tick = 0, for one that
+ * frames_per_tick = 1 is heaac_pipeline_create (a tick in which every unit parsed passes no mask, and with T = 1 the
+ * streams calls then launch the batch kernels).  HEAAC_ERR_ARG for frames_per_tick = 0, for one that
  * heaac_he_decode_streams refuses on a device created for n_streams * T frames, and for what heaac_pipeline_create
  * refuses; HEAAC_ERR_NODEVICE without a usable device. */
 int heaac_pipeline_create_streams(HeaacPipeline **out, const HeaacAacConfig *aac, int he_cfg,
@@ -93,8 +95,8 @@ size_t heaac_pipeline_frames_per_tick(const HeaacPipeline *p);     /* T of the c
  * is one).  It does not wait for the decode or for earlier ticks' downloads.  The submit of a host-parse pipeline only
  * enqueues.  collect, timing, destroy and the depth are the same; heaac_pipeline_timing's ms[0] is submit's host time up
  * to the point the tick's records are complete (pack, the wait, the host parser's part) and ms[1] the copy-in stream's
- * time for the same (upload, the parse kernels, the fix-up copies and kernels).  The GPU stage runs the *_streams_ex
- * calls for every frames_per_tick, 1 included.
+ * time for the same (upload, the parse kernels, the fix-up copies and kernels).  The GPU stage is the host-parse
+ * pipeline's.
  *
  * HEAAC_ERR_ARG for an unknown flag bit; with HEAAC_PIPELINE_DEVICE_PARSE for what the device parsers refuse: an object
  * type other than AAC-LC or AAC-Main, n_streams * frames_per_tick beyond their 32-bit unit index, and a mono

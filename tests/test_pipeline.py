@@ -239,7 +239,7 @@ def test_the_parse_slices_take_no_stack_per_stream(pkg):
     text = subprocess.run([objdump, "-d", "-C", "--no-show-raw-insn", pkg.LIB_PATH], check=True, capture_output=True,
                           text=True).stdout
     fn, seen, moves = None, set(), []
-    walkers = ("parse_slice", "commit_slice", "heaac_pool_run", "worker(", "pipeline_submit", "neutral(",
+    walkers = ("parse_slice", "fix_slice", "commit_slice", "heaac_pool_run", "worker(", "pipeline_submit", "neutral(",
                "lp_settle(", "lp_after_streams(", "lp_gain_list(")
     for line in text.splitlines():
         m = re.match(r"^[0-9a-f]+ <(.*)>:$", line)
@@ -250,10 +250,10 @@ def test_the_parse_slices_take_no_stack_per_stream(pkg):
             continue
         if fn and re.search(r"\s(mov|sub|lea)\w*\s+[^$\s]\S*,%rsp$", line):
             moves.append((fn, line.strip()))
-    # every per-stream loop of the two pipelines -- the parse slices and the stages of the layout pipeline's submit that
-    # walk the streams -- and the pool (csrc/host_common.hip) that runs them
-    assert {"parse_slice(HeaacPipeline*, int)", "lp_parse_slice(HeaacLayoutPipeline*, int)",
-            "lp_commit_slice(HeaacLayoutPipeline*, int)", "pool_worker(void*)",
+    # every per-stream loop of the two pipelines -- the parse slices, the fix-up slice of a device-parse tick and the
+    # stages of the layout pipeline's submit that walk the streams -- and the pool (csrc/host_common.hip) that runs them
+    assert {"parse_slice(HeaacPipeline*, int)", "fix_slice(HeaacPipeline*, int)",
+            "lp_parse_slice(HeaacLayoutPipeline*, int)", "lp_commit_slice(HeaacLayoutPipeline*, int)", "pool_worker(void*)",
             "heaac_pool_run(HeaacPool*, int)"} <= seen, sorted(seen)
     for stage in ("lp_settle(", "lp_after_streams(", "lp_gain_list("):
         assert any(fn.startswith(stage) for fn in seen), (stage, sorted(seen))

@@ -1,8 +1,12 @@
 """The pipeline's streams form (heaac_pipeline_create_streams: T access units per stream and tick, the streams calls with
-hold masks on the GPU) against the pipeline as it was: Pipeline(..., frames_per_tick=1), fed the same units over K * T
-ticks, runs the batch calls with the failed streams' state parked around them.  PCM and status bit for bit; later ticks
-depend on the state carried across the tick boundary, so the state is covered through the PCM."""
+hold masks on the GPU) against the same pipeline at one unit per tick: Pipeline(..., frames_per_tick=1), fed the same
+units over K * T ticks.  PCM and status bit for bit: T units in one tick = T ticks of one unit; later ticks depend on
+the state carried across the tick boundary, so the state is covered through the PCM.  Both sides are one code path (a
+one-unit tick is held by the same masks), so the one-unit pipeline is itself compared, on the damaged corpus, with
+something that shares no code with it: one heaac_codec_decode context per stream (csrc/shim.hip), which refuses a
+damaged unit before it touches the DSP -- no mask, nothing to hold."""
 import copy
+import ctypes as C
 import itertools
 
 import numpy as np
@@ -166,3 +170,58 @@ def test_damaged_units_in_streams_ticks(pkg, dev, name, T):
         _compare(got, status, ref, ref_status, n, T)
         results.append(got)
     assert np.array_equal(results[0], results[1])
+
+
+# The configurations of the cases as a codec context takes them (AudioSpecificConfig: tests/test_pipeline_vs_codec_gpu.py,
+# tests/test_shim_gpu.py), with the samples and channels of one decoded unit.  The AAC-LC / Main ones end in the sync
+# extension 0x2b7 with sbrPresentFlag = 0: _case() writes their units with extras, some of which carry a fill element
+# of SBR type, and a context left to implicit signalling would turn SBR on at the first of them; TP._cfg (sbr = 0)
+# tells the pipeline explicitly that there is none.
+def _lc_asc(aot, ch):
+    return bytes([(aot << 3) | 1, 0x80 | (ch << 3), 0x56, 0xE5, 0x00])
+
+
+CODEC = {"hev2": (bytes([0xEB, 0x09, 0x88, 0x00]), 2048, 2), "hev1": (bytes([0x2B, 0x11, 0x88, 0x00]), 2048, 2),
+         "hev1_down": (bytes([0x2B, 0x13, 0x08, 0x00]), 1024, 2), "lc_stereo_main": (_lc_asc(1, 2), 1024, 2),
+         "lc_mono": (_lc_asc(2, 1), 1024, 1)}
+
+
+@pytest.mark.parametrize("name", CASES)
+def test_one_unit_ticks_equal_codec_contexts_on_damaged_units(pkg, dev, name):
+    """The reference of the tests above, anchored: the damaged corpus of T = 5 through the one-unit pipeline and through
+    one codec context per stream, unit for unit -- refused there <=> negative status and silence here, otherwise the
+    same PCM.  Stream 5 is left out: its damaged units are empty, and a context does not refuse a packet of no bytes
+    (heaac_codec_decode returns 0 for it without calling the decoder)."""
+    from test_shim_gpu import HeaacCodecContext, HeaacPacket
+    lib = pkg.lib()
+    T = 5
+    m4, cfg, n, units, where, damaged = _damage(pkg, name, T)
+    _both_refusal_kinds_occur(pkg, name, m4, damaged)
+    got, status = _reference(pkg, m4, cfg, n, units, K * T)
+    asc, length, nout = CODEC[name]
+    assert got.shape == (K * T, n, length, nout)
+    codec = C.c_void_p.in_dll(lib, "heaac_aac_decoder")
+    out = (C.c_int16 * (192000 // 2))()
+    for i in range(n):
+        if i == 5:
+            continue
+        ctx = HeaacCodecContext(cfg=-1, extradata=asc, extradata_size=len(asc))
+        assert lib.heaac_codec_open(C.byref(ctx), C.c_void_p(C.addressof(codec))) == 0
+        refused = []
+        for u in range(K * T):
+            b = units[i][u]
+            buf = C.create_string_buffer(b, len(b))
+            pkt = HeaacPacket(C.cast(buf, C.c_void_p), len(b))
+            size = C.c_int(192000)
+            used = lib.heaac_codec_decode(C.byref(ctx), out, C.byref(size), C.byref(pkt))
+            if used < 0:
+                assert status[u][i] < 0 and not got[u][i].any(), (name, i, u, used, int(status[u][i]))
+                refused.append(u)
+                continue
+            assert size.value == length * nout * 2, (name, i, u)
+            pcm = np.frombuffer(out, np.int16, length * nout).reshape(length, nout)
+            assert np.array_equal(pcm, got[u][i]), (name, i, u, int(status[u][i]))
+        assert lib.heaac_codec_close(C.byref(ctx)) == 0
+        # exactly the damaged units are refused, and the stream is heard again after them
+        assert refused == sorted(where.get(i, [])), (name, i, refused)
+        assert got[max(refused) + 1:, i].any() if refused else got[:, i].any(), (name, i)

@@ -1,5 +1,6 @@
 """What damaged units cost the host-buffer pipeline: n HE-AACv2 streams, a share of them handed a unit that does not parse
-in every tick (silence for the tick, state parked and put back).  ms per tick, ticks collected one by one.
+in every tick (silence for the tick, the stream held by the masks of the streams calls).  ms per tick and the mean GPU
+stage of heaac_pipeline_timing, ticks collected one by one.
 usage: python tools/damage_rate.py [n streams] [ticks]"""
 import ctypes as C, importlib, json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -24,7 +25,7 @@ for t in range(ticks):
         aus.append(TP._write_au(rng, 6, 2, False, extras=False, sbr=(bits, False), quiet=True)[0])
     good.append(aus)
 bad = C.create_string_buffer(bytes([0x40, 0]) + bytes(8), 10)      # a coupling element: refused, nothing moves
-res = {}
+res, gpu = {}, {}
 for share in (0.0, 0.001, 0.01, 0.1):
     failing = rng.random(n) < share
     pl = pkg.Pipeline(cfg, pkg.CFG_HEV2, n, threads=0)
@@ -36,8 +37,12 @@ for share in (0.0, 0.001, 0.01, 0.1):
         frames.append((keep, ptrs, sizes))
     pl.submit_raw(frames[0][1], frames[0][2]); pl.collect()
     t0 = time.perf_counter()
+    stage = []
     for t in range(1, ticks):
         pl.submit_raw(frames[t][1], frames[t][2]); pl.collect()
+        stage.append(pl.timing()["gpu"])
     res[share] = (time.perf_counter() - t0) / (ticks - 1) * 1e3
+    gpu[share] = sum(stage) / len(stage)
     pl.close()
-print(json.dumps(dict(streams=n, ms_per_tick_by_failing_share={str(k): round(v, 2) for k, v in res.items()})))
+print(json.dumps(dict(streams=n, ms_per_tick_by_failing_share={str(k): round(v, 2) for k, v in res.items()},
+                      gpu_stage_ms_by_failing_share={str(k): round(v, 3) for k, v in gpu.items()})))
